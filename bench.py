@@ -20,6 +20,9 @@ all-gather of the emitted code / grain indices and the loss pair; it runs asynch
 and every exchange is waited for and unpacked inside the timed region.
 
 Contract: python bench.py --gpus N --steps K --warmup W  -> ONE JSON line (rank 0).
+A plain run sets up, warms up, times exactly K steps, writes the last step's outputs if --dump-outputs DIR is given and
+prints the line.  --full adds everything else after the timed region: repeated blocks, the parity check against the oracle,
+the model-order legs, the serial step, the dominant kernel's roofline, every BASELINE config and the CPU baselines.
 `--gpus N` with no RANK in the environment makes this process a launcher: it starts N fresh rank
 processes (one per GPU, RCCL rendezvous on 127.0.0.1) BEFORE anything touches a GPU, relays rank 0's
 JSON line and exits non-zero if any rank fails.  Under `python -m torch.distributed.run` (RANK set) it is
@@ -46,10 +49,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=40)
-    ap.add_argument("--repeats", type=int, default=7,
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also measure and check everything beside the headline (see the module docstring); "
+                         "the --no-* / --configs / --cpu-seconds options below act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (the arrays its caller receives) as DIR/<name>.npy, float32 / "
+                         "float64 (integers), at most 56 MiB in all: an array that does not fit keeps a fixed, seeded sample of its "
+                         "images, whose indices go to DIR/<name>_images.npy")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="the timed region is measured this many times back to back inside one run (each block = exactly --steps "
                          "steps, barrier + synchronize on both sides, max over ranks); ms_per_step / value are the MEDIAN block, "
-                         "min / max are reported beside it (a 20-step block is 4 ms: launch ramp and box variance dominate one block)")
+                         "min / max are reported beside it (a 20-step block is 4 ms: launch ramp and run-to-run variance dominate one block). "
+                         "Default 1 (the timed steps are exactly --steps), 7 with --full")
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak")
     ap.add_argument("--batch", type=int, default=None,
                     help="weak: images per GPU (default 256); strong: GLOBAL batch (default 1024)")
@@ -67,7 +78,7 @@ def parse():
                          "scores the branches against E W, no conv is computed for decided tokens; same codes); model_fold: the "
                          "model order for loss-free inference by the fold (codes + z_q = codebook[code], no loss)")
     ap.add_argument("--no-model-order", action="store_true",
-                    help="default command only (1 GPU, weak, --path routed): skip the short second measurement of the "
+                    help="--full, default command only (1 GPU, weak, --path routed): skip the short second measurement of the "
                          "model order (--path model: the same step behind the models' 1x1 quant_conv, as one op) that is "
                          "reported under 'model_order' beside the headline")
     ap.add_argument("--spinup", type=int, default=100,
@@ -78,13 +89,16 @@ def parse():
                          "with its own outputs / workspace / exchange buffers, so a step's latency-bound tail (resolver, "
                          "list kernel, exchange) runs under the next batch's pass 1; 1 = strictly serial")
     ap.add_argument("--configs", choices=["auto", "full", "small", "off"], default="auto",
-                    help="default command only (1 GPU, weak, --path routed, filter): after the timed region, measure and check every "
+                    help="--full, default command only (1 GPU, weak, --path routed, filter): after the timed region, measure and check every "
                          "BASELINE.json config in the reference's own op order (pixels -> entropy map / feature-router gate -> select + "
                          "quant_conv + assign) and report them under 'configs'; auto = full at the default batch, small when --batch is given")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 7 if a.full else 1
+    return a
 
 
 # ------------------------------------------------------------------------------------------------
@@ -255,6 +269,33 @@ def cpu_baseline(E, target_s):
     return res
 
 
+DUMP_BUDGET = 56 << 20         # bytes --dump-outputs may write in all (the .npy headers fit in the margin to 64 MB)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array of `arrays` (device tensors, batch axis first) as path/<name>.npy, integers as float64 (exact),
+    floats as float32.  Smallest first; an array larger than what is left of DUMP_BUDGET keeps the images of a fixed, seeded
+    sample (the first n of one seeded permutation, in order), whose indices go to path/<name>_images.npy"""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    left = DUMP_BUDGET
+    for name, t in sorted(arrays.items(), key=lambda kv: (kv[1].numel(), kv[0])):
+        t = t.detach().to(torch.float32 if t.is_floating_point() else torch.float64)
+        nbytes = t.numel() * t.element_size()
+        if nbytes > left:
+            per = nbytes // t.shape[0] + 8                     # + its entry in the index file
+            n = min(t.shape[0] - 1, left // per)
+            if n < 1:
+                raise SystemExit("bench.py --dump-outputs: no room for one image of %r within %d bytes" % (name, DUMP_BUDGET))
+            idx = np.sort(np.random.default_rng(0).permutation(t.shape[0])[:n])
+            t = t.index_select(0, torch.from_numpy(idx).to(t.device))
+            np.save(os.path.join(path, name + "_images.npy"), idx.astype(np.float64))
+            nbytes = t.numel() * t.element_size() + idx.size * 8
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy())
+        left -= nbytes
+
+
 # ------------------------------------------------------------------------------------------------
 # workloads
 # ------------------------------------------------------------------------------------------------
@@ -418,6 +459,17 @@ class WeakDual:
         if ev:
             ev[1].record()
         return o.codes, o.grain, o.loss
+
+    def outputs(self, o):
+        """what the step hands its caller, by the routed op's names (intermediates such as h_dual are not outputs)"""
+        d = {"codes": o.codes, "indices": o.grain, "codebook_mask": o.cmask, "gate": o.gate}
+        if o.zq is not None:
+            d["zq"] = o.zq
+        if self.a.path not in ("tokens", "tokens_model", "tokens_fold", "model_fold"):      # these paths compute no loss
+            d["loss"] = o.loss
+        if self.permuter is not None:
+            d.update(zip(("coarse_content", "coarse_position", "coarse_segment", "fine_content", "fine_position", "fine_segment"), o.seq))
+        return d
 
     def dominant(self, o, ev):
         """the dominant kernel alone (pass 1 of the assign), same launch geometry"""
@@ -650,6 +702,9 @@ class StrongTriple:
         if ev:
             ev[1].record()
         return o.codes, o.grain, o.loss
+
+    def outputs(self, o):
+        return {"gate_logits": o.logits, "zq": o.zq, "codes": o.codes, "loss": o.loss, "indices": o.grain, "codebook_mask": o.cmask}
 
     def dominant(self, o, ev):
         from dynamicvectorquantization_amd import _lib
@@ -1132,12 +1187,14 @@ def run_rank(a):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)   # per block: the slowest rank
         dts = [float(v) for v in tt.tolist()]
     dt = float(np.median(dts))
+    if a.dump_outputs and rank == 0:       # before anything below reuses a slot's buffers
+        dump_outputs(a.dump_outputs, wl.outputs(wl.slots[(nstep[0] - 1) % S]))
 
     # the exchange alone: pack kernel -> all-gather -> unpack kernel, serial on one stream (HIP events), max over ranks.  Inside the
     # timed region it is launched async and completed two or three steps later (hidden under the next batches' pass 1); this is
     # what an UN-hidden exchange would add to a step (DESIGN.md section 6 states both predictions).
     exchange_ms = None
-    if xchs:
+    if xchs and a.full:
         torch.cuda.synchronize()
         o0 = wl.slots[0]
         x = CodeExchange(o0.codes, o0.grain, K, wl.Bglobal, numel_per_image=H * W * D)    # its own buffers: the slots' results stay for the parity check
@@ -1160,7 +1217,7 @@ def run_rank(a):
             exchange_ms = float(tx.item())
 
     parity = None
-    if not a.no_parity:
+    if a.full and not a.no_parity:
         # every rank checks ITS images against the oracle, after the timed region, on the last step's outputs
         try:
             import ctypes
@@ -1203,7 +1260,8 @@ def run_rank(a):
     # the model order beside the headline: the same step behind the models' 1x1 quant_conv (select -> conv -> assign as ONE op,
     # --path model), a short second measurement on the same streams, its own inputs and its own parity check
     model_order = None
-    if (world == 1 and a.scaling == "weak" and a.path == "routed" and a.mode == "filter" and not a.no_model_order and not force_xch):
+    if (a.full and world == 1 and a.scaling == "weak" and a.path == "routed" and a.mode == "filter" and not a.no_model_order
+            and not force_xch):
         import copy
 
         def side_leg(path, note):
@@ -1257,122 +1315,123 @@ def run_rank(a):
         model_order["tokens_fold"] = side_leg("tokens_fold", "bench.py --path tokens_fold: stage 2's tokenisation of a stage-1 checkpoint (codes only "
                                                              "+ permuter) with the quant_conv folded into the codebook")
 
-    # the same K steps strictly serial (one stream, one slot's buffers): what a caller without stream slots gets
-    # (HIP events around blocks of >= 200 steps: with the driver's --steps 20 a wall-clock bracket of 20 steps = 4 ms carried the
-    # synchronize / first-launch latency and the clock ramp after the idle gap -- 0.241 against 0.223 ms on the same box)
-    serial_ms, serial_blocks = None, None
-    n_ser = max(a.steps, 200)
-    if S > 1:
-        serial_blocks = []
-        for _ in range(10):
-            wl.step(wl.slots[0])
-        for r in range(R):
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            torch.cuda.synchronize()
-            for _ in range(5):
+    serial_ms, serial_blocks, roof = None, None, None
+    if a.full:
+        # the same K steps strictly serial (one stream, one slot's buffers): what a caller without stream slots gets
+        # (HIP events around blocks of >= 200 steps: with --steps 20 a wall-clock bracket of 20 steps = 4 ms carried the
+        # synchronize / first-launch latency and the clock ramp after the idle gap -- 0.241 against 0.223 ms on the same GPU)
+        n_ser = max(a.steps, 200)
+        if S > 1:
+            serial_blocks = []
+            for _ in range(10):
                 wl.step(wl.slots[0])
-            e0.record()
-            for _ in range(n_ser):
-                wl.step(wl.slots[0])
-            e1.record()
-            torch.cuda.synchronize()
-            serial_blocks.append(e0.elapsed_time(e1) / n_ser)
-        serial_ms = float(np.median(serial_blocks))
-    # the step's ops (all their kernels) and, below, the dominant kernel alone: HIP events on the launch stream, serial,
-    # after the timed region (inside it the ops of consecutive steps overlap across the stream slots)
-    nev = 200                                                 # (not --steps: 20 brackets are too few for a 2 % question)
-    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nev)]
-    for i in range(-3, nev):
-        wl.step(wl.slots[0], ev[i] if i >= 0 else None)
-    torch.cuda.synchronize()
-    op_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
-    if serial_ms is None:
-        serial_ms = dt / a.steps * 1e3
-    # the dominant kernel alone, HIP events on the launch stream, after the timed region
-    dom_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nev)]
-    scratch = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
-    for i in range(-3, nev):
-        # the profiling mode leaves its workspace's queue counters dirty; they are zeroed HERE, in front of the bracket, and the
-        # workspace declared clean, so that the events enclose the pass-1 kernel and nothing else (rounds 1-4 had the op's own
-        # 5-us counter-zero kernel inside the bracket)
-        lw = getattr(wl.prep_dom, "_last_ws", None)
-        if lw is not None and hasattr(lw[1], "clean"):
-            lw[1].t[:min(lw[1].t.numel(), 4 << 20)].zero_()
-            lw[1].clean = True
-        wl.dominant(wl.slots[0], dom_ev[i] if i >= 0 else scratch)
-    torch.cuda.synchronize()
-    dom_ms_bracketed = float(np.mean([s.elapsed_time(e) for s, e in dom_ev]))
-    dom_ms = dom_ms_bracketed
-    if a.mode == "filter":
-        # The same kernel BACK TO BACK: NP launches between ONE pair of events, each through a _CodebookPrep (workspace) of its
-        # own that was zeroed and declared clean in front of the bracket -- so the bracket holds NP pass-1 kernels and nothing
-        # else, and the event / first-launch latency (4-7 % of a single-launch bracket; rocprofv3's per-kernel duration has none)
-        # is amortised.  This is `roofline.kernel_ms`; the single-launch bracket stays beside it as `kernel_ms_bracketed`.
-        NP = 8
-        keep = wl.prep_dom
-        preps = [_CodebookPrep() for _ in range(NP)]
+            for r in range(R):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                torch.cuda.synchronize()
+                for _ in range(5):
+                    wl.step(wl.slots[0])
+                e0.record()
+                for _ in range(n_ser):
+                    wl.step(wl.slots[0])
+                e1.record()
+                torch.cuda.synchronize()
+                serial_blocks.append(e0.elapsed_time(e1) / n_ser)
+            serial_ms = float(np.median(serial_blocks))
+        # the step's ops (all their kernels) and, below, the dominant kernel alone: HIP events on the launch stream, serial,
+        # after the timed region (inside it the ops of consecutive steps overlap across the stream slots)
+        nev = 200                                                 # (not --steps: 20 brackets are too few for a 2 % question)
+        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nev)]
+        for i in range(-3, nev):
+            wl.step(wl.slots[0], ev[i] if i >= 0 else None)
+        torch.cuda.synchronize()
+        op_ms = float(np.mean([s.elapsed_time(e) for s, e in ev]))
+        if serial_ms is None:
+            serial_ms = dt / a.steps * 1e3
+        # the dominant kernel alone, HIP events on the launch stream, after the timed region
+        dom_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(nev)]
+        scratch = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
+        for i in range(-3, nev):
+            # the profiling mode leaves its workspace's queue counters dirty; they are zeroed HERE, in front of the bracket, and the
+            # workspace declared clean, so that the events enclose the pass-1 kernel and nothing else (rounds 1-4 had the op's own
+            # 5-us counter-zero kernel inside the bracket)
+            lw = getattr(wl.prep_dom, "_last_ws", None)
+            if lw is not None and hasattr(lw[1], "clean"):
+                lw[1].t[:min(lw[1].t.numel(), 4 << 20)].zero_()
+                lw[1].clean = True
+            wl.dominant(wl.slots[0], dom_ev[i] if i >= 0 else scratch)
+        torch.cuda.synchronize()
+        dom_ms_bracketed = float(np.mean([s.elapsed_time(e) for s, e in dom_ev]))
+        dom_ms = dom_ms_bracketed
+        if a.mode == "filter":
+            # The same kernel BACK TO BACK: NP launches between ONE pair of events, each through a _CodebookPrep (workspace) of its
+            # own that was zeroed and declared clean in front of the bracket -- so the bracket holds NP pass-1 kernels and nothing
+            # else, and the event / first-launch latency (4-7 % of a single-launch bracket; rocprofv3's per-kernel duration has none)
+            # is amortised.  This is `roofline.kernel_ms`; the single-launch bracket stays beside it as `kernel_ms_bracketed`.
+            NP = 8
+            keep = wl.prep_dom
+            preps = [_CodebookPrep() for _ in range(NP)]
 
-        def zero_all():
-            for pp in preps:
-                lw = getattr(pp, "_last_ws", None)
-                if lw is not None and hasattr(lw[1], "clean"):
-                    lw[1].t[:min(lw[1].t.numel(), 4 << 20)].zero_()
-                    lw[1].clean = True
-        blocks = []
-        for r in range(-2, 12):
-            zero_all()
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            for pp in preps:
-                wl.prep_dom = pp
-                wl.dominant(wl.slots[0], None)
-            e1.record()
-            torch.cuda.synchronize()
-            if r >= 0:
-                blocks.append(e0.elapsed_time(e1) / NP)
-        wl.prep_dom = keep
-        del preps
-        dom_ms = float(np.median(blocks))
-    N = wl.dominant_tokens()                                  # tokens per launch of the dominant kernel
-    per_token = D * 4 + 8 + 4 + (D * 4 if a.path not in ("tokens", "tokens_model", "tokens_fold") else 0)   # z read + int64 code + mask (+ z_q write)
-    alg_bytes = N * per_token + K * D * 4                     # codebook once per launch
-    alg_flops = 2.0 * K * D * N
-    gbs = alg_bytes / (dom_ms * 1e-3) / 1e9
-    tfs = alg_flops / (dom_ms * 1e-3) / 1e12
-    traffic, tsrc = None, None
-    tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
-    if os.path.exists(tpath):
-        try:
-            tj = json.load(open(tpath))
-            traffic = tj.get(a.mode if a.path in ("select", "model2") else ("routed" if a.path not in ("model", "tokens_fold", "model_fold") else a.path), {}).get("hbm_bytes_per_launch")
-            tsrc = "profiles/pmc_traffic.json (rocprofv3 --pmc passes of this command, collected by tools/pmc_traffic.py; not re-measured in this run)"
-        except Exception:
-            traffic = None
-    # rocprofv3 --kernel-trace --stats duration of the same kernel, if a summary made from THESE sources is committed
-    rocprof_ms = None
-    for mname in ("bench_kernel_stats.%s.meta.json" % a.path, "bench_kernel_stats.meta.json"):     # per path, then the default path's
-        try:
-            meta = json.load(open(os.path.join(ROOT, "profiles", mname)))
-            if meta.get("source_sha16") == source_sha16() and meta.get("path") == a.path and meta.get("scaling") == a.scaling:
-                rocprof_ms = meta.get("dominant_kernel_avg_ms")
-                break
-        except Exception:
-            pass
-    if a.mode == "filter":
-        roof = {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": gbs / HBM_PEAK_GBS, "traffic": traffic}
-    else:
-        roof = {"bound": "mfma", "achieved": tfs, "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                "frac": tfs / FP32_MFMA_PEAK_TF, "traffic": traffic}
-    roof.update({"kernel": wl.dominant_kernel_name(), "kernel_ms": dom_ms, "kernel_ms_bracketed": dom_ms_bracketed,
-                 "kernel_ms_rocprof": rocprof_ms,
-                 "serial_over_kernel": (serial_ms / dom_ms) if (serial_ms and dom_ms) else None,
-                 "algorithmic_bytes": alg_bytes, "algorithmic_flops": alg_flops, "fp16_mfma_frac_of_2500": tfs / 2500.0,
-                 "whole_op_ms": op_ms, "target_frac": 0.70, "target_met": bool(gbs / HBM_PEAK_GBS >= 0.70)})
-    # (what the fields mean -- the brackets, the byte count, where `traffic` and `kernel_ms_rocprof` come from -- is DESIGN.md
-    # section 5; the line itself stays short enough for the driver's record to hold all of it)
+            def zero_all():
+                for pp in preps:
+                    lw = getattr(pp, "_last_ws", None)
+                    if lw is not None and hasattr(lw[1], "clean"):
+                        lw[1].t[:min(lw[1].t.numel(), 4 << 20)].zero_()
+                        lw[1].clean = True
+            blocks = []
+            for r in range(-2, 12):
+                zero_all()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                for pp in preps:
+                    wl.prep_dom = pp
+                    wl.dominant(wl.slots[0], None)
+                e1.record()
+                torch.cuda.synchronize()
+                if r >= 0:
+                    blocks.append(e0.elapsed_time(e1) / NP)
+            wl.prep_dom = keep
+            del preps
+            dom_ms = float(np.median(blocks))
+        N = wl.dominant_tokens()                                  # tokens per launch of the dominant kernel
+        per_token = D * 4 + 8 + 4 + (D * 4 if a.path not in ("tokens", "tokens_model", "tokens_fold") else 0)   # z read + int64 code + mask (+ z_q write)
+        alg_bytes = N * per_token + K * D * 4                     # codebook once per launch
+        alg_flops = 2.0 * K * D * N
+        gbs = alg_bytes / (dom_ms * 1e-3) / 1e9
+        tfs = alg_flops / (dom_ms * 1e-3) / 1e12
+        traffic, tsrc = None, None
+        tpath = os.path.join(ROOT, "profiles", "pmc_traffic.json")
+        if os.path.exists(tpath):
+            try:
+                tj = json.load(open(tpath))
+                traffic = tj.get(a.mode if a.path in ("select", "model2") else ("routed" if a.path not in ("model", "tokens_fold", "model_fold") else a.path), {}).get("hbm_bytes_per_launch")
+                tsrc = "profiles/pmc_traffic.json (rocprofv3 --pmc passes of this command, collected by tools/pmc_traffic.py; not re-measured in this run)"
+            except Exception:
+                traffic = None
+        # rocprofv3 --kernel-trace --stats duration of the same kernel, if a summary made from THESE sources is committed
+        rocprof_ms = None
+        for mname in ("bench_kernel_stats.%s.meta.json" % a.path, "bench_kernel_stats.meta.json"):     # per path, then the default path's
+            try:
+                meta = json.load(open(os.path.join(ROOT, "profiles", mname)))
+                if meta.get("source_sha16") == source_sha16() and meta.get("path") == a.path and meta.get("scaling") == a.scaling:
+                    rocprof_ms = meta.get("dominant_kernel_avg_ms")
+                    break
+            except Exception:
+                pass
+        if a.mode == "filter":
+            roof = {"bound": "hbm", "achieved": gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": gbs / HBM_PEAK_GBS, "traffic": traffic}
+        else:
+            roof = {"bound": "mfma", "achieved": tfs, "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s",
+                    "frac": tfs / FP32_MFMA_PEAK_TF, "traffic": traffic}
+        roof.update({"kernel": wl.dominant_kernel_name(), "kernel_ms": dom_ms, "kernel_ms_bracketed": dom_ms_bracketed,
+                     "kernel_ms_rocprof": rocprof_ms,
+                     "serial_over_kernel": (serial_ms / dom_ms) if (serial_ms and dom_ms) else None,
+                     "algorithmic_bytes": alg_bytes, "algorithmic_flops": alg_flops, "fp16_mfma_frac_of_2500": tfs / 2500.0,
+                     "whole_op_ms": op_ms, "target_frac": 0.70, "target_met": bool(gbs / HBM_PEAK_GBS >= 0.70)})
+        # (what the fields mean -- the brackets, the byte count, where `traffic` and `kernel_ms_rocprof` come from -- is DESIGN.md
+        # section 5; the line itself stays short)
     configs = None
-    if (rank == 0 and world == 1 and a.scaling == "weak" and a.path == "routed" and a.mode == "filter" and not force_xch
+    if (a.full and rank == 0 and world == 1 and a.scaling == "weak" and a.path == "routed" and a.mode == "filter" and not force_xch
             and a.configs != "off" and not a.no_parity):
         mode_c = a.configs if a.configs != "auto" else ("full" if a.batch is None else "small")
         del wl.slots[1:]
@@ -1391,18 +1450,22 @@ def run_rank(a):
             "value": wl.Bglobal * a.steps / dt, "unit": "images/s", "n_gpus": world, "steps": a.steps,
             "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3,
             "ms_per_step_min": min(dts) / a.steps * 1e3, "ms_per_step_max": max(dts) / a.steps * 1e3,
-            "serial_ms_per_step": serial_ms,
-            "serial_ms_per_step_min_max": [min(serial_blocks), max(serial_blocks)] if serial_blocks else None,
-            "serial_value": wl.Bglobal / (serial_ms * 1e-3) if world == 1 else None, "higher_is_better": True,
-            "scaling": a.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        }
+        if a.full:
+            out.update({"serial_ms_per_step": serial_ms,
+                        "serial_ms_per_step_min_max": [min(serial_blocks), max(serial_blocks)] if serial_blocks else None,
+                        "serial_value": wl.Bglobal / (serial_ms * 1e-3) if world == 1 else None})
+        out.update({
+            "higher_is_better": True, "scaling": a.scaling, "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": wl.describe(), "global_batch": wl.Bglobal, "assign_mode": a.mode, "path": a.path,
-                       "source_sha16": source_sha16(), "spinup_steps": a.spinup, "streams": S, "repeats": R,
+                       "source_sha16": source_sha16(), "spinup_steps": a.spinup, "streams": S, "repeats": R, "full": a.full,
                        "setup_seconds_slowest_rank": setup_s, "host_issue_ms_per_step": t_issue / a.steps * 1e3,
                        "parallelism": par, "backend": backend_name, "world": world, "distinct_devices": distinct_devices,
                        "ranks": [{k: d[k] for k in ("rank", "local_rank", "device_index", "pci_bus_id", "device_uuid", "device_name")}
                                  for d in idents]},
-            "roofline": roof,
-        }
+        })
+        if a.full:
+            out["roofline"] = roof
         if exchange_ms is not None:
             out["exchange_ms_per_step"] = exchange_ms          # pack -> all-gather -> unpack, un-hidden (serial, max over ranks)
         if parity is not None:
@@ -1414,7 +1477,7 @@ def run_rank(a):
                 out["parity"]["oracle_full_batch_images_per_s"] = wl.B / wl.oracle_seconds   # cold, fresh output arrays
         if model_order is not None:
             out["model_order"] = model_order
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(wl.E_np, a.cpu_seconds)
         if configs is not None:
             out["configs"] = configs                           # last: a truncated record keeps the END of the line

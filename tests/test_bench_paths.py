@@ -1,5 +1,6 @@
-"""GPU (-m gpu): every path of bench.py at a small batch -- one JSON line with the contract's fields, `roofline`, the path's own
-parity check green; the default path also reports the model order (the fused quant_conv op) beside the headline."""
+"""GPU (-m gpu): every path of bench.py --full at a small batch -- one JSON line with the contract's fields, `roofline`, the path's own
+parity check green; the default path also reports the model order (the fused quant_conv op) beside the headline.  The plain command
+times its steps and nothing else, and --dump-outputs writes the same arrays on every run with the same arguments."""
 import json
 import os
 import subprocess
@@ -11,9 +12,9 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*extra):
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--spinup", "2", "--batch", "16",
-                        "--no-cpu-baseline"] + list(extra), capture_output=True, text=True, timeout=600)
+def _run(*extra, full=True):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--spinup", "2", "--batch", "16"]
+                       + (["--full", "--no-cpu-baseline"] if full else []) + list(extra), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -66,3 +67,29 @@ def test_default_bench_reports_the_model_order_too():
     assert cfg["world"] == 1 and cfg["distinct_devices"] == 1 and cfg["backend"] is None and len(cfg["ranks"]) == 1
     assert cfg["ranks"][0]["device_index"] == 0 and cfg["ranks"][0]["device_name"] and "no exchange" in cfg["parallelism"]
     assert "exchange_ms_per_step" not in d
+
+
+def test_plain_run_times_only_its_steps_and_dumps_the_same_outputs(tmp_path):
+    """the contract's command without --full: one block of exactly --steps steps and none of the side blocks; --dump-outputs writes
+    the last timed step's outputs at the default batch (float32 / float64, at most 64 MB: z_q of a seeded sample of the images),
+    bit-identical on a second run"""
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        d = _run("--batch", "256", "--dump-outputs", str(tmp_path / str(k)), full=False)
+        for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype"):
+            assert key in d, key
+        assert d["steps"] == 6 and d["config"]["repeats"] == 1 and d["value"] > 0
+        for key in ("ms_per_step_min", "ms_per_step_max"):           # one block: min = median = max (side fields at 7 digits)
+            assert abs(d[key] - d["ms_per_step"]) <= 1e-6 * d["ms_per_step"], key
+        for key in ("roofline", "parity", "model_order", "configs", "cpu_baseline", "serial_ms_per_step"):
+            assert key not in d, key
+        files = sorted(os.listdir(tmp_path / str(k)))
+        assert files == ["codebook_mask.npy", "codes.npy", "gate.npy", "indices.npy", "loss.npy", "zq.npy", "zq_images.npy"], files
+        assert sum(os.path.getsize(tmp_path / str(k) / f) for f in files) <= 64e6
+        dumps.append({f[:-len(".npy")]: np.load(tmp_path / str(k) / f) for f in files})
+    for f, x in dumps[0].items():
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, dumps[1][f]), f
+    x = dumps[0]
+    assert x["codes"].shape == (256, 32, 32) and np.all((x["codes"] >= 0) & (x["codes"] < 1024))
+    assert 0 < x["zq"].shape[0] == x["zq_images"].shape[0] < 256 and x["zq"].shape[1:] == (256, 32, 32) and np.all(np.isfinite(x["zq"]))

@@ -173,7 +173,7 @@ def test_bench_launcher_spawns_ranks_and_exchanges_on_device():
     env.pop("RANK", None)
     for extra in (["--batch", "8"], ["--scaling", "strong", "--batch", "12"], ["--batch", "8", "--path", "model"]):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                            "--spinup", "1", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True,
+                            "--spinup", "1", "--full", "--no-cpu-baseline"] + extra, env=env, capture_output=True, text=True,
                            timeout=900)
         assert p.returncode == 0, p.stderr[-3000:]
         line = [ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1]
@@ -198,7 +198,7 @@ def test_bench_launcher_eight_ranks_on_one_device():
     env.pop("RANK", None)
     for extra, nimg in ((["--scaling", "strong", "--batch", "1024"], 1024), (["--batch", "16"], 128)):
         p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                            "--spinup", "1", "--repeats", "2", "--no-cpu-baseline"] + extra, env=env, capture_output=True,
+                            "--spinup", "1", "--repeats", "2", "--full", "--no-cpu-baseline"] + extra, env=env, capture_output=True,
                            text=True, timeout=1500)
         assert p.returncode == 0, p.stderr[-3000:]
         d = json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])

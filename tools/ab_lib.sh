@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp
 for t in A B A B; do
   L=$A; [ $t = B ] && L=$B
   n=$(ls $O | grep -c "^trace_$t") 
-  DVQ_LIBRARY=$R/$L timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_${t}_$n -o t -- python3 $R/bench.py --streams 1 --steps 300 --repeats 3 --no-cpu-baseline --no-parity --no-model-order "$@" > $O/trace_${t}_$n.json 2>> $O/err.log
+  DVQ_LIBRARY=$R/$L timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_${t}_$n -o t -- python3 $R/bench.py --full --streams 1 --steps 300 --repeats 3 --no-cpu-baseline --no-parity --no-model-order "$@" > $O/trace_${t}_$n.json 2>> $O/err.log
 done
 cd $R
 python3 - <<PY

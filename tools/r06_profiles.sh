@@ -10,21 +10,21 @@ WHAT=${*:-bench rocprof pmc misc}
 TUNE=$R/dynamicvectorquantization_amd/csrc/libdvq_tuning.so
 has() { [[ " $WHAT " == *" $1 "* ]]; }
 if has bench; then
-  timeout 400 python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json
-  timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_driver_flags.json 2>> $O/bench.err; cut -c1-200 $O/bench_driver_flags.json
-  timeout 300 python bench.py --streams 1 --no-cpu-baseline --no-model-order --configs off > $O/bench_streams1.json 2>> $O/bench.err
+  timeout 400 python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-300 $O/bench.json
+  timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_driver_flags.json 2>> $O/bench.err; cut -c1-200 $O/bench_driver_flags.json
+  timeout 300 python bench.py --full --streams 1 --no-cpu-baseline --no-model-order --configs off > $O/bench_streams1.json 2>> $O/bench.err
   for p in model model_fold tokens tokens_fold; do
-    timeout 300 python bench.py --path $p --no-cpu-baseline > $O/bench_$p.json 2>> $O/bench.err; cut -c1-160 $O/bench_$p.json
+    timeout 300 python bench.py --full --path $p --no-cpu-baseline > $O/bench_$p.json 2>> $O/bench.err; cut -c1-160 $O/bench_$p.json
   done
-  timeout 300 python bench.py --scaling strong --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_strong_n1.json 2>> $O/bench.err
-  timeout 300 python bench.py --scaling strong --batch 128 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_strong_b128_rank_size.json 2>> $O/bench.err
-  DVQ_BENCH_FORCE_EXCHANGE=1 timeout 300 python bench.py --no-cpu-baseline --no-model-order --configs off > $O/bench_exchange_world1.json 2>> $O/bench.err
+  timeout 300 python bench.py --full --scaling strong --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_strong_n1.json 2>> $O/bench.err
+  timeout 300 python bench.py --full --scaling strong --batch 128 --steps 200 --warmup 20 --no-cpu-baseline > $O/bench_strong_b128_rank_size.json 2>> $O/bench.err
+  DVQ_BENCH_FORCE_EXCHANGE=1 timeout 300 python bench.py --full --no-cpu-baseline --no-model-order --configs off > $O/bench_exchange_world1.json 2>> $O/bench.err
 fi
 if has rocprof; then
   cd /tmp && export TMPDIR=/tmp
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_s1 -o t -- python3 $R/bench.py --streams 1 --no-cpu-baseline --no-parity --no-model-order --configs off > $O/trace_bench_streams1.json 2> $O/trace.err
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_model -o t -- python3 $R/bench.py --path model --streams 1 --no-cpu-baseline --no-parity > $O/trace_bench_model.json 2>> $O/trace.err
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_configs -o t -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline > $O/trace_bench_configs.json 2>> $O/trace.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_s1 -o t -- python3 $R/bench.py --full --streams 1 --no-cpu-baseline --no-parity --no-model-order --configs off > $O/trace_bench_streams1.json 2> $O/trace.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_model -o t -- python3 $R/bench.py --full --path model --streams 1 --no-cpu-baseline --no-parity > $O/trace_bench_model.json 2>> $O/trace.err
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_configs -o t -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/trace_bench_configs.json 2>> $O/trace.err
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_entropy -o t -- python3 $R/tools/entropy_time.py > /dev/null 2>> $O/trace.err
   cd $R
   python3 tools/rocprof_meta.py $O/trace_s1 $O/r06_bench_kernel_stats.csv routed weak "vq_assign_filter_kernel<256, 2, false, false>" | tee $O/rocprof_meta.log
