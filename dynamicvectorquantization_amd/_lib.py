@@ -14,7 +14,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 # DVQ_LIBRARY: load another build of the same sources instead (tools/ use csrc/libdvq_tuning.so, made by
-# `make -C csrc tuning`, which additionally exports the A/B switches dvq_tuning_set / dvq_tuning_buffers)
+# `make -C csrc tuning`, which additionally exports dvq_tuning_buffers: in-kernel diagnostics and clock stamps)
 LIB_PATH = os.environ.get("DVQ_LIBRARY") or os.path.join(CSRC, "libdvq.so")
 
 DVQ_OK = 0
@@ -126,17 +126,9 @@ def _load():
     lib.dvq_qconv_f32.argtypes = [vp, vp, i32, i32, i32, vp, vp]
     lib.dvq_qconv_select_f32.restype = i32
     lib.dvq_qconv_select_f32.argtypes = [i32, vp, i32, f32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    if hasattr(lib, "dvq_tuning_set"):                     # tuning build only
-        lib.dvq_tuning_set.restype = i32
-        lib.dvq_tuning_set.argtypes = [ctypes.c_char_p, i32]
+    if hasattr(lib, "dvq_tuning_buffers"):                 # tuning build only
         lib.dvq_tuning_buffers.restype = i32
         lib.dvq_tuning_buffers.argtypes = [vp, vp]
-        # tools/ only: DVQ_TUNE="key=value,..." sets A/B switches of the tuning build for a whole process (e.g. bench.py under
-        # tools/archive/ab_lib.sh); the product library exports no such symbol and this branch is not taken
-        for kv in filter(None, os.environ.get("DVQ_TUNE", "").split(",")):
-            k, v = kv.split("=")
-            if lib.dvq_tuning_set(k.strip().encode(), int(v)) != 0:
-                raise DvqError("DVQ_TUNE: unknown switch %r" % k)
     lib.dvq_debug_filter_scores_f32.restype = i32
     lib.dvq_debug_filter_scores_f32.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
     lib.dvq_exchange_bytes.restype = sz

@@ -135,19 +135,26 @@ struct DvqLossTail {
 #endif
 #define DVQ_EXACT_LIST_BLOCKS 512   // grid of the list-mode exact kernel (2 per CU; it walks the list in chunks)
 
-// Kernels with more than 64 KiB of dynamic LDS need the per-device opt-in once; `done` is the caller's
-// static bitmask (one bit per device ordinal, so a process driving several GPUs opts in on each; relaxed
-// atomics: two host threads may both apply the attribute, which is idempotent).  Returns the HIP error
-// of hipFuncSetAttribute (0 = ok).
-static inline int dvq_allow_dynamic_lds(const void *kernel, int bytes, unsigned long long *done)
+// Launch of a kernel with more than 64 KiB of dynamic LDS: the per-device opt-in to OPTIN bytes (0 = the launch's `lds`) is
+// applied once per kernel and device -- a bitmask per kernel, one bit per device ordinal, so a process driving several GPUs opts
+// in on each; relaxed atomics: two host threads may both apply the attribute, which is idempotent.  Returns the HIP error of the
+// opt-in or of the launch (0 = ok).
+template <auto Kernel>
+static unsigned long long dvq_lds_done = 0;
+
+template <auto Kernel, int OPTIN = 0, class... A>
+static inline int dvq_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args)
 {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 63;     // shared bit: always re-apply
-    if (dev != 63 && ((__atomic_load_n(done, __ATOMIC_RELAXED) >> dev) & 1ull)) return 0;
-    const hipError_t rc = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    if (rc != hipSuccess) return (int)rc;
-    if (dev != 63) __atomic_fetch_or(done, 1ull << dev, __ATOMIC_RELAXED);
-    return 0;
+    if (dev == 63 || !((__atomic_load_n(&dvq_lds_done<Kernel>, __ATOMIC_RELAXED) >> dev) & 1ull)) {
+        const hipError_t rc = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                  OPTIN ? OPTIN : (int)lds);
+        if (rc != hipSuccess) return (int)rc;
+        if (dev != 63) __atomic_fetch_or(&dvq_lds_done<Kernel>, 1ull << dev, __ATOMIC_RELAXED);
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args...);
+    return (int)hipGetLastError();
 }
 
 // per-launch host-side error plumbing (dvq_abi.hip)

@@ -374,17 +374,15 @@ int dvq_launch_ema_accumulate(const float *z, const long long *codes, int D, int
         hipLaunchKernelGGL(ema_zero_kernel, dim3(blocks), dim3(256), 0, st, cluster_size, (size_t)K, vectors_sum, n);
     }
     if (K <= 4096 && (HW & 3) == 0 && (D & 15) == 0 && N >= 32 * EMS_BT) {
-        static unsigned long long done_s = 0;
         const size_t shm = (size_t)EMS_BC * EMS_STR * 4 + (size_t)EMS_BT * 6 + ((size_t)K + 1) * 4;
-        int rc = dvq_allow_dynamic_lds((const void *)ema_accumulate_sorted_kernel, (int)shm, &done_s);
-        if (rc) return rc;
         int ncu = 256, dev = 0;
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
         const long nitems = ((N + EMS_BT - 1) / EMS_BT) * (D / EMS_BC);
         const unsigned grid = (unsigned)(nitems < ncu ? nitems : (ncu > 0 ? ncu : 256));
-        hipLaunchKernelGGL(ema_accumulate_sorted_kernel, dim3(grid), dim3(1024), shm, st, z, codes, D, HW, N, K, cluster_size,
-                           vectors_sum);
-    } else if (K <= 8192)
+        return dvq_launch_lds<ema_accumulate_sorted_kernel>(dim3(grid), dim3(1024), shm, st, z, codes, D, HW, N, K, cluster_size,
+                                                            vectors_sum);
+    }
+    if (K <= 8192)
         hipLaunchKernelGGL(ema_accumulate_kernel<true>, dim3((unsigned)((N + 63) / 64)), dim3(256), (size_t)K * sizeof(int), st, z,
                            codes, D, HW, N, K, cluster_size, vectors_sum);
     else
@@ -469,12 +467,8 @@ int dvq_launch_restart_pick(unsigned long long seed, long long n, int k, long lo
     if (k < 1 || k > 2048 || n < 1 || n > 0xFFFFFFFFll) return -1000;
     int hbits = 3;
     while ((1 << hbits) < 8 * k) ++hbits;                    // table = 4 x the draws
-    static unsigned long long done = 0;
     const size_t shm = (size_t)(1 << hbits) * sizeof(unsigned long long);
-    int rc = dvq_allow_dynamic_lds((const void *)restart_pick_kernel, (int)shm, &done);
-    if (rc) return rc;
-    hipLaunchKernelGGL(restart_pick_kernel, dim3(1), dim3(1024), shm, st, seed, n, k, hbits, out);
-    return (int)hipGetLastError();
+    return dvq_launch_lds<restart_pick_kernel>(dim3(1), dim3(1024), shm, st, seed, n, k, hbits, out);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -223,13 +223,9 @@ int dvq_launch_qconv_prep(const float *Wt, const float *bias, int D, void *prep,
 template <int D, bool SEL>
 static int launch_qconv(const float *x, const DvqRouted &rv, const void *prep, int HW, long N, float *hout, hipStream_t st)
 {
-    static unsigned long long done = 0;
     const size_t shmem = 2 * (2 * (size_t)(D / 16) * 1024 + 256);
-    int rc = dvq_allow_dynamic_lds((const void *)qconv_kernel<D, SEL>, (int)shmem, &done);
-    if (rc) return rc;
-    hipLaunchKernelGGL((qconv_kernel<D, SEL>), dim3((unsigned)((N + 127) / 128)), dim3(256), shmem, st, x, rv,
-                       (const char *)prep + 256, (const QconvMeta *)prep, HW, N, hout);
-    return (int)hipGetLastError();
+    return dvq_launch_lds<qconv_kernel<D, SEL>>(dim3((unsigned)((N + 127) / 128)), dim3(256), shmem, st, x, rv,
+                                                 (const char *)prep + 256, (const QconvMeta *)prep, HW, N, hout);
 }
 
 // x != nullptr: dense input [B, D, HW]; else the select fused in through rv (dense form, gate given)

@@ -605,9 +605,6 @@ __global__ __launch_bounds__(GATE_NW * 64) void router_gate_kernel(
 // a workgroup walks its cell blocks with stride gridDim.x.  The output layer is contracted in the epilogue (bias, activation,
 // W2 rows from LDS); the partial logits of the hidden groups go to part[hg][cell][g] and are summed in a fixed order by
 // gate_finalize_kernel (deterministic; no float atomics).
-#ifndef DVQ_GEMM_ABL
-#define DVQ_GEMM_ABL 0           // timing experiments of the tuning build only (results WRONG): 1 no ring DMA in the loop, 2 no MFMAs,
-#endif                           // 4 no epilogue, 8 no B-fragment reads
 #ifndef DVQ_GEMM_CH16
 #define DVQ_GEMM_CH16 1          // ring chunks of 16 k-steps (4 slots) instead of 8 (8 slots): half the workgroup barriers, the kernel -2 ... -4 %
 #endif                           // (same box; profiles/r05_gate_counters.json)
@@ -688,12 +685,12 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         issue_begin(qn + RING - 2);                          // its pieces ride between the MFMAs of the next k-steps
-        if (!(DVQ_GEMM_ABL & 1)) issue_piece(0);
+        issue_piece(0);
         rd_base = lds_lane + (unsigned)((qn & (RING - 1)) * CHB);
     };
     __builtin_amdgcn_s_barrier();                            // everybody's pieces of the first chunks (and PB) are in LDS
     asm volatile("" ::: "memory");
-    if (!(DVQ_GEMM_ABL & 1)) issue(RING - 2);
+    issue(RING - 2);
     rd_base = lds_lane;
     GG_RD(0, 0); GG_RD(1, 1); GG_RD(2, 2); GG_RD(3, 3);
     // Epilogue of a cell block = bias, activation, contraction with the output layer: register r of lane half h is hidden row
@@ -749,18 +746,16 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
                 // four pairs (k-steps sk .. sk + 3) are in flight: the oldest has landed when at most six reads are outstanding
                 asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(bh[sk & 3]), "+v"(bl[sk & 3]) :: "memory");
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(DVQ_GEMM_ABL & 2)) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sk], bh[sk & 3], acc, 0, 0, 0);     // small terms first
-                    __builtin_amdgcn_sched_barrier(0);
-                    // one ring piece per k-step, behind an MFMA that keeps the pipe busy while the DMA instruction issues
-                    if (u % CH > 0 && u % CH < PPW && !(DVQ_GEMM_ABL & 1)) issue_piece(u % CH);
-                    __builtin_amdgcn_sched_barrier(0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bl[sk & 3], acc, 0, 0, 0);
-                    if (PIPE && PREV && sk < 16 && !(DVQ_GEMM_ABL & 4)) { __builtin_amdgcn_sched_barrier(0); epi_row(sk); __builtin_amdgcn_sched_barrier(0); }
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bh[sk & 3], acc, 0, 0, 0);
-                }
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sk], bh[sk & 3], acc, 0, 0, 0);     // small terms first
                 __builtin_amdgcn_sched_barrier(0);
-                if (PIPE && PREV && sk == 16 && !(DVQ_GEMM_ABL & 4)) {
+                // one ring piece per k-step, behind an MFMA that keeps the pipe busy while the DMA instruction issues
+                if (u % CH > 0 && u % CH < PPW) issue_piece(u % CH);
+                __builtin_amdgcn_sched_barrier(0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bl[sk & 3], acc, 0, 0, 0);
+                if (PIPE && PREV && sk < 16) { __builtin_amdgcn_sched_barrier(0); epi_row(sk); __builtin_amdgcn_sched_barrier(0); }
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bh[sk & 3], acc, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (PIPE && PREV && sk == 16) {
                     store_part(i - 1, ptp);
 #pragma unroll
                     for (int g = 0; g < G; ++g) ptp[g] = 0.0f;
@@ -773,7 +768,6 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
                 GG_RD(u, u % CH);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (DVQ_GEMM_ABL & 4) { if (acc[0] == 12345.678f) part[0] = acc[1]; return; }
             if (PIPE) {
                 accp = acc;                                  // consumed during the next block (or after the loop)
                 return;
@@ -807,7 +801,7 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
         // drain the read-ahead (its last four pairs are never consumed) and, PIPE, the last block's epilogue
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bh[0]), "+v"(bl[0]), "+v"(bh[1]), "+v"(bl[1]), "+v"(bh[2]), "+v"(bl[2]),
                      "+v"(bh[3]), "+v"(bl[3]) :: "memory");
-        if (PIPE && !(DVQ_GEMM_ABL & 4)) {
+        if (PIPE) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) epi_row(r);
             store_part(nmine - 1, ptp);
@@ -828,20 +822,17 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
                 const int u = sk + 4;
                 asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(bh[sk & 3]), "+v"(bl[sk & 3]) :: "memory");
                 __builtin_amdgcn_sched_barrier(0);
-                if (!(DVQ_GEMM_ABL & 2)) {
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sk], bh[sk & 3], acc, 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (u % CH > 0 && u % CH < PPW && !(DVQ_GEMM_ABL & 1)) issue_piece(u % CH);
-                    __builtin_amdgcn_sched_barrier(0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bl[sk & 3], acc, 0, 0, 0);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bh[sk & 3], acc, 0, 0, 0);
-                }
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sk], bh[sk & 3], acc, 0, 0, 0);
+                __builtin_amdgcn_sched_barrier(0);
+                if (u % CH > 0 && u % CH < PPW) issue_piece(u % CH);
+                __builtin_amdgcn_sched_barrier(0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bl[sk & 3], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bh[sk & 3], acc, 0, 0, 0);
                 __builtin_amdgcn_sched_barrier(0);
                 if (u % CH == 0) enter_chunk(i * NCH + u / CH);
                 GG_RD(u, u % CH);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            if (DVQ_GEMM_ABL & 4) { if (acc[0] == 12345.678f) part[0] = acc[1]; continue; }
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bh[0]), "+v"(bl[0]), "+v"(bh[1]), "+v"(bl[1]), "+v"(bh[2]), "+v"(bl[2]),
                          "+v"(bh[3]), "+v"(bl[3]) :: "memory");
             float pt[G];
@@ -1051,14 +1042,12 @@ int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn
         if (CG > nblocks) CG = nblocks;
 #define DVQ_GEMM_LAUNCH(GG, SS)                                                                                        \
         do {                                                                                                           \
-            static unsigned long long done_ = 0;                                                                       \
             constexpr int CH_ = (DVQ_GEMM_CH16 && SS % 16 == 0) ? 16 : ((SS % 8 == 0) ? 8 : 4);                         \
             constexpr int CHB_ = CH_ * 2048;                                                                           \
             const size_t shm = (CH_ == 16 ? 4 : 8) * (size_t)CHB_ + (4 * (1 + GG) * 32 + 4 * GG * 32) * sizeof(float); \
-            int rc = dvq_allow_dynamic_lds((const void *)gate_gemm_kernel<GG, SS>, (int)shm, &done_);                  \
+            int rc = dvq_launch_lds<gate_gemm_kernel<GG, SS>>(dim3(CG, HG), dim3(256), shm, st, ximg, imgH, imgLg, b1, W2, \
+                                                             Hid, act, ncell, nblocks, xs, part, wtail);               \
             if (rc) return rc;                                                                                         \
-            hipLaunchKernelGGL((gate_gemm_kernel<GG, SS>), dim3(CG, HG), dim3(256), shm, st, ximg, imgH, imgLg, b1, W2, \
-                               Hid, act, ncell, nblocks, xs, part, wtail);                                             \
         } while (0)
         if (nb == 2) {
             switch (S16) {
@@ -1100,16 +1089,12 @@ int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn
     const int CBv = cb2 ? 2 : 1;
     const unsigned grid = (unsigned)((ncell + 32 * CBv - 1) / (32 * CBv));
     const size_t shmem = cb2 ? shmem2 : ((size_t)32 * Fp + (size_t)(1 + nb) * Hid) * sizeof(float);
+    // opted in to the LDS of the largest tile (not this launch's shmem), once per kernel and device
 #define DVQ_GATE_LAUNCH(GG, CC)                                                                                        \
-    do {                                                                                                               \
-        static unsigned long long done_ = 0;                                                                           \
-        int rc = dvq_allow_dynamic_lds((const void *)router_gate_kernel<GG, CC>, 160 * 1024 - 256, &done_);            \
-        if (rc) return rc;                                                                                             \
-        hipLaunchKernelGGL((router_gate_kernel<GG, CC>), dim3(grid), dim3(GATE_NW * 64), shmem, st, a, stats, pool,    \
-                           imgH, imgL, b1, W2, b2, Hid, act, gate, wtail);                                             \
-    } while (0)
-    if (nb == 2) { if (cb2) DVQ_GATE_LAUNCH(2, 2); else DVQ_GATE_LAUNCH(2, 1); }
-    else         { if (cb2) DVQ_GATE_LAUNCH(3, 2); else DVQ_GATE_LAUNCH(3, 1); }
+    dvq_launch_lds<router_gate_kernel<GG, CC>, 160 * 1024 - 256>(dim3(grid), dim3(GATE_NW * 64), shmem, st, a, stats,  \
+                                                                 pool, imgH, imgL, b1, W2, b2, Hid, act, gate, wtail)
+    const int rc = nb == 2 ? (cb2 ? DVQ_GATE_LAUNCH(2, 2) : DVQ_GATE_LAUNCH(2, 1))
+                           : (cb2 ? DVQ_GATE_LAUNCH(3, 2) : DVQ_GATE_LAUNCH(3, 1));
 #undef DVQ_GATE_LAUNCH
-    return (int)hipGetLastError();
+    return rc;
 }

@@ -511,29 +511,19 @@ static int launch_exact(const float *z, const float *tiles, const float *E, cons
                         const int *list, const int *list_count, DvqLossTail tail, const DvqRouted &rv,
                         hipStream_t st, const DvqConv *fold_conv)
 {
-    static unsigned long long done_dense = 0, done_list = 0, done_fold = 0;
     const size_t shmem = 2 * (32 * D + 64) * sizeof(float);
-    int rc = dvq_allow_dynamic_lds((const void *)vq_assign_exact_kernel<D, false, ROUTED>, (int)shmem, &done_dense);
-    if (rc) return rc;
-    rc = dvq_allow_dynamic_lds((const void *)vq_assign_exact_kernel<D, true, ROUTED>, (int)shmem, &done_list);
-    if (rc) return rc;
     int blocks = (int)((N + 127) / 128);
-    const DvqConv nocv = {};
-    if (list != nullptr && fold_conv != nullptr) {
-        rc = dvq_allow_dynamic_lds((const void *)vq_assign_exact_kernel<D, true, ROUTED, true>, (int)shmem, &done_fold);
-        if (rc) return rc;
-        if (blocks > DVQ_EXACT_LIST_BLOCKS) blocks = DVQ_EXACT_LIST_BLOCKS;
-        hipLaunchKernelGGL((vq_assign_exact_kernel<D, true, ROUTED, true>), dim3(blocks), dim3(256), shmem, st,
-                           z, tiles, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, rv, *fold_conv);
-    } else if (list != nullptr) {
-        if (blocks > DVQ_EXACT_LIST_BLOCKS) blocks = DVQ_EXACT_LIST_BLOCKS;
-        hipLaunchKernelGGL((vq_assign_exact_kernel<D, true, ROUTED>), dim3(blocks), dim3(256), shmem, st,
-                           z, tiles, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, rv, nocv);
-    } else {
-        hipLaunchKernelGGL((vq_assign_exact_kernel<D, false, ROUTED>), dim3(blocks), dim3(256), shmem, st,
-                           z, tiles, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, rv, nocv);
-    }
-    return (int)hipGetLastError();
+    if (list == nullptr)
+        return dvq_launch_lds<vq_assign_exact_kernel<D, false, ROUTED>>(dim3(blocks), dim3(256), shmem, st, z, tiles, E, mask, HW,
+                                                                         K, N, zq, codes, partials, list, list_count, tail, rv,
+                                                                         DvqConv{});
+    if (blocks > DVQ_EXACT_LIST_BLOCKS) blocks = DVQ_EXACT_LIST_BLOCKS;
+    if (fold_conv != nullptr)
+        return dvq_launch_lds<vq_assign_exact_kernel<D, true, ROUTED, true>>(dim3(blocks), dim3(256), shmem, st, z, tiles, E, mask,
+                                                                              HW, K, N, zq, codes, partials, list, list_count, tail,
+                                                                              rv, *fold_conv);
+    return dvq_launch_lds<vq_assign_exact_kernel<D, true, ROUTED>>(dim3(blocks), dim3(256), shmem, st, z, tiles, E, mask, HW, K, N,
+                                                                    zq, codes, partials, list, list_count, tail, rv, DvqConv{});
 }
 
 static const DvqRouted kNoRoute = {};
@@ -544,18 +534,12 @@ int dvq_launch_exact_list(const float *z, const float *prep, const float *E, con
                           const int *list, const int *list_count, DvqLossTail tail, const DvqRouted *rv,
                           hipStream_t st, const DvqConv *fold_conv)
 {
-    if (rv != nullptr) {
-        switch (D) {
-        case 64:  return launch_exact<64, true>(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, *rv, st, fold_conv);
-        case 128: return launch_exact<128, true>(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, *rv, st, fold_conv);
-        case 256: return launch_exact<256, true>(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, *rv, st, fold_conv);
-        default:  return -1000;
-        }
-    }
+    const bool routed = rv != nullptr;
+    const DvqRouted &r = routed ? *rv : kNoRoute;
     switch (D) {
-    case 64:  return launch_exact<64, false>(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, kNoRoute, st, fold_conv);
-    case 128: return launch_exact<128, false>(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, kNoRoute, st, fold_conv);
-    case 256: return launch_exact<256, false>(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, kNoRoute, st, fold_conv);
+    case 64:  return (routed ? launch_exact<64, true> : launch_exact<64, false>)(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, r, st, fold_conv);
+    case 128: return (routed ? launch_exact<128, true> : launch_exact<128, false>)(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, r, st, fold_conv);
+    case 256: return (routed ? launch_exact<256, true> : launch_exact<256, false>)(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, r, st, fold_conv);
     default:  return -1000;
     }
 }

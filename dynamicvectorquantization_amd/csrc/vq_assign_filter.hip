@@ -30,7 +30,6 @@
 // W is the sum with ||e_j||, en_j, ||eta_j|| replaced by their maxima over the codebook.
 #include "dvq_filter.h"
 #include <stdlib.h>
-#include <string.h>
 #include <type_traits>
 
 // z is read once and z_q written once per launch: stream them past L2 (nt) so that the codebook
@@ -219,6 +218,10 @@ __device__ unsigned long long *g_dvq_stamps = nullptr;
 // (best, second, code) per token in `split`; the workgroup that takes a block's last ticket merges them (lower slice wins ties, as
 // the lower tile does in the loop) and runs the epilogue of the whole block.  Everything downstream sees what one workgroup
 // would have produced, up to which of two equal scores is called best (tokens that close are undecided either way).
+// Dynamic LDS of every form of pass 1 (the wide kernel's too): 4 ring slots of a code tile's image (D / 16 KiB each), the slots'
+// accumulator seeds per wave ([4][4 waves][64] floats) and a 2-KiB permutation scratch per wave -- the carve below
+constexpr size_t dvq_pass1_lds_bytes(int D) { return 4 * (size_t)(D / 16) * 1024 + 4 * 4 * 64 * sizeof(float) + 4 * 2048; }
+
 template <int D, int SEL, bool CONV, bool FOLD, bool NT, bool FLAT = false, bool SPLIT = false>
 __device__ __forceinline__ void pass1_body(
     const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
@@ -248,7 +251,8 @@ __device__ __forceinline__ void pass1_body(
     constexpr int FLAT_LPT = D * 2 / 16;                     // lanes (16-byte pieces) per token-half
     constexpr int FLAT_TPI = 64 / FLAT_LPT;                  // tokens per wave-instruction
     constexpr int FLAT_IPH = 32 / FLAT_TPI;                  // wave-instructions per half
-    static_assert(!FLAT || NW * FLAT_TRW <= NBUF * IMG_BYTES + NBUF * NW * 64 * 4 + NW * 2048, "the images fit the kernel's LDS");
+    static_assert(NBUF * IMG_BYTES + NBUF * NW * 64 * 4 + NW * 2048 == dvq_pass1_lds_bytes(D), "the launch's LDS is this carve");
+    static_assert(!FLAT || NW * FLAT_TRW <= dvq_pass1_lds_bytes(D), "the images fit the kernel's LDS");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float *enraw = (float *)(lds + NBUF * IMG_BYTES);        // [NBUF][NW][64] accumulator seeds, per-wave copy
     DVQ_STAMP(0);
@@ -1070,6 +1074,7 @@ __global__ __launch_bounds__(256, 2) void vq_assign_filter_wide_kernel(
     constexpr int CPW = (S16 + NW - 1) / NW;
     constexpr int PER_TILE = CPW + 1;
     constexpr int NBUF = 4;
+    static_assert(NBUF * IMG_BYTES + NBUF * NW * 64 * 4 + NW * 2048 == dvq_pass1_lds_bytes(D), "the launch's LDS is this carve");
     extern __shared__ __attribute__((aligned(16))) char lds[];
     float *enraw = (float *)(lds + NBUF * IMG_BYTES);        // [NBUF][NW][64] accumulator seeds, per-wave copy
 
@@ -1448,10 +1453,6 @@ struct ResLds {
     static_assert(CAND % 16 == 0 && BEST % 8 == 0 && RED % 8 == 0, "carve alignment");
 };
 
-#ifndef DVQ_FOLD_ABL
-#define DVQ_FOLD_ABL 0           // timing experiments of the tuning build only (results WRONG): 1 no conv loop, 2 no xn, 4 no h write-back
-#endif
-
 // One chunk: the records [base, base + nlive) (record indices; nlive <= RES_SLOTS), code tiles [t_begin, t_end).
 // FOLD (vq_fold.hip): the records hold the conv's INPUT x and `img` / `meta` are the folded codebook: the enumeration below
 // runs on x exactly as pass 1 scored it (its candidate set contains the reference's winner for every h inside the conv's
@@ -1631,7 +1632,7 @@ __device__ __forceinline__ double resolve_chunk(
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][r] = 0.0f;
 #pragma unroll
-        for (int s0 = 0; s0 < ((DVQ_FOLD_ABL & 1) ? 0 : S16); s0 += SB) {
+        for (int s0 = 0; s0 < S16; s0 += SB) {
             f16x8 wh[SB][NT], wl[SB][NT];
 #pragma unroll
             for (int q = 0; q < SB; ++q)
@@ -1668,7 +1669,7 @@ __device__ __forceinline__ double resolve_chunk(
             }
         }
         __syncthreads();                                         // every wave has read x: h takes its place
-        if (live && !(DVQ_FOLD_ABL & 4)) {
+        if (live) {
             float *hrow = (float *)(srec + c * RB);
 #pragma unroll
             for (int i = 0; i < NT; ++i) {
@@ -1681,22 +1682,20 @@ __device__ __forceinline__ double resolve_chunk(
             }
         }
         __syncthreads();
-        if (!(DVQ_FOLD_ABL & 2)) {
-            // the reference's norm of h (ATen order: 32 partial sums a[i % 32], ((a[l] + a[l+8]) + a[l+16]) + a[l+24], then l = 0..7
-            // left to right) for the exact chains: 8 lanes per token, lane l owns a[l], a[l+8], a[l+16], a[l+24]
-            static_assert(RW * 64 >= RES_SLOTS * 8, "8 lanes per queued token");
-            const int tk = (tid >> 3) < RES_SLOTS ? (tid >> 3) : RES_SLOTS - 1, l8 = tid & 7;   // (threads past the last token: idle repeats)
-            const float *hv = (const float *)(srec + tk * RB);
-            float a4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            for (int k0 = 0; k0 < D; k0 += 32)
+        // the reference's norm of h (ATen order: 32 partial sums a[i % 32], ((a[l] + a[l+8]) + a[l+16]) + a[l+24], then l = 0..7
+        // left to right) for the exact chains: 8 lanes per token, lane l owns a[l], a[l+8], a[l+16], a[l+24]
+        static_assert(RW * 64 >= RES_SLOTS * 8, "8 lanes per queued token");
+        const int tk = (tid >> 3) < RES_SLOTS ? (tid >> 3) : RES_SLOTS - 1, l8 = tid & 7;   // (threads past the last token: idle repeats)
+        const float *hv = (const float *)(srec + tk * RB);
+        float a4[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        for (int k0 = 0; k0 < D; k0 += 32)
 #pragma unroll
-                for (int g = 0; g < 4; ++g) a4[g] = __fadd_rn(a4[g], sq_rn(hv[k0 + l8 + 8 * g]));
-            const float tl = __fadd_rn(__fadd_rn(__fadd_rn(a4[0], a4[1]), a4[2]), a4[3]);
-            float sn = __shfl(tl, lane & ~7);
+            for (int g = 0; g < 4; ++g) a4[g] = __fadd_rn(a4[g], sq_rn(hv[k0 + l8 + 8 * g]));
+        const float tl = __fadd_rn(__fadd_rn(__fadd_rn(a4[0], a4[1]), a4[2]), a4[3]);
+        float sn = __shfl(tl, lane & ~7);
 #pragma unroll
-            for (int i = 1; i < 8; ++i) sn = __fadd_rn(sn, __shfl(tl, (lane & ~7) + i));
-            if (l8 == 0 && (tid >> 3) < nlive) ((RecMeta *)(srec + tk * RB + (size_t)D * 4))->xn = sn;
-        }
+        for (int i = 1; i < 8; ++i) sn = __fadd_rn(sn, __shfl(tl, (lane & ~7) + i));
+        if (l8 == 0 && (tid >> 3) < nlive) ((RecMeta *)(srec + tk * RB + (size_t)D * 4))->xn = sn;
         __syncthreads();
     }
     __syncthreads();
@@ -1925,59 +1924,21 @@ __global__ __launch_bounds__(256, 2) void vq_assign_filter_flat_kernel(
     pass1_body<D, 0, false, FOLD, true, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records, rec_cap, rv, cv);
 }
 
-// small batches: `ksplit` workgroups per token block, each on its slice of the code tiles (SPLIT, see pass1_body)
-template <int D, bool FLAT>
+// small batches: `ksplit` workgroups per token block, each on its slice of the code tiles (SPLIT, see pass1_body).  Dense (FLAT:
+// row-major latents), with the router select fused in (per-lane form, SEL = 1: every slice's workgroup writes the same indices /
+// codebook_mask / gate), with the 1x1 conv as the prologue (CONV: every slice's workgroup computes the block's h itself,
+// 3 x 8.4 MFLOP, nothing to share; the conv's inputs are read with the non-temporal hint) or on the conv-folded codebook (FOLD:
+// loss-free inference / stage-2 tokenisation of single images)
+template <int D, int SEL, bool CONV, bool FOLD, bool FLAT>
 __global__ __launch_bounds__(256, 2) void vq_assign_filter_split_kernel(
     const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
     const float *__restrict__ E, const float *__restrict__ mask,
     int HW, int K, long N, float *__restrict__ zq, long long *__restrict__ codes,
     double *__restrict__ partials, int *__restrict__ counters, int *__restrict__ exact_list,
-    char *__restrict__ records, int rec_cap, f32x4 *__restrict__ split, int ksplit)
-{
-    const DvqRouted rv = {};
-    const DvqConv cv = {};
-    pass1_body<D, 0, false, false, false, FLAT, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records,
-                                                      rec_cap, rv, cv, split, ksplit);
-}
-
-// ... with the router select fused in (per-lane form; every slice's workgroup writes the same indices / codebook_mask / gate)
-template <int D>
-__global__ __launch_bounds__(256, 2) void vq_assign_filter_split_sel_kernel(
-    const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
-    const float *__restrict__ E, const float *__restrict__ mask,
-    int HW, int K, long N, float *__restrict__ zq, long long *__restrict__ codes,
-    double *__restrict__ partials, int *__restrict__ counters, int *__restrict__ exact_list,
-    char *__restrict__ records, int rec_cap, const DvqRouted rv, f32x4 *__restrict__ split, int ksplit)
-{
-    const DvqConv cv = {};
-    pass1_body<D, 1, false, false, false, false, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records,
-                                                       rec_cap, rv, cv, split, ksplit);
-}
-
-// ... and with the 1x1 conv as the prologue (every slice's workgroup computes the block's h itself: 3 x 8.4 MFLOP, nothing to share)
-template <int D, int SEL>
-__global__ __launch_bounds__(256, 2) void vq_assign_filter_split_conv_kernel(
-    const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
-    const float *__restrict__ E, const float *__restrict__ mask,
-    int HW, int K, long N, float *__restrict__ zq, long long *__restrict__ codes,
-    double *__restrict__ partials, int *__restrict__ counters, int *__restrict__ exact_list,
     char *__restrict__ records, int rec_cap, const DvqRouted rv, const DvqConv cv, f32x4 *__restrict__ split, int ksplit)
 {
-    pass1_body<D, SEL, true, false, true, false, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records,
-                                                       rec_cap, rv, cv, split, ksplit);
-}
-
-// ... and on the conv-folded codebook (loss-free inference / stage-2 tokenisation of single images)
-template <int D, int SEL>
-__global__ __launch_bounds__(256, 2) void vq_assign_filter_split_fold_kernel(
-    const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
-    const float *__restrict__ E, const float *__restrict__ mask,
-    int HW, int K, long N, float *__restrict__ zq, long long *__restrict__ codes,
-    double *__restrict__ partials, int *__restrict__ counters, int *__restrict__ exact_list,
-    char *__restrict__ records, int rec_cap, const DvqRouted rv, const DvqConv cv, f32x4 *__restrict__ split, int ksplit)
-{
-    pass1_body<D, SEL, false, true, false, false, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records,
-                                                        rec_cap, rv, cv, split, ksplit);
+    pass1_body<D, SEL, CONV, FOLD, CONV, FLAT, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records,
+                                                     rec_cap, rv, cv, split, ksplit);
 }
 
 // the same kernel with plain loads of the latents, for batches that fit the memory-side cache (dense or staged select, no conv)
@@ -1992,10 +1953,6 @@ __global__ __launch_bounds__(256, 2) void vq_assign_filter_cached_kernel(
     pass1_body<D, SEL, false, FOLD, false>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records, rec_cap, rv, cv);
 }
 
-// ---------------------------------------------------------------------------------------------
-// audit aid (dvq_debug_filter_scores_f32, tools/bound_audit.py): pass 1's score arithmetic on a few tokens
-// given as rows [n, D] -- same fp16 conversion, same seeded accumulator, same MFMA chain in the same order,
-// same index packing, same threshold -- with every score written out instead of reduced to a top-2.
 // ---------------------------------------------------------------------------------------------
 // audit aid (dvq_debug_filter_scores_f32, tools/bound_audit.py): pass 1's score arithmetic on a few tokens
 // given as rows [n, D] -- same fp16 conversion, same seeded accumulator, same MFMA chain in the same order
@@ -2157,25 +2114,7 @@ int dvq_launch_exact_list(const float *z, const float *prep, const float *E, con
                           const int *list, const int *list_count, DvqLossTail tail, const DvqRouted *rv,
                           hipStream_t st, const DvqConv *fold_conv = nullptr);
 
-// Launch-time choices of the filter path.  They are compile-time constants of the production library; only the
-// tuning build (-DDVQ_TUNING: libdvq_tuning.so, tools/) can change them, through dvq_tuning_set().
-struct DvqTune {
-    int sel_staged;      // routed op on a 32-wide output grid: coarser branches through LDS (SEL = 2) instead of per-lane loads
-    int res_slices;      // resolver slices over the code tiles, 0 = by codebook size
-    int flat;            // HW == 1 (row-major [N, D]) through the row-major form of pass 1 (0: through the NCHW kernel, for the A/B)
-    int split;           // small batches: several workgroups per token block (SPLIT form of pass 1); 0: never (for the A/B)
-};
 #ifdef DVQ_TUNING
-static DvqTune g_tune = {1, 0, 1, 1};
-extern "C" __attribute__((visibility("default"))) int dvq_tuning_set(const char *key, int value)
-{
-    if (!strcmp(key, "sel_staged")) g_tune.sel_staged = value;
-    else if (!strcmp(key, "res_slices")) g_tune.res_slices = value;
-    else if (!strcmp(key, "flat")) g_tune.flat = value;
-    else if (!strcmp(key, "split")) g_tune.split = value;
-    else return -1;
-    return 0;
-}
 // device buffer the tuning build's pass 1 writes its per-token diagnostics to (null = off): tokdbg [N][4] f32 = best, second,
 // 2W, code; stamps [workgroup][8] u64 = stage times of the split form of pass 1 (null = off)
 extern "C" __attribute__((visibility("default"))) int dvq_tuning_buffers(void *stamps, void *tokdbg)
@@ -2184,11 +2123,7 @@ extern "C" __attribute__((visibility("default"))) int dvq_tuning_buffers(void *s
     if (rc) return rc;
     return (int)hipMemcpyToSymbol(HIP_SYMBOL(g_dvq_tokdbg), &tokdbg, sizeof(void *));
 }
-#else
-static constexpr DvqTune g_tune = {1, 0, 1, 1};
 #endif
-
-static bool dvq_flat_form_enabled() { return g_tune.flat != 0; }
 
 // slots per shard (a multiple of RES_SLOTS); the whole record area holds DVQ_QSHARDS times that
 static int shard_capacity(long N)
@@ -2211,7 +2146,6 @@ bool dvq_filter_supported(int D, int HW, int K, long N)
 // resolver slices over the code tiles: 1 up to 64 tiles (K <= 2048), then one per 64 tiles, at most 8
 static int resolver_slices(int K)
 {
-    if (g_tune.res_slices >= 1 && g_tune.res_slices <= 8) return g_tune.res_slices;
     int T = dvq_num_tiles(K);
     int ns = (T + 63) / 64;
     return ns < 1 ? 1 : (ns > 8 ? 8 : ns);
@@ -2224,7 +2158,7 @@ static int resolver_slices(int K)
 static int split_slices(int K, long N)
 {
     const long nb = (N + 127) / 128;
-    if (!g_tune.split || nb > DVQ_SPLIT_MAX_BLOCKS) return 1;
+    if (nb > DVQ_SPLIT_MAX_BLOCKS) return 1;
     int ks = DVQ_SPLIT_MAX_SLICES;
     while (ks > 1 && (nb * ks > 256 || dvq_num_tiles(K) / ks < 2)) ks >>= 1;
     return ks;
@@ -2292,192 +2226,147 @@ static FilterWs carve_ws(void *ws_extra, long N, int D)
 // branch tensors the 16-byte DMA pieces can address
 static bool staged_select_ok(const DvqRouted &rv)
 {
-    if (!g_tune.sel_staged || rv.Wout != 32 || rv.HWout % 128 != 0) return false;
+    if (rv.Wout != 32 || rv.HWout % 128 != 0) return false;
     for (int g = 0; g < rv.G; ++g)
         if (((uintptr_t)rv.src[g] & 15) != 0) return false;
     return true;
 }
 
-template <int D, int SEL, bool CONV = false, bool FOLD = false>
-static int launch_pass1_form(const float *z, const char *img16, const DvqF16Meta *meta, const float *E,
-                             const float *mask, int HW, int K, long N, float *zq, long long *codes,
-                             double *partials, const FilterWs &w, const DvqRouted &rv, hipStream_t st,
-                             const DvqConv &cv = DvqConv{})
+// The forms of pass 1 (one kernel family each) and the plan of one launch
+enum class P1Form { plain, cached, flat, split, wide };
+struct P1Plan {
+    P1Form form;
+    int sel;                                                 // pass1_body's SEL
+    bool conv, fold, flat;                                   // ... CONV, FOLD and FLAT
+    int ks;                                                  // the split form's workgroups per token block
+};
+
+// The form of pass 1: for the op, the first row that applies.  fold: the conv folded into the codebook (it takes precedence over
+// conv); conv: the 1x1 conv as pass 1's prologue; routed: the select fused in; dense: none of these.  "Small batch":
+// split_slices(K, N) > 1 and the workspace has the split area; "aligned": z and zq 16-byte aligned; "fits":
+// N * D * 4 <= DVQ_CACHED_MAX_BYTES.
+//   | op                          | condition, in order                             | kernel                                     |
+//   |-----------------------------|-------------------------------------------------|--------------------------------------------|
+//   | fold                        | small batch                                     | split, SEL = rv ? 1 : 0, FOLD              |
+//   | fold, dense                 | HW == 1 and aligned                             | flat <D, FOLD = true>                      |
+//   | fold, dense / staged routed | D == 256 and fits                               | cached <D, SEL in {0, 2}, true>            |
+//   | fold                        | otherwise                                       | plain <D, SEL in {0, 1, 2}, false, true>   |
+//   | conv (D = 256, else -1000)  | small batch                                     | split, SEL = rv ? 1 : 0, CONV              |
+//   | conv                        | otherwise                                       | plain <256, rv ? 1 : 0, true, false>       |
+//   | routed                      | small batch                                     | split, SEL = 1                             |
+//   | routed                      | staged_select_ok                                | cached (D = 256, fits) else plain, SEL = 2 |
+//   | routed                      | otherwise                                       | plain, SEL = 1                             |
+//   | dense                       | D == 256 and (force_wide or K >= DVQ_WIDE_MIN_K | wide (checked BEFORE the small-batch test) |
+//   |                             | and N >= 256 * 512)                             |                                            |
+//   | dense                       | small batch                                     | split, FLAT = (HW == 1 and aligned)        |
+//   | dense                       | HW == 1 and aligned                             | flat <D, false>                            |
+//   | dense                       | D == 256 and fits                               | cached <D, 0, false>                       |
+//   | dense                       | otherwise                                       | plain <D, 0, false, false>                 |
+static P1Plan pass1_plan(int D, int HW, int K, long N, bool aligned, const FilterWs &w, bool force_wide, const DvqRouted *rv,
+                         bool conv, bool fold)
 {
-    static unsigned long long done = 0;
-    const size_t shmem1 = 4 * (size_t)(D / 16) * 1024 + 4 * 4 * 64 * sizeof(float) + 4 * 2048;
-    const unsigned grid = (unsigned)((N + 127) / 128);
-    if constexpr (SEL == 0 && !CONV && !FOLD) {
-        // fewer token blocks than CUs: several workgroups per block, each on a slice of the code tiles
-        const int ks = split_slices(K, N);
-        if (ks > 1 && w.split != nullptr) {
-            const bool flat = HW == 1 && dvq_flat_form_enabled() && (((uintptr_t)z | (uintptr_t)zq) & 15) == 0;
-            static unsigned long long done_s = 0, done_sf = 0;
-            int rcs = flat ? dvq_allow_dynamic_lds((const void *)vq_assign_filter_split_kernel<D, true>, (int)shmem1, &done_sf)
-                           : dvq_allow_dynamic_lds((const void *)vq_assign_filter_split_kernel<D, false>, (int)shmem1, &done_s);
-            if (rcs) return rcs;
-            if (flat)
-                hipLaunchKernelGGL((vq_assign_filter_split_kernel<D, true>), dim3(grid * ks), dim3(256), shmem1, st,
-                                   z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                                   w.cap / DVQ_QSHARDS, w.split, ks);
-            else
-                hipLaunchKernelGGL((vq_assign_filter_split_kernel<D, false>), dim3(grid * ks), dim3(256), shmem1, st,
-                                   z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                                   w.cap / DVQ_QSHARDS, w.split, ks);
-            return (int)hipGetLastError();
-        }
-    }
-    if constexpr (SEL == 0 && !CONV) {
-        // HW == 1 is a row-major [N, D] tensor: 16-byte accesses along a token's row (rows are 16-byte aligned: D % 16 == 0)
-        if (HW == 1 && dvq_flat_form_enabled() && (((uintptr_t)z | (uintptr_t)zq) & 15) == 0) {
-            static unsigned long long done_f = 0;
-            int rcf = dvq_allow_dynamic_lds((const void *)vq_assign_filter_flat_kernel<D, FOLD>, (int)shmem1, &done_f);
-            if (rcf) return rcf;
-            hipLaunchKernelGGL((vq_assign_filter_flat_kernel<D, FOLD>), dim3(grid), dim3(256), shmem1, st,
-                               z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                               w.cap / DVQ_QSHARDS, rv, cv);
-            return (int)hipGetLastError();
-        }
-    }
-    if constexpr (D == 256 && !CONV && SEL != 1) {
-        // a batch whose features fit the memory-side cache (with room for what else is live): plain loads instead of non-temporal ones
-        if ((size_t)N * D * sizeof(float) <= DVQ_CACHED_MAX_BYTES) {
-            static unsigned long long done_c = 0;
-            int rcc = dvq_allow_dynamic_lds((const void *)vq_assign_filter_cached_kernel<D, SEL, FOLD>, (int)shmem1, &done_c);
-            if (rcc) return rcc;
-            hipLaunchKernelGGL((vq_assign_filter_cached_kernel<D, SEL, FOLD>), dim3(grid), dim3(256), shmem1, st,
-                               z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                               w.cap / DVQ_QSHARDS, rv, cv);
-            return (int)hipGetLastError();
-        }
-    }
-    int rc = dvq_allow_dynamic_lds((const void *)vq_assign_filter_kernel<D, SEL, CONV, FOLD>, (int)shmem1, &done);
-    if (rc) return rc;
-    hipLaunchKernelGGL((vq_assign_filter_kernel<D, SEL, CONV, FOLD>), dim3(grid), dim3(256), shmem1, st,
-                       z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                       w.cap / DVQ_QSHARDS, rv, cv);
-    return (int)hipGetLastError();
+    const bool dense = rv == nullptr && !conv && !fold;
+    if (dense && D == 256 && (force_wide || (K >= DVQ_WIDE_MIN_K && N >= 256L * 512)))   // large codebook and enough tokens to fill
+        return {P1Form::wide, 0, false, false, false, 1};                                 // every CU with two 256-token workgroups
+    const int ks = split_slices(K, N);
+    if (ks > 1 && w.split != nullptr)                        // fewer token blocks than CUs: several workgroups per block
+        return {P1Form::split, rv != nullptr ? 1 : 0, conv, fold, dense && HW == 1 && aligned, ks};
+    if (conv) return {P1Form::plain, rv != nullptr ? 1 : 0, true, false, false, 1};
+    const int sel = rv == nullptr ? 0 : (staged_select_ok(*rv) ? 2 : 1);
+    // HW == 1 is a row-major [N, D] tensor: 16-byte accesses along a token's row (rows are 16-byte aligned: D % 16 == 0)
+    if (sel == 0 && HW == 1 && aligned) return {P1Form::flat, 0, false, fold, true, 1};
+    // a batch whose features fit the memory-side cache (with room for what else is live): plain loads instead of non-temporal ones
+    if (sel != 1 && D == 256 && (size_t)N * D * sizeof(float) <= DVQ_CACHED_MAX_BYTES) return {P1Form::cached, sel, false, fold, false, 1};
+    return {P1Form::plain, sel, false, fold, false, 1};
 }
 
-template <int D>
-static int launch_pass1(const float *z, const char *img, const DvqF16Meta *meta, const float *E,
-                        const float *mask, int HW, int K, long N, float *zq, long long *codes,
-                        double *partials, const FilterWs &w, bool force_wide, const DvqRouted *rv,
-                        hipStream_t st, const DvqConv *cv, const DvqConv *fold_cv)
+struct P1Args {
+    const float *z;
+    const char *img16;
+    const DvqF16Meta *meta;
+    const float *E, *mask;
+    int HW, K;
+    long N;
+    float *zq;
+    long long *codes;
+    double *partials;
+    const FilterWs &w;
+    DvqRouted rv;
+    DvqConv cv;
+    hipStream_t st;
+};
+
+// One launch site per kernel family.  `if constexpr` keeps to the kernels the plans use: 20 plain, 4 cached, 6 flat, 17 split, 1 wide.
+template <int D, int SEL, bool CONV, bool FOLD, bool FLAT>
+static int launch_pass1_form(const P1Plan &p, const P1Args &a)
 {
-    const int nb1 = (int)((N + 127) / 128);
-    const char *img16 = img + dvq_img16_offset(K, D);       // the code loop runs on v_mfma_f32_16x16x32_f16
-    const DvqRouted none = {};
-    const DvqConv nocv = {};
-    if (fold_cv != nullptr) {                                // img / meta: the folded codebook; z (or the branches): the conv's input
-        if (const int ks = split_slices(K, N); ks > 1 && w.split != nullptr) {   // small batch: several workgroups per token block
-            static unsigned long long done_f0 = 0, done_f1 = 0;
-            const size_t shm = 4 * (size_t)(D / 16) * 1024 + 4 * 4 * 64 * sizeof(float) + 4 * 2048;
-            int rcs = rv != nullptr ? dvq_allow_dynamic_lds((const void *)vq_assign_filter_split_fold_kernel<D, 1>, (int)shm, &done_f1)
-                                    : dvq_allow_dynamic_lds((const void *)vq_assign_filter_split_fold_kernel<D, 0>, (int)shm, &done_f0);
-            if (rcs) return rcs;
-            if (rv != nullptr)
-                hipLaunchKernelGGL((vq_assign_filter_split_fold_kernel<D, 1>), dim3((unsigned)nb1 * ks), dim3(256), shm, st,
-                                   z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                                   w.cap / DVQ_QSHARDS, *rv, *fold_cv, w.split, ks);
-            else
-                hipLaunchKernelGGL((vq_assign_filter_split_fold_kernel<D, 0>), dim3((unsigned)nb1 * ks), dim3(256), shm, st,
-                                   z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                                   w.cap / DVQ_QSHARDS, none, *fold_cv, w.split, ks);
-            return (int)hipGetLastError();
-        }
-        if (rv == nullptr)
-            return launch_pass1_form<D, 0, false, true>(z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w, none, st, *fold_cv);
-        if (staged_select_ok(*rv))
-            return launch_pass1_form<D, 2, false, true>(z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w, *rv, st, *fold_cv);
-        return launch_pass1_form<D, 1, false, true>(z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w, *rv, st, *fold_cv);
+    const unsigned nb = (unsigned)((a.N + 127) / 128);
+    const size_t lds = dvq_pass1_lds_bytes(D);
+#define DVQ_P1_ARGS a.z, a.img16, a.meta, a.E, a.mask, a.HW, a.K, a.N, a.zq, a.codes, a.partials, a.w.counters, a.w.exact_list, \
+                    a.w.records, a.w.cap / DVQ_QSHARDS
+    switch (p.form) {
+    case P1Form::plain:
+        if constexpr (!FLAT)
+            return dvq_launch_lds<vq_assign_filter_kernel<D, SEL, CONV, FOLD>>(dim3(nb), dim3(256), lds, a.st, DVQ_P1_ARGS, a.rv, a.cv);
+        break;
+    case P1Form::cached:
+        if constexpr (D == 256 && SEL != 1 && !CONV && !FLAT)
+            return dvq_launch_lds<vq_assign_filter_cached_kernel<D, SEL, FOLD>>(dim3(nb), dim3(256), lds, a.st, DVQ_P1_ARGS, a.rv, a.cv);
+        break;
+    case P1Form::flat:
+        if constexpr (FLAT)
+            return dvq_launch_lds<vq_assign_filter_flat_kernel<D, FOLD>>(dim3(nb), dim3(256), lds, a.st, DVQ_P1_ARGS, a.rv, a.cv);
+        break;
+    case P1Form::split:
+        if constexpr (SEL != 2 && !(FLAT && FOLD))
+            return dvq_launch_lds<vq_assign_filter_split_kernel<D, SEL, CONV, FOLD, FLAT>>(dim3(nb * p.ks), dim3(256), lds, a.st,
+                                                                                         DVQ_P1_ARGS, a.rv, a.cv, a.w.split, p.ks);
+        break;
+    case P1Form::wide:
+        if constexpr (D == 256 && SEL == 0 && !CONV && !FOLD && !FLAT)
+            return dvq_launch_lds<vq_assign_filter_wide_kernel<D>>(dim3((unsigned)((a.N + 255) / 256)), dim3(256), lds, a.st,
+                                                                   DVQ_P1_ARGS, (int)nb);
+        break;
     }
-    if (cv != nullptr) {                                     // the 1x1 conv as the prologue (D = 256; the ABI layer checked)
-        if constexpr (D == 256) {
-            if (const int ks = split_slices(K, N); ks > 1 && w.split != nullptr) {   // small batch: several workgroups per token block
-                static unsigned long long done_c0 = 0, done_c1 = 0;
-                const size_t shm = 4 * (size_t)(D / 16) * 1024 + 4 * 4 * 64 * sizeof(float) + 4 * 2048;
-                int rcs = rv != nullptr ? dvq_allow_dynamic_lds((const void *)vq_assign_filter_split_conv_kernel<D, 1>, (int)shm, &done_c1)
-                                        : dvq_allow_dynamic_lds((const void *)vq_assign_filter_split_conv_kernel<D, 0>, (int)shm, &done_c0);
-                if (rcs) return rcs;
-                if (rv != nullptr)
-                    hipLaunchKernelGGL((vq_assign_filter_split_conv_kernel<D, 1>), dim3((unsigned)nb1 * ks), dim3(256), shm, st,
-                                       z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                                       w.cap / DVQ_QSHARDS, *rv, *cv, w.split, ks);
-                else
-                    hipLaunchKernelGGL((vq_assign_filter_split_conv_kernel<D, 0>), dim3((unsigned)nb1 * ks), dim3(256), shm, st,
-                                       z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                                       w.cap / DVQ_QSHARDS, none, *cv, w.split, ks);
-                return (int)hipGetLastError();
-            }
-            if (rv != nullptr)
-                return launch_pass1_form<D, 1, true>(z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w, *rv, st, *cv);
-            return launch_pass1_form<D, 0, true>(z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w, none, st, *cv);
-        } else {
-            return -1000;
-        }
-    }
-    if (rv != nullptr) {                                     // select fused in
-        if (const int ks = split_slices(K, N); ks > 1 && w.split != nullptr) {   // small batch: several workgroups per token block
-            static unsigned long long done_ss = 0;
-            const size_t shm = 4 * (size_t)(D / 16) * 1024 + 4 * 4 * 64 * sizeof(float) + 4 * 2048;
-            int rcs = dvq_allow_dynamic_lds((const void *)vq_assign_filter_split_sel_kernel<D>, (int)shm, &done_ss);
-            if (rcs) return rcs;
-            hipLaunchKernelGGL((vq_assign_filter_split_sel_kernel<D>), dim3((unsigned)nb1 * ks), dim3(256), shm, st,
-                               z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list, w.records,
-                               w.cap / DVQ_QSHARDS, *rv, w.split, ks);
-            return (int)hipGetLastError();
-        }
-        if (staged_select_ok(*rv))
-            return launch_pass1_form<D, 2>(z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w, *rv, st, nocv);
-        return launch_pass1_form<D, 1>(z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w, *rv, st, nocv);
-    }
-    if constexpr (D == 256) {
-        if (force_wide || (K >= DVQ_WIDE_MIN_K && N >= 256L * 512)) {   // large codebook and enough tokens to fill every CU
-                                                             // with two 256-token workgroups: two blocks per wave
-            static unsigned long long done_w = 0;
-            const unsigned gridw = (unsigned)((N + 255) / 256);
-            const size_t shm = 4 * (size_t)(D / 16) * 1024 + 4 * 4 * 64 * sizeof(float) + 4 * 2048;
-            int rc = dvq_allow_dynamic_lds((const void *)vq_assign_filter_wide_kernel<D>, (int)shm, &done_w);
-            if (rc) return rc;
-            hipLaunchKernelGGL((vq_assign_filter_wide_kernel<D>), dim3(gridw), dim3(256), shm, st,
-                               z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w.counters, w.exact_list,
-                               w.records, w.cap / DVQ_QSHARDS, nb1);
-            return (int)hipGetLastError();
-        }
-    }
-    return launch_pass1_form<D, 0>(z, img16, meta, E, mask, HW, K, N, zq, codes, partials, w, none, st, nocv);
+#undef DVQ_P1_ARGS
+    return -1000;
 }
 
+// the plan's flags as template arguments
 template <int D>
-static int launch_resolver(const char *img, const DvqF16Meta *meta, const float *en_all, const float *E,
+static int launch_pass1(const P1Plan &p, const P1Args &a)
+{
+    if (p.conv) {
+        if constexpr (D == 256)
+            return p.sel ? launch_pass1_form<D, 1, true, false, false>(p, a) : launch_pass1_form<D, 0, true, false, false>(p, a);
+        return -1000;
+    }
+    if (p.flat) return p.fold ? launch_pass1_form<D, 0, false, true, true>(p, a) : launch_pass1_form<D, 0, false, false, true>(p, a);
+    switch (p.sel) {
+    case 0:  return p.fold ? launch_pass1_form<D, 0, false, true, false>(p, a) : launch_pass1_form<D, 0, false, false, false>(p, a);
+    case 1:  return p.fold ? launch_pass1_form<D, 1, false, true, false>(p, a) : launch_pass1_form<D, 1, false, false, false>(p, a);
+    default: return p.fold ? launch_pass1_form<D, 2, false, true, false>(p, a) : launch_pass1_form<D, 2, false, false, false>(p, a);
+    }
+}
+
+static int launch_resolver(int D, const char *img, const DvqF16Meta *meta, const float *en_all, const float *E,
                            int HWout, int K, float *zq, long long *codes, double *partials,
                            const FilterWs &w, int Wout, float *h_spill, const DvqFold *fd, hipStream_t st,
                            const double *p1_partials, int np1)
 {
-    const int nslice = resolver_slices(K);
-    if (fd != nullptr)
-        hipLaunchKernelGGL((vq_resolve_kernel<D, true>), dim3(w.cap / RES_SLOTS, nslice), dim3(DVQ_RES_WAVES * 64), 0, st, img,
-                           meta, en_all, E, HWout, K, zq, codes, partials, w.counters, w.exact_list, w.records,
-                           w.cap / DVQ_QSHARDS, nslice, w.chunk_sync, Wout, h_spill, fd->cv, p1_partials, np1);
-    else
-        hipLaunchKernelGGL((vq_resolve_kernel<D, false>), dim3(w.cap / RES_SLOTS, nslice), dim3(DVQ_RES_WAVES * 64), 0, st, img,
-                           meta, en_all, E, HWout, K, zq, codes, partials, w.counters, w.exact_list, w.records,
-                           w.cap / DVQ_QSHARDS, nslice, w.chunk_sync, Wout, h_spill, DvqConv{}, p1_partials, np1);
-    return (int)hipGetLastError();
-}
-
-static int launch_resolver_d(int D, const char *img, const DvqF16Meta *meta, const float *en_all, const float *E,
-                             int HWout, int K, float *zq, long long *codes, double *partials,
-                             const FilterWs &w, int Wout, float *h_spill, const DvqFold *fd, hipStream_t st,
-                             const double *p1_partials, int np1)
-{
+    const bool fold = fd != nullptr;
+    decltype(&vq_resolve_kernel<64, false>) kernel;
     switch (D) {
-    case 64:  return launch_resolver<64>(img, meta, en_all, E, HWout, K, zq, codes, partials, w, Wout, h_spill, fd, st, p1_partials, np1);
-    case 128: return launch_resolver<128>(img, meta, en_all, E, HWout, K, zq, codes, partials, w, Wout, h_spill, fd, st, p1_partials, np1);
-    case 256: return launch_resolver<256>(img, meta, en_all, E, HWout, K, zq, codes, partials, w, Wout, h_spill, fd, st, p1_partials, np1);
+    case 64:  kernel = fold ? vq_resolve_kernel<64, true> : vq_resolve_kernel<64, false>; break;
+    case 128: kernel = fold ? vq_resolve_kernel<128, true> : vq_resolve_kernel<128, false>; break;
+    case 256: kernel = fold ? vq_resolve_kernel<256, true> : vq_resolve_kernel<256, false>; break;
     default:  return -1000;
     }
+    const int nslice = resolver_slices(K);
+    hipLaunchKernelGGL(kernel, dim3(w.cap / RES_SLOTS, nslice), dim3(DVQ_RES_WAVES * 64), 0, st, img, meta, en_all, E, HWout, K,
+                       zq, codes, partials, w.counters, w.exact_list, w.records, w.cap / DVQ_QSHARDS, nslice, w.chunk_sync, Wout,
+                       h_spill, fold ? fd->cv : DvqConv{}, p1_partials, np1);
+    return (int)hipGetLastError();
 }
 
 // Dense op: z [B, D, HW].  Routed op (rv != nullptr): one token per output position of rv (the select fused into
@@ -2508,16 +2397,20 @@ int dvq_launch_filter(const float *z, const void *prep, const float *E, const fl
         if (rc) return rc;
     }
     const int np1 = (int)((N + 127) / 128);
-    const DvqConv *fold_cv = fd ? &fd->cv : nullptr;
-    switch (D) {
-    case 64:  rc = launch_pass1<64>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, w, force_wide, rv, st, cv, fold_cv); break;
-    case 128: rc = launch_pass1<128>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, w, force_wide, rv, st, cv, fold_cv); break;
-    case 256: rc = launch_pass1<256>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, w, force_wide, rv, st, cv, fold_cv); break;
+    const DvqConv *conv = fd != nullptr ? &fd->cv : cv;      // the conv folded into the codebook or computed by pass 1
+    const bool aligned = (((uintptr_t)z | (uintptr_t)zq) & 15) == 0;
+    const P1Plan plan = pass1_plan(D, HW, K, N, aligned, w, force_wide, rv, fd == nullptr && cv != nullptr, fd != nullptr);
+    const P1Args args = {z, img + dvq_img16_offset(K, D), meta, E, mask, HW, K, N, zq, codes, partials, w,
+                         routed ? *rv : DvqRouted{}, conv != nullptr ? *conv : DvqConv{}, st};
+    switch (D) {                                             // (pass 1's code loop runs on v_mfma_f32_16x16x32_f16: image "16")
+    case 64:  rc = launch_pass1<64>(plan, args); break;
+    case 128: rc = launch_pass1<128>(plan, args); break;
+    case 256: rc = launch_pass1<256>(plan, args); break;
     default:  return -1000;
     }
     if (rc || pass1_only) return rc;
     const int HWout = routed ? rv->HWout : HW, Wout = routed ? rv->Wout : 0;
-    rc = launch_resolver_d(D, img, meta, en_all, E, HWout, K, zq, codes, partials ? partials + np1 : nullptr,
+    rc = launch_resolver(D, img, meta, en_all, E, HWout, K, zq, codes, partials ? partials + np1 : nullptr,
                            w, Wout, nullptr, fd, st, partials, np1);
     if (rc) return rc;
     double *partials3 = partials ? partials + np1 + w.cap / RES_SLOTS : nullptr;
@@ -2527,17 +2420,11 @@ int dvq_launch_filter(const float *z, const void *prep, const float *E, const fl
                               w.cap / RES_SLOTS + list_blocks(N),
                               1.0 / ((double)N * D), beta, w.counters, w.cap / DVQ_QSHARDS};
     const int *list_count = w.counters + DVQ_C_EXACT;
-    // conv folded in: the list kernel computes its tokens' h itself, from the conv's input (dense z or the branches)
-    if (fd != nullptr)
-        return dvq_launch_exact_list(z, (const float *)prep, E, mask, D, HWout, K, N, zq, codes, partials3,
-                                     w.exact_list, list_count, tail, rv, st, &fd->cv);
-    // conv fused into pass 1: the same -- the list kernel's conv is qconv.hip's arithmetic, what pass 1's prologue computes too (and
-    // with h_all it writes the h it scored over pass 1's row of the token)
-    if (cv != nullptr)
-        return dvq_launch_exact_list(z, (const float *)prep, E, mask, D, HWout, K, N, zq, codes, partials3,
-                                     w.exact_list, list_count, tail, rv, st, cv);
-    return dvq_launch_exact_list(z, (const float *)prep, E, mask, D, HWout, K, N, zq, codes, partials3,
-                                 w.exact_list, list_count, tail, rv, st);
+    // conv folded in or fused into pass 1: the list kernel computes its tokens' h itself, from the conv's input (dense z or the
+    // branches) -- qconv.hip's arithmetic, what pass 1's prologue computes too (and with h_all it writes the h it scored over pass
+    // 1's row of the token)
+    return dvq_launch_exact_list(z, (const float *)prep, E, mask, D, HWout, K, N, zq, codes, partials3, w.exact_list, list_count,
+                                 tail, rv, st, conv);
 }
 
 // ---- routed op ---------------------------------------------------------------------------------

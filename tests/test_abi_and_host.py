@@ -37,8 +37,8 @@ def test_dynamic_symbol_table_is_exactly_the_abi():
     syms = sorted(ln.split()[-1] for ln in out.splitlines() if ln.strip())
     assert not [s for s in syms if s.startswith("_Z") or "__device_stub__" in s or "__hip" in s], syms
     extra = set(syms) - set(_declared())
-    if os.path.basename(_lib.LIB_PATH) != "libdvq.so":          # DVQ_LIBRARY=<tuning build>: plus its A/B switches
-        extra = {s for s in extra if not s.startswith("dvq_tuning_")}
+    if os.path.basename(_lib.LIB_PATH) != "libdvq.so":          # DVQ_LIBRARY=<tuning build>: plus its diagnostics buffers
+        extra -= {"dvq_tuning_buffers"}
     assert not extra, extra
     assert set(_declared()) <= set(syms)
 
@@ -76,10 +76,10 @@ def test_header_is_plain_c_and_links_from_a_c_program(tmp_path):
 
 def test_documents_name_only_entry_points_that_exist():
     """every `dvq_*` identifier README / INTEGRATION / DESIGN / profiles/README spell out in full is declared in include/dvq.h
-    (patterns with braces or wildcards and prefixes ending in `_` are skipped); the tuning build's two extra exports, the
+    (patterns with braces or wildcards and prefixes ending in `_` are skipped); the tuning build's extra export, the
     snippet's own Python function and two file stems are the only other names"""
     decl = set(_declared())
-    other = {"dvq_tuning_set", "dvq_tuning_buffers", "dvq_forward", "dvq_filter", "dvq_oracle", "dvq_common", "dvq_abi"}
+    other = {"dvq_tuning_buffers", "dvq_forward", "dvq_filter", "dvq_oracle", "dvq_common", "dvq_abi"}
     for doc in ("README.md", "INTEGRATION.md", "DESIGN.md", os.path.join("profiles", "README.md")):
         text = open(os.path.join(ROOT, doc)).read()
         names = set(re.findall(r"(?<![A-Za-z0-9_*{}])(dvq_[a-z0-9_]+)(?![A-Za-z0-9_*{}])", text))
@@ -233,7 +233,7 @@ def test_conv_prologue_isa_has_no_load_hazards():
 
 def test_product_library_reads_no_environment():
     """include/dvq.h promises that libdvq.so reads no environment variable (kernel choices are functions of the arguments and
-    compile-time constants): the product library does not even import getenv; the A/B switches live in libdvq_tuning.so"""
+    compile-time constants): the product library does not even import getenv"""
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

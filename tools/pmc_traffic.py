@@ -62,8 +62,7 @@ if "model_pass1" in kernels:
                     "ratio_to_line_granular_floor": kernels["model_pass1"]["hbm_bytes_per_launch"] / floor,
                     "note": "per-lane select form (the ring slots the staged form parks the coarse branch in carry the conv's weights)"}
 # the routed pass 1's fetch split by what it is.  Dispatches of vq_assign_filter_kernel<256, 2, false, false>
-# in tools/pmc_workload.py order: [0:4] the whole op (3), then -- after the per-lane-select runs, a different instantiation --
-# [4:8] pass 1 alone (6), [8:12] codes only (7: no e-row gather), [12:16] codes only against K = 32 (8: one code tile)
+# in tools/pmc_workload.py order: [0:4] the whole op (3), then [4:8] pass 1 alone (6), [8:12] codes only (7: no e-row gather), [12:16] codes only against K = 32 (8: one code tile)
 kf = find(fetch, "vq_assign_filter_kernel<256, 2, false, false>")
 kw = find(write, "vq_assign_filter_kernel<256, 2, false, false>")
 if kf is not None and len(fetch[kf]) >= 16:
