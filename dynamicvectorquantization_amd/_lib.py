@@ -42,6 +42,7 @@ EXPORTS = (
     "dvq_vq_assign_routed_fold_triple_f32", "dvq_debug_fold_scores_f32",
     "dvq_entropy_gate_f32", "dvq_route_select_dual_f32", "dvq_route_select_dual_entropy_f32", "dvq_route_select_triple_f32",
     "dvq_entropy_map_f32", "dvq_ema_accumulate_nchw_f32", "dvq_restart_pick_i64", "dvq_ema_update_f32", "dvq_router_gate_workspace_bytes", "dvq_router_gate_prep_bytes", "dvq_router_gate_prepare_f32", "dvq_router_gate_prepare_norm_f32", "dvq_router_gate_f32", "dvq_permute_dual_count_i64", "dvq_permute_dual_forward_i64", "dvq_permute_dual_backward_i64",
+    "dvq_route_train_workspace_bytes", "dvq_route_train_forward_f32", "dvq_route_train_backward_f32",
 )
 
 
@@ -164,6 +165,13 @@ def _load():
     lib.dvq_router_gate_f32.restype = i32
     lib.dvq_router_gate_f32.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp,
                                         vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]
+    lib.dvq_route_train_workspace_bytes.restype = sz
+    lib.dvq_route_train_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32]
+    _rt_in = [i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, f32]
+    lib.dvq_route_train_forward_f32.restype = i32
+    lib.dvq_route_train_forward_f32.argtypes = _rt_in + [vp, vp, vp, vp, vp, sz, vp]
+    lib.dvq_route_train_backward_f32.restype = i32
+    lib.dvq_route_train_backward_f32.argtypes = _rt_in + [vp, vp, vp, sz] + [vp] * 3 + [vp] * 6 + [vp] * 4 + [vp]
     lib.dvq_entropy_map_f32.restype = i32
     lib.dvq_entropy_map_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.dvq_permute_dual_count_i64.restype = i32

@@ -6,7 +6,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 600   // 0.6.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 700   // 0.7.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -79,6 +79,9 @@ int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn
                            int B, int C, int hc, int wc, int groups, float eps,
                            const float *W1, const float *b1, const float *W2, const float *b2,
                            int Hid, int act, const void *w1_prep, float *gate, void *ws, hipStream_t st);
+size_t dvq_route_train_ws_bytes(int nb, int B, int C, int hc, int wc, int groups, int H);
+int dvq_launch_route_train_fwd(const DvqRouteTrain *p, hipStream_t st);
+int dvq_launch_route_train_bwd(const DvqRouteTrain *p, hipStream_t st);
 
 size_t dvq_qconv_prep_bytes_impl(int D);
 int dvq_launch_qconv_prep(const float *Wt, const float *bias, int D, void *prep, hipStream_t st);
@@ -668,6 +671,106 @@ int dvq_router_gate_f32(int nb, const float *h_coarse, const float *h_median, co
     return hip_rc(dvq_launch_router_gate(nb, h, gw, gb, B, C, hc, wc, num_groups, eps, w1, b1, w2, b2,
                                          activation == DVQ_ACT_NONE ? 32 : hidden, activation, w1_prep, gate, ws,
                                          (hipStream_t)stream), "router_gate");
+}
+
+// shared argument checks of the training-mode routing tail; fills the branch / parameter slots of *a
+static int route_train_args(const char *fn, DvqRouteTrain *a, int nb, const float *h_coarse, const float *h_median, const float *h_fine,
+                            int B, int C, int hc, int wc, int num_groups, float eps,
+                            const float *gn_w_coarse, const float *gn_b_coarse, const float *gn_w_median, const float *gn_b_median,
+                            const float *gn_w_fine, const float *gn_b_fine, const float *w1, const float *b1, const float *w2,
+                            const float *b2, int hidden, int activation, const float *gumbels, float tau, void *ws, size_t ws_bytes)
+{
+    if (nb != 2 && nb != 3) { dvq_set_error("%s: num_branches=%d (2 or 3)", fn, nb); return DVQ_EINVAL; }
+    if (!h_coarse || !h_fine || !w2 || !b2) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if ((nb == 3) != (h_median != nullptr)) { dvq_set_error("%s: h_median must be given exactly when num_branches == 3", fn); return DVQ_EINVAL; }
+    if (B <= 0 || C <= 0 || hc <= 0 || wc <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
+    if (activation != DVQ_ACT_NONE && activation != DVQ_ACT_SILU && activation != DVQ_ACT_RELU) { dvq_set_error("%s: unknown activation %d", fn, activation); return DVQ_EINVAL; }
+    if (activation != DVQ_ACT_NONE && (!w1 || !b1 || hidden <= 0)) { dvq_set_error("%s: hidden layer requested without w1 / b1 / hidden", fn); return DVQ_EINVAL; }
+    if (activation == DVQ_ACT_NONE && hidden != 0) { dvq_set_error("%s: hidden must be 0 with DVQ_ACT_NONE", fn); return DVQ_EINVAL; }
+    if (num_groups < 0 || (num_groups > 0 && C % num_groups != 0)) { dvq_set_error("%s: C=%d is not divisible by num_groups=%d", fn, C, num_groups); return DVQ_EINVAL; }
+    if (num_groups > 0 && (!gn_w_coarse || !gn_b_coarse || !gn_w_fine || !gn_b_fine || (nb == 3 && (!gn_w_median || !gn_b_median)))) {
+        dvq_set_error("%s: GroupNorm affine parameters missing", fn); return DVQ_EINVAL;
+    }
+    if (!(tau > 0.0f)) { dvq_set_error("%s: tau must be positive", fn); return DVQ_EINVAL; }
+    const int S = nb == 2 ? 2 : 4;
+    if (C % 8 != 0 || nb * C > 1280 || hidden > 1280) { dvq_set_error("%s: C=%d hidden=%d unsupported (C %% 8 == 0, num_branches*C <= 1280, hidden <= 1280)", fn, C, hidden); return DVQ_EUNSUPPORTED; }
+    if ((long)S * wc > 4096 || (double)B * C * S * hc * S * wc >= 2147483648.0) { dvq_set_error("%s: grid %dx%d x B=%d too large", fn, hc, wc, B); return DVQ_EUNSUPPORTED; }
+    const size_t need = dvq_route_train_ws_bytes(nb, B, C, hc, wc, num_groups, hidden);
+    if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, need); return DVQ_EWORKSPACE; }
+    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    *a = DvqRouteTrain{};
+    a->nb = nb; a->B = B; a->C = C; a->hc = hc; a->wc = wc; a->groups = num_groups; a->eps = eps;
+    const float *hs[3] = {h_coarse, nb == 3 ? h_median : h_fine, h_fine};
+    const float *gw[3] = {gn_w_coarse, nb == 3 ? gn_w_median : gn_w_fine, gn_w_fine};
+    const float *gb[3] = {gn_b_coarse, nb == 3 ? gn_b_median : gn_b_fine, gn_b_fine};
+    for (int i = 0; i < 3; ++i) { a->h[i] = i < nb ? hs[i] : nullptr; a->gn_w[i] = i < nb ? gw[i] : nullptr; a->gn_b[i] = i < nb ? gb[i] : nullptr; }
+    a->w1 = w1; a->b1 = b1; a->w2 = w2; a->b2 = b2;
+    a->hid = activation == DVQ_ACT_NONE ? 0 : hidden;
+    a->act = activation;
+    a->gumbels = gumbels; a->tau = tau; a->ws = ws;
+    return DVQ_OK;
+}
+
+size_t dvq_route_train_workspace_bytes(int nb, int B, int C, int hc, int wc, int num_groups, int hidden)
+{
+    if ((nb != 2 && nb != 3) || B <= 0 || C <= 0 || hc <= 0 || wc <= 0 || num_groups < 0 || hidden < 0) return 0;
+    if (C % 8 != 0 || nb * C > 1280 || hidden > 1280) return 0;
+    return dvq_route_train_ws_bytes(nb, B, C, hc, wc, num_groups, hidden);
+}
+
+int dvq_route_train_forward_f32(int nb, const float *h_coarse, const float *h_median, const float *h_fine,
+                                int B, int C, int hc, int wc, int num_groups, float eps,
+                                const float *gn_w_coarse, const float *gn_b_coarse,
+                                const float *gn_w_median, const float *gn_b_median,
+                                const float *gn_w_fine, const float *gn_b_fine,
+                                const float *w1, const float *b1, const float *w2, const float *b2,
+                                int hidden, int activation, const float *gumbels, float tau,
+                                float *h_out, int64_t *indices, float *codebook_mask, float *gate,
+                                void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_route_train_forward_f32";
+    DvqRouteTrain a;
+    const int rc = route_train_args(fn, &a, nb, h_coarse, h_median, h_fine, B, C, hc, wc, num_groups, eps, gn_w_coarse, gn_b_coarse,
+                                    gn_w_median, gn_b_median, gn_w_fine, gn_b_fine, w1, b1, w2, b2, hidden, activation, gumbels, tau,
+                                    ws, ws_bytes);
+    if (rc != DVQ_OK) return rc;
+    if (!h_out || !indices || !codebook_mask || !gate) { dvq_set_error("%s: null output pointer", fn); return DVQ_EINVAL; }
+    a.h_out = h_out; a.indices = (long long *)indices; a.cmask = codebook_mask; a.gate = gate;
+    return hip_rc(dvq_launch_route_train_fwd(&a, (hipStream_t)stream), "route_train_forward");
+}
+
+int dvq_route_train_backward_f32(int nb, const float *h_coarse, const float *h_median, const float *h_fine,
+                                 int B, int C, int hc, int wc, int num_groups, float eps,
+                                 const float *gn_w_coarse, const float *gn_b_coarse,
+                                 const float *gn_w_median, const float *gn_b_median,
+                                 const float *gn_w_fine, const float *gn_b_fine,
+                                 const float *w1, const float *b1, const float *w2, const float *b2,
+                                 int hidden, int activation, const float *gumbels, float tau,
+                                 const float *g_out, const float *g_gate, void *ws, size_t ws_bytes,
+                                 float *dh_coarse, float *dh_median, float *dh_fine,
+                                 float *dgn_w_coarse, float *dgn_b_coarse, float *dgn_w_median, float *dgn_b_median,
+                                 float *dgn_w_fine, float *dgn_b_fine,
+                                 float *dw1, float *db1, float *dw2, float *db2, void *stream)
+{
+    const char *fn = "dvq_route_train_backward_f32";
+    DvqRouteTrain a;
+    const int rc = route_train_args(fn, &a, nb, h_coarse, h_median, h_fine, B, C, hc, wc, num_groups, eps, gn_w_coarse, gn_b_coarse,
+                                    gn_w_median, gn_b_median, gn_w_fine, gn_b_fine, w1, b1, w2, b2, hidden, activation, gumbels, tau,
+                                    ws, ws_bytes);
+    if (rc != DVQ_OK) return rc;
+    if (!dh_coarse || !dh_fine || (nb == 3 && !dh_median) || !dw2 || !db2 || (a.hid > 0 && (!dw1 || !db1))) {
+        dvq_set_error("%s: null output pointer", fn); return DVQ_EINVAL;
+    }
+    if (num_groups > 0 && (!dgn_w_coarse || !dgn_b_coarse || !dgn_w_fine || !dgn_b_fine || (nb == 3 && (!dgn_w_median || !dgn_b_median)))) {
+        dvq_set_error("%s: GroupNorm gradient outputs missing", fn); return DVQ_EINVAL;
+    }
+    a.g_out = g_out; a.g_gate = g_gate;
+    float *dh[3] = {dh_coarse, nb == 3 ? dh_median : dh_fine, dh_fine};
+    float *dw[3] = {dgn_w_coarse, nb == 3 ? dgn_w_median : dgn_w_fine, dgn_w_fine};
+    float *db[3] = {dgn_b_coarse, nb == 3 ? dgn_b_median : dgn_b_fine, dgn_b_fine};
+    for (int i = 0; i < 3; ++i) { a.dh[i] = i < nb ? dh[i] : nullptr; a.dgn_w[i] = i < nb ? dw[i] : nullptr; a.dgn_b[i] = i < nb ? db[i] : nullptr; }
+    a.dw1 = dw1; a.db1 = db1; a.dw2 = dw2; a.db2 = db2;
+    return hip_rc(dvq_launch_route_train_bwd(&a, (hipStream_t)stream), "route_train_backward");
 }
 
 int dvq_entropy_map_f32(const float *images, int B, int H, int W, int patch, float *out, void *stream)

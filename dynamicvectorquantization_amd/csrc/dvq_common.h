@@ -159,3 +159,19 @@ static inline int dvq_launch_lds(dim3 grid, dim3 block, size_t lds, hipStream_t 
 
 // per-launch host-side error plumbing (dvq_abi.hip)
 void dvq_set_error(const char *fmt, ...);
+
+// training-mode routing tail (router_train.hip): arguments of one forward or backward call, branches coarse -> fine
+struct DvqRouteTrain {
+    int nb, B, C, hc, wc, groups;  // groups == 0: no normalisation
+    float eps;
+    const float *h[3], *gn_w[3], *gn_b[3];
+    const float *w1, *b1, *w2, *b2;
+    int hid, act;                  // hid == 0: single Linear (w2 = that layer)
+    const float *gumbels;          // nullptr: no-gumbel mode (gate = logits, no scale)
+    float tau;
+    float *h_out, *cmask, *gate;   // forward outputs
+    long long *indices;
+    const float *g_out, *g_gate;   // backward inputs (nullable)
+    float *dh[3], *dgn_w[3], *dgn_b[3], *dw1, *db1, *dw2, *db2;
+    void *ws;
+};

@@ -11,7 +11,9 @@ signatures, return structures and state_dict keys (`gate.*`, `feature_norm_{fine
 The entropy gate and both selects are HIP kernels (one launch each).  The feature routers' gate
 (GroupNorm -> AvgPool -> concat -> Linear[/act/Linear]) runs as the fused `dvq_router_gate_f32`
 kernel whenever no gradient is needed; with autograd recording (router
-training) the same math runs as differentiable torch ops on the GPU.
+training) the modules' forward runs the same math as differentiable torch ops on the GPU.  The training-mode
+tail as a whole -- gate, gumbel-hard select and gate_grad scale, with their backward into the branches and
+every router parameter -- is `route_train_dual` / `route_train_triple` (`dvq_route_train_*_f32`).
 """
 import json
 
@@ -433,3 +435,138 @@ class TripleGrainFeatureRouter(_GateCacheMixin, nn.Module):
         avg_h_median = self.gate_median_pool(h_median)
         h_logistic = torch.cat([h_coarse, avg_h_median, avg_h_fine], dim=1).permute(0, 2, 3, 1)
         return self.gate(h_logistic)
+
+
+
+def _router_args(router, nb):
+    """(num_groups, eps, [gn weights], [gn biases], w1, b1, w2, b2, hidden, act) of a feature router, coarse -> fine;
+    the parameter tensors themselves (autograd inputs)"""
+    names = ["feature_norm_coarse"] + (["feature_norm_median"] if nb == 3 else []) + ["feature_norm_fine"]
+    norms = [getattr(router, n) for n in names]
+    groups, eps, gw, gb = 0, 0.0, [None] * nb, [None] * nb
+    if isinstance(norms[0], nn.GroupNorm):
+        if not all(n.affine for n in norms):
+            raise _lib.DvqError("GroupNorm without affine parameters is not supported")
+        groups, eps = norms[0].num_groups, float(norms[0].eps)
+        gw, gb = [n.weight for n in norms], [n.bias for n in norms]
+    elif not all(isinstance(n, nn.Identity) for n in norms):
+        raise _lib.DvqError("router normalisation %r is not supported" % type(norms[0]).__name__)
+    if router.gate_type not in _ACT_OF_GATE:
+        raise _lib.DvqError("gate_type %r is not supported" % router.gate_type)
+    act = _ACT_OF_GATE[router.gate_type]
+    gate = router.gate
+    if act == _lib.ACT_NONE:
+        w1 = b1 = None
+        w2, b2, hidden = gate.weight, gate.bias, 0
+    else:
+        w1, b1, w2, b2 = gate[0].weight, gate[0].bias, gate[2].weight, gate[2].bias
+        hidden = w1.shape[0]
+    return groups, eps, gw, gb, w1, b1, w2, b2, hidden, act
+
+
+def _kernel_tensor(t):
+    return None if t is None else (t.detach() if (t.dtype == torch.float32 and t.is_contiguous()) else t.detach().float().contiguous())
+
+
+class _RouteTrainFn(torch.autograd.Function):
+    """`dvq_route_train_forward_f32` / `dvq_route_train_backward_f32` under autograd.  Inputs: the branches coarse -> fine
+    (h_median None for dual) and the router's parameters (GroupNorm weight / bias per branch, gate Linear weights / biases;
+    None where the router has none).  The workspace of the forward holds the saved activations and lives on the ctx until
+    the graph is freed."""
+
+    @staticmethod
+    def forward(ctx, meta, gumbels, h_coarse, h_median, h_fine, gw_c, gb_c, gw_m, gb_m, gw_f, gb_f, w1, b1, w2, b2):
+        nb, groups, eps, hidden, act, tau = meta
+        hs = [h_coarse, h_median, h_fine]
+        params = [_kernel_tensor(t) for t in (gw_c, gb_c, gw_m, gb_m, gw_f, gb_f, w1, b1, w2, b2)]
+        B, C, hc, wc = h_coarse.shape
+        S = 2 if nb == 2 else 4
+        dev = h_coarse.device
+        ws_bytes = _lib_handle.dvq_route_train_workspace_bytes(nb, B, C, hc, wc, groups, hidden)
+        if ws_bytes == 0:
+            raise _lib.DvqError("unsupported router shape: num_branches=%d C=%d hidden=%d (C %% 8 == 0, num_branches*C <= 1280)"
+                                % (nb, C, hidden))
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        h_out = torch.empty((B, C, S * hc, S * wc), dtype=torch.float32, device=dev)
+        indices = torch.empty((B, hc, wc), dtype=torch.int64, device=dev)
+        cmask = torch.empty((B, 1, S * hc, S * wc), dtype=torch.float32, device=dev)
+        gate = torch.empty((B, hc, wc, nb), dtype=torch.float32, device=dev)
+        ptr = _lib.ptr
+        args = ([nb] + [ptr(t) for t in hs] + [B, C, hc, wc, groups, eps] + [ptr(t) for t in params]
+                + [hidden, act, ptr(gumbels), tau])
+        with _lib.on_device(dev):
+            _lib.check(_lib_handle.dvq_route_train_forward_f32(
+                *args, h_out.data_ptr(), indices.data_ptr(), cmask.data_ptr(), gate.data_ptr(), ws.data_ptr(), ws_bytes,
+                _lib.stream_ptr(dev)), "dvq_route_train_forward_f32")
+        ctx.meta, ctx.args, ctx.ws, ctx.hs, ctx.params = meta, args, ws, hs, params
+        ctx.mark_non_differentiable(indices, cmask)
+        return h_out, indices, cmask, gate
+
+    @staticmethod
+    def backward(ctx, g_out, _g_ind, _g_mask, g_gate):
+        nb, groups, _eps, hidden, _act, _tau = ctx.meta
+        dev = ctx.ws.device
+        g_out = None if g_out is None else g_out.float().contiguous()
+        g_gate = None if g_gate is None else g_gate.float().contiguous()
+        dh = [None if h is None else torch.empty_like(h) for h in ctx.hs]
+        dp = [None if t is None else torch.empty_like(t) for t in ctx.params]
+        ptr = _lib.ptr
+        with _lib.on_device(dev):
+            _lib.check(_lib_handle.dvq_route_train_backward_f32(
+                *ctx.args, ptr(g_out), ptr(g_gate), ctx.ws.data_ptr(), ctx.ws.numel(), *[ptr(t) for t in dh],
+                *[ptr(t) for t in dp], _lib.stream_ptr(dev)), "dvq_route_train_backward_f32")
+        return (None, None) + tuple(dh) + tuple(dp)
+
+
+def _route_train(router, nb, branches, tau, gumbels, use_gumbel):
+    names = ("coarse", "median", "fine") if nb == 3 else ("coarse", "fine")
+    hs = [_lib.require_cuda_f32(h, "h_" + n) for h, n in zip(branches, names)]
+    B, C, hc, wc = hs[0].shape
+    for i, h in enumerate(hs):
+        sc = (1 << i) if nb == 3 else (1 + i)
+        if h.dim() != 4 or tuple(h.shape) != (B, C, hc * sc, wc * sc):
+            raise ValueError("branch %d has shape %s, expected %s" % (i, tuple(h.shape), (B, C, hc * sc, wc * sc)))
+    groups, eps, gw, gb, w1, b1, w2, b2, hidden, act = _router_args(router, nb)
+    for t in [w2] + [p for p in gw if p is not None]:
+        if not t.is_cuda or t.device != hs[0].device:
+            raise _lib.DvqError("router parameters are on %s, features on %s: the dvq kernels run on one GPU" % (t.device, hs[0].device))
+    if use_gumbel:
+        if gumbels is None:     # F.gumbel_softmax's draw: same shape, dtype, device and call order -> the same noise under one seed
+            gumbels = -torch.empty((B, hc, wc, nb), dtype=torch.float32, device=hs[0].device).exponential_().log()
+        else:
+            gumbels = _lib.require_cuda_f32(gumbels, "gumbels")
+            if tuple(gumbels.shape) != (B, hc, wc, nb):
+                raise ValueError("gumbels must be %s, got %s" % ((B, hc, wc, nb), tuple(gumbels.shape)))
+    else:
+        gumbels = None
+    if nb == 2:
+        gw = [gw[0], None, gw[1]]
+        gb = [gb[0], None, gb[1]]
+        hs = [hs[0], None, hs[1]]
+    meta = (nb, groups, eps, hidden, act, float(tau))
+    h_out, indices, cmask, gate = _RouteTrainFn.apply(meta, gumbels, hs[0], hs[1], hs[2], gw[0], gb[0], gw[1], gb[1], gw[2], gb[2],
+                                                      w1, b1, w2, b2)
+    return h_out, indices, cmask, gate.permute(0, 3, 1, 2)
+
+
+def route_train_dual(router, h_fine, h_coarse, entropy=None, tau=1.0, gumbels=None, update_router=True):
+    """DualGrainEncoder.forward's routing tail in TRAINING mode (EncoderDual.py:131-156) as one differentiable op:
+    router gate, F.gumbel_softmax(hard=True) (update_router), argmax, select, h_dual * gate_grad, codebook_mask.
+    router: a DualGrainFeatureRouter (or a module with its attribute names) -> gradients reach h_fine, h_coarse and every
+    router parameter; a DualGrainFixedEntropyRouter -> route_select_dual_entropy (int64 gate, no gumbel).
+    gumbels: [B, hc, wc, 2] noise (None: drawn as F.gumbel_softmax draws it).  update_router=False: gate = the logits,
+    no gumbel, no scale (still differentiable into the router through the returned gate).
+    -> dict(h_dual, indices, codebook_mask, gate [B, 2, hc, wc])."""
+    if isinstance(router, DualGrainFixedEntropyRouter):
+        if entropy is None:
+            raise ValueError("the fixed-entropy router needs the entropy map")
+        return route_select_dual_entropy(entropy, router.fine_grain_threshold, h_coarse, h_fine)
+    h_out, indices, cmask, gate = _route_train(router, 2, [h_coarse, h_fine], tau, gumbels, update_router)
+    return {"h_dual": h_out, "indices": indices, "codebook_mask": cmask, "gate": gate}
+
+
+def route_train_triple(router, h_fine, h_median, h_coarse, tau=1.0, gumbels=None):
+    """TripleGrainEncoder.forward's routing tail in TRAINING mode (EncoderTriple.py:145-183) as one differentiable op;
+    see route_train_dual.  -> dict(h_triple, indices, codebook_mask, gate [B, 3, hc, wc])."""
+    h_out, indices, cmask, gate = _route_train(router, 3, [h_coarse, h_median, h_fine], tau, gumbels, True)
+    return {"h_triple": h_out, "indices": indices, "codebook_mask": cmask, "gate": gate}

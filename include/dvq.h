@@ -28,6 +28,8 @@
  *     (quantize.py: _padded_width); divide the returned loss mean by D / D_padded.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.7.0  dvq_route_train_workspace_bytes, dvq_route_train_forward_f32, dvq_route_train_backward_f32 (new): the training-mode
+ *          routing tail (feature-router gate, gumbel-hard select, gate_grad scale) and its backward.  Nothing else changed.
  *   0.6.0  dvq_ema_update_f32 (new); the conv-fused assigns (dvq_vq_assign_qconv_f32, dvq_vq_assign_routed_qconv_*_f32) take h_buf = NULL: no scratch tensor
  *          (0.3 - 0.5 required a full-size one); dvq_entropy_map_f32 refuses more than 2^30 patches per call; DVQ_MODE_WS_CLEAN's
  *          contract spelled out (valid for the same entry point and shape only).  No signature changed.
@@ -427,6 +429,46 @@ DVQ_API int dvq_router_gate_f32(int num_branches, const float *h_coarse, const f
                         const float *w1, const float *b1, const float *w2, const float *b2,
                         int hidden, int activation, const void *w1_prep, float *gate, void *ws, size_t ws_bytes,
                         void *stream);
+
+/*
+ * Training-mode routing tail of the feature routers and its backward (DualGrainEncoder.forward with update_router,
+ * EncoderDual.py:131-156; TripleGrainEncoder.forward in training, EncoderTriple.py:145-183), differentiable into the branches
+ * and every router parameter.  Router arguments as dvq_router_gate_f32 (hidden = 0 and w1 = b1 = NULL with DVQ_ACT_NONE:
+ * w2 [nb, nb*C] is the single Linear); same shape limits.  Forward:
+ *   logits = gate MLP(concat(pool(GroupNorm(h_*))));  with gumbels ([B, hc, wc, nb] f32, the noise F.gumbel_softmax draws):
+ *   y = softmax((logits + gumbels) / tau), k = first max of y, gate_j = (onehot_j - y_j) + y_j (the reference's rounding:
+ *   0 off k), indices = argmax gate, h_out = select(indices) * gate_k, codebook_mask as dvq_route_select_*_f32.
+ *   gumbels == NULL (no-gumbel mode, the dual encoder with update_router=False): gate = logits, h_out = select(indices).
+ * h_out is [B, C, S hc, S wc] (S = 2 dual, 4 triple), indices [B, hc, wc], codebook_mask [B, 1, S hc, S wc], gate [B, hc, wc, nb].
+ * The workspace (dvq_route_train_workspace_bytes, 256-byte aligned) holds the saved activations: the caller keeps it unchanged
+ * from the forward to the backward of the same arguments (the backward also uses it as scratch beyond the saved part).
+ * Backward: g_out = d h_out, g_gate = d gate (either nullable = zero) -> dh_* (the branches' full gradients), the GroupNorm
+ * affine gradients dgn_* (NULL / ignored when num_groups == 0), dw1 / db1 (2-layer gates), dw2 / db2; every output overwritten.
+ * All arithmetic fp32 (matrix products on the fp32 matrix cores); every reduction over cells runs in a fixed order: the outputs are
+ * bitwise reproducible run to run.  tau > 0; S * wc <= 4096; B * C * (S hc) * (S wc) < 2^31.
+ */
+DVQ_API size_t dvq_route_train_workspace_bytes(int num_branches, int B, int C, int hc, int wc, int num_groups, int hidden);
+DVQ_API int dvq_route_train_forward_f32(int num_branches, const float *h_coarse, const float *h_median, const float *h_fine,
+                                int B, int C, int hc, int wc, int num_groups, float eps,
+                                const float *gn_w_coarse, const float *gn_b_coarse,
+                                const float *gn_w_median, const float *gn_b_median,
+                                const float *gn_w_fine, const float *gn_b_fine,
+                                const float *w1, const float *b1, const float *w2, const float *b2,
+                                int hidden, int activation, const float *gumbels, float tau,
+                                float *h_out, int64_t *indices, float *codebook_mask, float *gate,
+                                void *ws, size_t ws_bytes, void *stream);
+DVQ_API int dvq_route_train_backward_f32(int num_branches, const float *h_coarse, const float *h_median, const float *h_fine,
+                                 int B, int C, int hc, int wc, int num_groups, float eps,
+                                 const float *gn_w_coarse, const float *gn_b_coarse,
+                                 const float *gn_w_median, const float *gn_b_median,
+                                 const float *gn_w_fine, const float *gn_b_fine,
+                                 const float *w1, const float *b1, const float *w2, const float *b2,
+                                 int hidden, int activation, const float *gumbels, float tau,
+                                 const float *g_out, const float *g_gate, void *ws, size_t ws_bytes,
+                                 float *dh_coarse, float *dh_median, float *dh_fine,
+                                 float *dgn_w_coarse, float *dgn_b_coarse, float *dgn_w_median, float *dgn_b_median,
+                                 float *dgn_w_fine, float *dgn_b_fine,
+                                 float *dw1, float *db1, float *dw2, float *db2, void *stream);
 
 /*
  * Patch-entropy map, Entropy.forward (models/stage1_dynamic/dqvae_dual_entropy.py:13-63) with
