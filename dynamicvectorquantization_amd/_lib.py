@@ -27,6 +27,8 @@ MODE_WS_CLEAN = 0x100   # flag OR-ed into a filter mode: the workspace is clean 
 GATE_F32 = 0
 GATE_I64 = 1
 GATE_ENTROPY = 2        # routed assign only: entropy map + threshold
+RQ_MAX_DEPTH = 16       # DVQ_RQ_MAX_DEPTH: residual-quantization depth limit
+RQ_EMBED_SUM, RQ_EMBED_SELECT, RQ_EMBED_EACH = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
 
 EXPORTS = (
@@ -43,6 +45,8 @@ EXPORTS = (
     "dvq_entropy_gate_f32", "dvq_route_select_dual_f32", "dvq_route_select_dual_entropy_f32", "dvq_route_select_triple_f32",
     "dvq_entropy_map_f32", "dvq_ema_accumulate_nchw_f32", "dvq_restart_pick_i64", "dvq_ema_update_f32", "dvq_router_gate_workspace_bytes", "dvq_router_gate_prep_bytes", "dvq_router_gate_prepare_f32", "dvq_router_gate_prepare_norm_f32", "dvq_router_gate_f32", "dvq_permute_dual_count_i64", "dvq_permute_dual_forward_i64", "dvq_permute_dual_backward_i64",
     "dvq_route_train_workspace_bytes", "dvq_route_train_forward_f32", "dvq_route_train_backward_f32",
+    "dvq_rq_workspace_bytes", "dvq_rq_residual_offset", "dvq_rq_step_f32", "dvq_rq_loss_f32", "dvq_rq_backward_f32",
+    "dvq_rq_embed_code_f32",
 )
 
 
@@ -172,6 +176,19 @@ def _load():
     lib.dvq_route_train_forward_f32.argtypes = _rt_in + [vp, vp, vp, vp, vp, sz, vp]
     lib.dvq_route_train_backward_f32.restype = i32
     lib.dvq_route_train_backward_f32.argtypes = _rt_in + [vp, vp, vp, sz] + [vp] * 3 + [vp] * 6 + [vp] * 4 + [vp]
+    lib.dvq_rq_workspace_bytes.restype = sz
+    lib.dvq_rq_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    lib.dvq_rq_residual_offset.restype = sz
+    lib.dvq_rq_residual_offset.argtypes = [i64, i32, i32, i32]
+    lib.dvq_rq_step_f32.restype = i32
+    lib.dvq_rq_step_f32.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]
+    lib.dvq_rq_loss_f32.restype = i32
+    lib.dvq_rq_loss_f32.argtypes = [i64, i32, i32, vp, sz, vp, vp]
+    lib.dvq_rq_backward_f32.restype = i32
+    lib.dvq_rq_backward_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp]
+    lib.dvq_rq_embed_code_f32.restype = i32
+    lib.dvq_rq_embed_code_f32.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i32), i32, vp, i32, i32, i32, i32, i32, i32, i32,
+                                          i32, i32, vp, vp]
     lib.dvq_entropy_map_f32.restype = i32
     lib.dvq_entropy_map_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp]
     lib.dvq_permute_dual_count_i64.restype = i32

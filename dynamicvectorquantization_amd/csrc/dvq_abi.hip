@@ -6,7 +6,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 700   // 0.7.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 800   // 0.8.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -83,6 +83,17 @@ size_t dvq_route_train_ws_bytes(int nb, int B, int C, int hc, int wc, int groups
 int dvq_launch_route_train_fwd(const DvqRouteTrain *p, hipStream_t st);
 int dvq_launch_route_train_bwd(const DvqRouteTrain *p, hipStream_t st);
 
+int dvq_rq_blocks(long N, int D);
+void dvq_rq_layout(long N, int D, int depth, int want_grad, size_t *off_res0, size_t *off_res1, size_t *off_agg, size_t *off_s,
+                   size_t *total);
+int dvq_launch_rq_step(const float *x, const float *r_in, const float *E, int K, const long long *code, int B, int h, int w,
+                       int rH, int rW, int Dl, int i, int depth, int want_grad, long long *codes, float *out, void *ws,
+                       hipStream_t st);
+int dvq_launch_rq_loss(long N, int D, int depth, const void *ws, float *loss, hipStream_t st);
+int dvq_launch_rq_backward(const float *g_out, const float *g_loss, int B, int h, int w, int rH, int rW, int Dl, int depth,
+                           const void *ws, float *g_x, hipStream_t st);
+int dvq_launch_rq_embed(const float *const *E, const int *K, int depth, const long long *codes, int B, int h, int w, int rH, int rW,
+                        int Dl, int mode, int j, float *out, hipStream_t st);
 size_t dvq_qconv_prep_bytes_impl(int D);
 int dvq_launch_qconv_prep(const float *Wt, const float *bias, int D, void *prep, hipStream_t st);
 int dvq_launch_qconv(const float *x, const DvqRouted *rv, const void *prep, int D, int HW, long N, float *hout,
@@ -937,6 +948,101 @@ int dvq_exchange_unpack(const void *gathered, int world, int global_batch, int64
     return hip_rc(dvq_launch_xch_unpack(gathered, world, global_batch, (long)codes_per_image, (long)grain_per_image,
                                         num_codes, (long long *)codes, grain_per_image > 0 ? (long long *)grain : nullptr,
                                         mean, (hipStream_t)stream), "exchange_unpack");
+}
+
+// ---- residual quantization (rq.hip) ------------------------------------------------------------------------------------
+static bool rq_width_ok(int D) { return D > 0 && D <= 256 && D % 32 == 0; }
+
+static size_t rq_ws_bytes(long N, int D, int depth, int want_grad)
+{
+    size_t o0, o1, oa, os, tot;
+    dvq_rq_layout(N, D, depth, want_grad, &o0, &o1, &oa, &os, &tot);
+    return tot;
+}
+
+// shared checks of the step / backward / embed geometry: -> DVQ_OK or the error code (message set)
+static int rq_geom_check(const char *fn, int B, int h, int w, int rH, int rW, int Dl, int D, int depth)
+{
+    if (B <= 0 || h <= 0 || w <= 0 || rH <= 0 || rW <= 0 || Dl <= 0 || D <= 0) {
+        dvq_set_error("%s: B=%d h=%d w=%d rH=%d rW=%d Dl=%d D=%d must be positive", fn, B, h, w, rH, rW, Dl, D); return DVQ_EINVAL;
+    }
+    if (depth < 1 || depth > DVQ_RQ_MAX_DEPTH) { dvq_set_error("%s: depth=%d outside [1, %d]", fn, depth, DVQ_RQ_MAX_DEPTH); return DVQ_EINVAL; }
+    if ((long)Dl * rH * rW != D) { dvq_set_error("%s: Dl * rH * rW = %d * %d * %d != D = %d", fn, Dl, rH, rW, D); return DVQ_EINVAL; }
+    if (!rq_width_ok(D)) { dvq_set_error("%s: D=%d unsupported (a multiple of 32 up to 256: the widths the assign serves)", fn, D); return DVQ_EUNSUPPORTED; }
+    if ((long)B * h * w * D >= (1L << 31)) { dvq_set_error("%s: N * D = %ld >= 2^31", fn, (long)B * h * w * D); return DVQ_EUNSUPPORTED; }
+    return DVQ_OK;
+}
+
+size_t dvq_rq_workspace_bytes(int64_t N, int D, int depth, int want_grad)
+{
+    if (N <= 0 || !rq_width_ok(D) || N * D >= ((int64_t)1 << 31) || depth < 1 || depth > DVQ_RQ_MAX_DEPTH) return 0;
+    return rq_ws_bytes((long)N, D, depth, want_grad ? 1 : 0);
+}
+
+size_t dvq_rq_residual_offset(int64_t N, int D, int depth, int i)
+{
+    if (N <= 0 || !rq_width_ok(D) || N * D >= ((int64_t)1 << 31) || depth < 1 || depth > DVQ_RQ_MAX_DEPTH || i < 1 || i >= depth) return 0;
+    size_t o0, o1, oa, os, tot;
+    dvq_rq_layout((long)N, D, depth, 0, &o0, &o1, &oa, &os, &tot);
+    return ((i - 1) & 1) ? o1 : o0;
+}
+
+int dvq_rq_step_f32(const float *x, const float *r, const float *codebook, int K, const int64_t *code,
+                    int B, int h, int w, int rH, int rW, int Dl, int D, int i, int depth, int want_grad,
+                    int64_t *codes, float *out, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_rq_step_f32";
+    if (!x || !r || !codebook || !code || !codes || !out || !ws) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (K <= 0) { dvq_set_error("%s: K=%d must be positive", fn, K); return DVQ_EINVAL; }
+    const int rc = rq_geom_check(fn, B, h, w, rH, rW, Dl, D, depth);
+    if (rc != DVQ_OK) return rc;
+    if (i < 0 || i >= depth) { dvq_set_error("%s: i=%d outside [0, depth=%d)", fn, i, depth); return DVQ_EINVAL; }
+    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    const long N = (long)B * h * w;
+    if (ws_bytes < rq_ws_bytes(N, D, depth, want_grad ? 1 : 0)) {
+        dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, rq_ws_bytes(N, D, depth, want_grad ? 1 : 0)); return DVQ_EWORKSPACE;
+    }
+    return hip_rc(dvq_launch_rq_step(x, r, codebook, K, (const long long *)code, B, h, w, rH, rW, Dl, i, depth, want_grad ? 1 : 0,
+                                     (long long *)codes, out, ws, (hipStream_t)stream), "rq_step");
+}
+
+int dvq_rq_loss_f32(int64_t N, int D, int depth, const void *ws, size_t ws_bytes, float *loss, void *stream)
+{
+    const char *fn = "dvq_rq_loss_f32";
+    if (!ws || !loss) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (N <= 0 || depth < 1 || depth > DVQ_RQ_MAX_DEPTH) { dvq_set_error("%s: N=%lld depth=%d out of range", fn, (long long)N, depth); return DVQ_EINVAL; }
+    if (!rq_width_ok(D) || N * D >= ((int64_t)1 << 31)) { dvq_set_error("%s: D=%d unsupported", fn, D); return DVQ_EUNSUPPORTED; }
+    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (ws_bytes < rq_ws_bytes((long)N, D, depth, 0)) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, rq_ws_bytes((long)N, D, depth, 0)); return DVQ_EWORKSPACE; }
+    return hip_rc(dvq_launch_rq_loss((long)N, D, depth, ws, loss, (hipStream_t)stream), "rq_loss");
+}
+
+int dvq_rq_backward_f32(const float *g_out, const float *g_loss, int B, int h, int w, int rH, int rW, int Dl, int D,
+                        int depth, const void *ws, size_t ws_bytes, float *g_x, void *stream)
+{
+    const char *fn = "dvq_rq_backward_f32";
+    if (!ws || !g_x) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    const int rc = rq_geom_check(fn, B, h, w, rH, rW, Dl, D, depth);
+    if (rc != DVQ_OK) return rc;
+    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    const long N = (long)B * h * w;
+    if (ws_bytes < rq_ws_bytes(N, D, depth, 1)) { dvq_set_error("%s: workspace %zu < %zu bytes (the want_grad workspace of the forward)", fn, ws_bytes, rq_ws_bytes(N, D, depth, 1)); return DVQ_EWORKSPACE; }
+    return hip_rc(dvq_launch_rq_backward(g_out, g_loss, B, h, w, rH, rW, Dl, depth, ws, g_x, (hipStream_t)stream), "rq_backward");
+}
+
+int dvq_rq_embed_code_f32(const float *const *codebooks, const int *K, int depth, const int64_t *codes,
+                          int B, int h, int w, int rH, int rW, int Dl, int D, int mode, int j, float *out, void *stream)
+{
+    const char *fn = "dvq_rq_embed_code_f32";
+    if (!codebooks || !K || !codes || !out) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    const int rc = rq_geom_check(fn, B, h, w, rH, rW, Dl, D, depth);
+    if (rc != DVQ_OK) return rc;
+    for (int t = 0; t < depth; ++t)
+        if (!codebooks[t] || K[t] <= 0) { dvq_set_error("%s: codebook %d is null or K <= 0", fn, t); return DVQ_EINVAL; }
+    if (mode != DVQ_RQ_EMBED_SUM && mode != DVQ_RQ_EMBED_SELECT && mode != DVQ_RQ_EMBED_EACH) { dvq_set_error("%s: unknown mode %d", fn, mode); return DVQ_EINVAL; }
+    if (j < 0 || j >= depth) { dvq_set_error("%s: j=%d outside [0, depth=%d)", fn, j, depth); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_rq_embed(codebooks, K, depth, (const long long *)codes, B, h, w, rH, rW, Dl, mode, j, out,
+                                      (hipStream_t)stream), "rq_embed_code");
 }
 
 }  // extern "C"

@@ -28,6 +28,8 @@
  *     (quantize.py: _padded_width); divide the returned loss mean by D / D_padded.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.8.0  dvq_rq_workspace_bytes, dvq_rq_residual_offset, dvq_rq_step_f32, dvq_rq_loss_f32, dvq_rq_backward_f32,
+ *          dvq_rq_embed_code_f32 (new): residual quantization (RQBottleneck) around the flat assign.  Nothing else changed.
  *   0.7.0  dvq_route_train_workspace_bytes, dvq_route_train_forward_f32, dvq_route_train_backward_f32 (new): the training-mode
  *          routing tail (feature-router gate, gumbel-hard select, gate_grad scale) and its backward.  Nothing else changed.
  *   0.6.0  dvq_ema_update_f32 (new); the conv-fused assigns (dvq_vq_assign_qconv_f32, dvq_vq_assign_routed_qconv_*_f32) take h_buf = NULL: no scratch tensor
@@ -469,6 +471,54 @@ DVQ_API int dvq_route_train_backward_f32(int num_branches, const float *h_coarse
                                  float *dgn_w_coarse, float *dgn_b_coarse, float *dgn_w_median, float *dgn_b_median,
                                  float *dgn_w_fine, float *dgn_b_fine,
                                  float *dw1, float *db1, float *dw2, float *db2, void *stream);
+
+/*
+ * Residual quantization: RQBottleneck (modules/vector_quantization/quantize_rqvae.py:149-400) around dvq_vq_assign_flat_f32.
+ * Geometry: x is the latent [B, H, W, Dl] channel-last (RQVAE.encode, models/stage1/rqvae.py:112-115), the code grid is
+ * h x w with H = h rH, W = w rW, N = B h w tokens of D = rH rW Dl channels (to_code_shape :216-224: code element (n, j) of
+ * token n = (b, hh, ww), channel j = (a rW + c) Dl + l, is latent element (b, hh rH + a, ww rW + c, l)).  D a multiple of 32,
+ * at most 256 (the widths the assign serves, with zero padding below 256; DVQ_EUNSUPPORTED otherwise); Dl rH rW == D;
+ * N D < 2^31; 1 <= depth <= DVQ_RQ_MAX_DEPTH.  quantize :237-271 as one caller loop, i = 0 .. depth-1:
+ *   dvq_vq_assign_flat_f32(r_i, E_i, ..., zq = NULL, codes = c_i [N], loss = NULL)   (r_0 = x in code layout)
+ *   dvq_rq_step_f32(.., r_i, E_i, c_i, i, ..)
+ *   (training) the EMA update of codebook i on (r_i, c_i) -- it reads r_i, so r_{i+1} lives in the other residual slot
+ * then dvq_rq_loss_f32.  The workspace (dvq_rq_workspace_bytes(N, D, depth, want_grad), 256-byte aligned) holds the loss
+ * partials, two residual slots, agg and (want_grad) s; r_i for i >= 1 is at byte dvq_rq_residual_offset(N, D, depth, i) of it
+ * (0 = no such residual).  With rH = rW = 1, r_0 is x itself; otherwise the caller passes one code-layout copy of x.
+ * Step i, per element, in this fp32 order (e = E_i[c_i], agg_0 = +0):
+ *   agg_{i+1} = fl(agg_i + e);  r_{i+1} = fl(r_i - e) (not on the last depth);  d = fl(x - agg_{i+1});
+ *   loss partial += fl(d d) in double, summed per block in a fixed order;  want_grad: s = d (i = 0), fl(s + d) (i > 0);
+ *   codes[n, i] = c_i  (codes [N, depth] int64);  last depth: out = fl(x + fl(agg_d - x)) in latent layout (forward :273-281),
+ *   instead of agg.  A code outside [0, K) gathers NaN.
+ * dvq_rq_loss_f32: loss[0] = fl(sum_i fl32(S_i / (N D)) / depth), S_i the partials of depth i in block order
+ *   (compute_commitment_loss :283-296, mean(stack(means))).  Bitwise reproducible run to run.
+ * dvq_rq_backward_f32: g_x = fl(g_out + fl(fl(g_loss[0] fl32(2 / (N D depth))) s)) in latent layout (g_out / g_loss nullable =
+ *   zero): the straight-through identity plus d loss / d x; the codebooks are EMA buffers and get no gradient.  Needs the
+ *   want_grad workspace of the forward, unchanged since.
+ * dvq_rq_embed_code_f32: codebooks / K = HOST arrays of `depth` device pointers / row counts (the reference's embed reads the
+ *   padding row too: pass K = n_embed + 1); codes [B h w, depth] int64; j < depth; out in latent layout:
+ *   DVQ_RQ_EMBED_SUM     out = fl(...fl(fl(0 + e_0) + e_1)... + e_j)   [B, H, W, Dl]  (embed_code :298-311 for j = depth-1,
+ *                        embed_partial_code 'add' :337-369)
+ *   DVQ_RQ_EMBED_SELECT  out = e_j                                   [B, H, W, Dl]  (embed_partial_code 'select')
+ *   DVQ_RQ_EMBED_EACH    out[.., t, :] = e_t, t <= j               [B, H, W, j+1, Dl]  (embed_code_with_depth :314-334;
+ *                        rH = rW = 1, Dl = D gives its code-layout form)
+ *   a code outside [0, K_t) writes a NaN row.
+ */
+#define DVQ_RQ_MAX_DEPTH     16
+#define DVQ_RQ_EMBED_SUM      0
+#define DVQ_RQ_EMBED_SELECT   1
+#define DVQ_RQ_EMBED_EACH     2
+DVQ_API size_t dvq_rq_workspace_bytes(int64_t N, int D, int depth, int want_grad);
+DVQ_API size_t dvq_rq_residual_offset(int64_t N, int D, int depth, int i);
+DVQ_API int dvq_rq_step_f32(const float *x, const float *r, const float *codebook, int K, const int64_t *code,
+                            int B, int h, int w, int rH, int rW, int Dl, int D, int i, int depth, int want_grad,
+                            int64_t *codes, float *out, void *ws, size_t ws_bytes, void *stream);
+DVQ_API int dvq_rq_loss_f32(int64_t N, int D, int depth, const void *ws, size_t ws_bytes, float *loss, void *stream);
+DVQ_API int dvq_rq_backward_f32(const float *g_out, const float *g_loss, int B, int h, int w, int rH, int rW, int Dl, int D,
+                                int depth, const void *ws, size_t ws_bytes, float *g_x, void *stream);
+DVQ_API int dvq_rq_embed_code_f32(const float *const *codebooks, const int *K, int depth, const int64_t *codes,
+                                  int B, int h, int w, int rH, int rW, int Dl, int D, int mode, int j, float *out,
+                                  void *stream);
 
 /*
  * Patch-entropy map, Entropy.forward (models/stage1_dynamic/dqvae_dual_entropy.py:13-63) with
