@@ -30,6 +30,9 @@ GATE_ENTROPY = 2        # routed assign only: entropy map + threshold
 RQ_MAX_DEPTH = 16       # DVQ_RQ_MAX_DEPTH: residual-quantization depth limit
 RQ_EMBED_SUM, RQ_EMBED_SELECT, RQ_EMBED_EACH = 0, 1, 2
 ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
+SAMPLE_MAX_V = 8192     # the sampling head's vocabulary limit (include/dvq.h: dvq_sample_head_f32)
+TRANSFER_SAMPLED, TRANSFER_REMAIN = 0, 1
+TRANSFER_SOS_NONE, TRANSFER_SOS_CONST, TRANSFER_SOS_COPY = 0, 1, 2
 
 EXPORTS = (
     "dvq_version", "dvq_last_error_string", "dvq_codebook_prep_bytes", "dvq_codebook_prepare_f32",
@@ -47,6 +50,7 @@ EXPORTS = (
     "dvq_route_train_workspace_bytes", "dvq_route_train_forward_f32", "dvq_route_train_backward_f32",
     "dvq_rq_workspace_bytes", "dvq_rq_residual_offset", "dvq_rq_step_f32", "dvq_rq_loss_f32", "dvq_rq_backward_f32",
     "dvq_rq_embed_code_f32",
+    "dvq_sample_head_f32", "dvq_sample_transfer_count_i64", "dvq_sample_transfer_fill_i64",
 )
 
 
@@ -198,6 +202,13 @@ def _load():
                                                  vp, vp, vp, vp, vp, vp, vp]
     lib.dvq_permute_dual_backward_i64.restype = i32
     lib.dvq_permute_dual_backward_i64.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, vp, vp]
+    lib.dvq_sample_head_f32.restype = i32
+    lib.dvq_sample_head_f32.argtypes = [vp, i64, i32, i32, f32, ctypes.POINTER(i64), vp, i64, i32, vp, i32, f32, i32, vp,
+                                        vp, i64, vp, vp, vp]
+    lib.dvq_sample_transfer_count_i64.restype = i32
+    lib.dvq_sample_transfer_count_i64.argtypes = [vp, i64, i32, i32, i32, i64, i32, vp, vp, vp]
+    lib.dvq_sample_transfer_fill_i64.restype = i32
+    lib.dvq_sample_transfer_fill_i64.argtypes = [vp, i64, i32, i32, i32, i64, i32, i32, i32, i64, i64, i64, i32, vp, vp]
     return lib
 
 

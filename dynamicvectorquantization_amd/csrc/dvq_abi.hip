@@ -6,7 +6,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 800   // 0.8.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 900   // 0.9.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -63,6 +63,17 @@ int dvq_launch_permute_backward(const long long *cc, const long long *fc, const 
                                 const long long *fp, int B, int Lc, int Lf, int hc, int wc,
                                 long long cpos_eos, long long fpos_eos, long long *target, hipStream_t st);
 int dvq_permute_max_cells(void);
+int dvq_launch_sample_head(const float *logits, long long lstride, int B, int V, float temperature, const long long *rules,
+                           const long long *hist, long long hstride, int hlen, float *flag, int top_k, float top_p,
+                           int sample, const float *q, long long *tokens, long long tstride, float *out_logits,
+                           float *out_probs, hipStream_t st);
+int dvq_launch_transfer_count(const long long *cp, long long cstride, int B, int Lc, int hc, long long ceos, int remain,
+                              int *counts, int *maxes, hipStream_t st);
+int dvq_launch_transfer_fill(const long long *cp, long long cstride, int B, int Lc, int hc, long long ceos, int remain,
+                             int row_first, int sos_mode, long long sos, long long feos, long long fpad, int L, long long *out,
+                             hipStream_t st);
+int dvq_sample_max_vocab(void);
+int dvq_sample_max_cells(void);
 int dvq_launch_ema_accumulate(const float *z, const long long *codes, int D, int HW, long N, int K,
                               float *cluster_size, float *vectors_sum, hipStream_t st);
 int dvq_launch_entropy_map(const float *img, int B, int H, int W, float *out, hipStream_t st);
@@ -1043,6 +1054,72 @@ int dvq_rq_embed_code_f32(const float *const *codebooks, const int *K, int depth
     if (j < 0 || j >= depth) { dvq_set_error("%s: j=%d outside [0, depth=%d)", fn, j, depth); return DVQ_EINVAL; }
     return hip_rc(dvq_launch_rq_embed(codebooks, K, depth, (const long long *)codes, B, h, w, rH, rW, Dl, mode, j, out,
                                       (hipStream_t)stream), "rq_embed_code");
+}
+
+int dvq_sample_head_f32(const float *logits, int64_t logits_row_stride, int B, int V, float temperature, const int64_t *rules,
+                        const int64_t *history, int64_t history_row_stride, int history_len, float *flag, int top_k,
+                        float top_p, int sample, const float *q, int64_t *tokens, int64_t tokens_row_stride,
+                        float *out_logits, float *out_probs, void *stream)
+{
+    const char *fn = "dvq_sample_head_f32";
+    if (!logits || !rules || !flag || !tokens || (sample && !q) || (history_len > 0 && !history)) {
+        dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL;
+    }
+    if (B <= 0 || V <= 0) { dvq_set_error("%s: B=%d V=%d must be positive", fn, B, V); return DVQ_EINVAL; }
+    if (V > dvq_sample_max_vocab()) { dvq_set_error("%s: V=%d exceeds %d", fn, V, dvq_sample_max_vocab()); return DVQ_EUNSUPPORTED; }
+    if (!(temperature > 0.0f)) { dvq_set_error("%s: temperature must be > 0", fn); return DVQ_EINVAL; }
+    if (top_k < 0 || top_k > V) { dvq_set_error("%s: top_k=%d (0 = off, else 1..V=%d)", fn, top_k, V); return DVQ_EINVAL; }
+    if (!(top_p >= 0.0f && top_p <= 1.0f)) { dvq_set_error("%s: top_p outside (0, 1] (0 = off)", fn); return DVQ_EINVAL; }
+    if (rules[0] < 0 || rules[0] >= V) { dvq_set_error("%s: pad code %lld outside [0, V=%d)", fn, (long long)rules[0], V); return DVQ_EINVAL; }
+    for (int i = 1; i < 7; ++i) {
+        const bool range = i == 2 || i == 5;                   // ban_from codes may be V (an empty range)
+        if (rules[i] < -1 || rules[i] > (range ? V : V - 1)) {
+            dvq_set_error("%s: rule code %d = %lld outside [0, V=%d) (-1 = unused)", fn, i, (long long)rules[i], V); return DVQ_EINVAL;
+        }
+    }
+    if (logits_row_stride < V || tokens_row_stride < 1 || history_len < 0 || (history_len > 0 && history_row_stride < history_len)) {
+        dvq_set_error("%s: bad stride / history length", fn); return DVQ_EINVAL;
+    }
+    return hip_rc(dvq_launch_sample_head(logits, logits_row_stride, B, V, temperature, (const long long *)rules,
+                                         (const long long *)history, history_row_stride, history_len, flag,
+                                         top_k, top_p, sample, q, (long long *)tokens, tokens_row_stride, out_logits,
+                                         out_probs, (hipStream_t)stream), "sample_head");
+}
+
+static int transfer_args_ok(const char *fn, const int64_t *coarse_position, int64_t row_stride, int B, int Lc, int hc, int variant)
+{
+    if (!coarse_position) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (B <= 0 || Lc <= 0 || hc <= 0 || row_stride < Lc) { dvq_set_error("%s: B=%d Lc=%d hc=%d stride=%lld", fn, B, Lc, hc, (long long)row_stride); return DVQ_EINVAL; }
+    if ((long)hc * hc > dvq_sample_max_cells()) { dvq_set_error("%s: hc*hc=%ld exceeds %d coarse cells", fn, (long)hc * hc, dvq_sample_max_cells()); return DVQ_EUNSUPPORTED; }
+    if (variant != DVQ_TRANSFER_SAMPLED && variant != DVQ_TRANSFER_REMAIN) { dvq_set_error("%s: variant %d", fn, variant); return DVQ_EINVAL; }
+    return DVQ_OK;
+}
+
+int dvq_sample_transfer_count_i64(const int64_t *coarse_position, int64_t row_stride, int B, int Lc, int hc,
+                                  int64_t coarse_position_eos, int variant, int32_t *counts, int32_t *max_count, void *stream)
+{
+    const char *fn = "dvq_sample_transfer_count_i64";
+    int rc = transfer_args_ok(fn, coarse_position, row_stride, B, Lc, hc, variant);
+    if (rc) return rc;
+    if (!counts || !max_count) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_transfer_count((const long long *)coarse_position, row_stride, B, Lc, hc, coarse_position_eos,
+                                            variant, counts, max_count, (hipStream_t)stream), "transfer_count");
+}
+
+int dvq_sample_transfer_fill_i64(const int64_t *coarse_position, int64_t row_stride, int B, int Lc, int hc,
+                                 int64_t coarse_position_eos, int variant, int order, int sos_mode, int64_t sos_code,
+                                 int64_t fine_position_eos, int64_t fine_position_pad, int L, int64_t *out, void *stream)
+{
+    const char *fn = "dvq_sample_transfer_fill_i64";
+    int rc = transfer_args_ok(fn, coarse_position, row_stride, B, Lc, hc, variant);
+    if (rc) return rc;
+    if (!out) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (order != 0 && order != 1) { dvq_set_error("%s: order %d (0 region-first, 1 row-first)", fn, order); return DVQ_EINVAL; }
+    if (sos_mode < DVQ_TRANSFER_SOS_NONE || sos_mode > DVQ_TRANSFER_SOS_COPY) { dvq_set_error("%s: sos_mode %d", fn, sos_mode); return DVQ_EINVAL; }
+    if (L < 1) { dvq_set_error("%s: L=%d must be positive", fn, L); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_transfer_fill((const long long *)coarse_position, row_stride, B, Lc, hc, coarse_position_eos,
+                                           variant, order, sos_mode, sos_code, fine_position_eos, fine_position_pad, L,
+                                           (long long *)out, (hipStream_t)stream), "transfer_fill");
 }
 
 }  // extern "C"

@@ -175,3 +175,19 @@ struct DvqRouteTrain {
     float *dh[3], *dgn_w[3], *dgn_b[3], *dw1, *db1, *dw2, *db2;
     void *ws;
 };
+
+// exclusive prefix count of `flag` over the 256 threads of the block (4 waves); `total` = the block's count.
+// wave_tot: 4 ints of LDS.  Used by the stream compactions of permute.hip and sample.hip.
+__device__ __forceinline__ int block_excl_scan_256(int flag, int *wave_tot, int &total)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const unsigned long long m = __ballot(flag);
+    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_tot[wave] = __popcll(m);
+    __syncthreads();
+    int off = 0;
+    for (int w = 0; w < wave; ++w) off += wave_tot[w];
+    total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
+    __syncthreads();
+    return off + in_wave;
+}

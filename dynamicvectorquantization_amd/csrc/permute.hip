@@ -13,21 +13,6 @@
 
 constexpr int PERM_MAX_CELLS = 1024;      // coarse cells per image (reference: 16 x 16 = 256)
 
-__device__ __forceinline__ int block_excl_scan_256(int flag, int *wave_tot, int &total)
-{
-    // exclusive prefix count of `flag` over the 256 threads of the block (4 waves)
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long m = __ballot(flag);
-    const int in_wave = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_tot[wave] = __popcll(m);
-    __syncthreads();
-    int off = 0;
-    for (int w = 0; w < wave; ++w) off += wave_tot[w];
-    total = wave_tot[0] + wave_tot[1] + wave_tot[2] + wave_tot[3];
-    __syncthreads();
-    return off + in_wave;
-}
-
 // counts[b] = (#coarse cells, #fine cells); maxes = batch maxima (must be zero on entry)
 __global__ __launch_bounds__(256) void permute_count_kernel(const long long *__restrict__ grain, int ncell,
                                                             int *__restrict__ counts, int *__restrict__ maxes)

@@ -45,6 +45,16 @@ class DualGrainSeperatePermuter(nn.Module):
         self.fine_position_eos_code = fine_position_eos_code
         self.fine_position_order = fine_position_order
         assert self.fine_position_order in ["row-first", "region-first"]
+        # the reference's tensor attributes (plain CPU tensors, not buffers): Dualformer.__init__ clones
+        # fine_position_eos_tensor and position_sequence_fine, and its position transfer indexes the latter
+        self.content_eos_tensor = content_eos_code * torch.ones(1).long()
+        self.coarse_position_eos_tensor = coarse_position_eos_code * torch.ones(1).long()
+        self.fine_position_eos_tensor = fine_position_eos_code * torch.ones(1).long()
+        self.position_sequence_coarse = torch.arange(coarse_hw * coarse_hw, dtype=torch.long)
+        seq = torch.arange(fine_hw * fine_hw, dtype=torch.long).view(fine_hw, fine_hw)
+        if fine_position_order == "region-first":            # "(h1 h2) (w1 w2) -> h1 w1 (h2 w2)"
+            seq = seq.view(coarse_hw, self.hw2, coarse_hw, self.hw2).permute(0, 2, 1, 3).reshape(coarse_hw, coarse_hw, self.hw2_square)
+        self.position_sequence_fine = seq
         self._special = (ctypes.c_int64 * 6)(content_pad_code, content_eos_code, coarse_position_pad_code,
                                             coarse_position_eos_code, fine_position_pad_code, fine_position_eos_code)
 

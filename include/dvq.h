@@ -28,6 +28,9 @@
  *     (quantize.py: _padded_width); divide the returned loss mean by D / D_padded.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.9.0  dvq_sample_head_f32, dvq_sample_transfer_count_i64, dvq_sample_transfer_fill_i64 (new): the sampling step and the
+ *          coarse -> fine position transfer of stage-2 generation.  top_k = 0 and top_p = 0 switch the filter off (the reference's
+ *          None); any other k < 1 or p outside (0, 1] is DVQ_EINVAL.  Nothing else changed.
  *   0.8.0  dvq_rq_workspace_bytes, dvq_rq_residual_offset, dvq_rq_step_f32, dvq_rq_loss_f32, dvq_rq_backward_f32,
  *          dvq_rq_embed_code_f32 (new): residual quantization (RQBottleneck) around the flat assign.  Nothing else changed.
  *   0.7.0  dvq_route_train_workspace_bytes, dvq_route_train_forward_f32, dvq_route_train_backward_f32 (new): the training-mode
@@ -554,6 +557,69 @@ DVQ_API int dvq_permute_dual_backward_i64(const int64_t *coarse_content, const i
                                   int B, int Lc, int Lf, int hc, int wc,
                                   int64_t coarse_position_eos, int64_t fine_position_eos,
                                   int64_t *target, void *stream);
+
+/*
+ * Stage-2 sampling (Dualformer.sample_from_scratch, models/stage2_dynamic/dqtransformer_{class,class2_entropy,uncond_entropy}.py).
+ *
+ * dvq_sample_head_f32: ONE sampling step for all B rows -- replaces `logits[:, -1, :] / temperature`, the avoid_* helper of
+ * the step (dqtransformer_class.py:518-557), top_k_logits, F.softmax, top_p_logits (models/stage2/utils.py:22-40) and
+ * torch.multinomial / torch.topk (dqtransformer_class.py:313-330 and the three other position / content blocks).  Per row b:
+ *   1. x[j] = logits[b * logits_row_stride + j] / temperature (IEEE division), j < V <= 8192 (larger V: DVQ_EUNSUPPORTED).
+ *      Pass the last time step of a [B, T, V] tensor as logits = base + (T-1) * V, logits_row_stride = T * V.
+ *   2. the mask rule.  rules (HOST array of 7) = {pad, ban_a, ban_from, restore, ban_b, ban_from_post, flag_code}; -1 marks an
+ *      unused code; pad, ban_a, restore, ban_b, flag_code must lie in [0, V) when used, ban_from / ban_from_post in [0, V]
+ *      (DVQ_EINVAL otherwise).  If flag[b] != 0: out = -inf everywhere except out[pad] = x[pad].  Otherwise, in this order:
+ *        out = x; out[history[b, :history_len]] = -inf (codes outside [0, V) are skipped); out[pad] = out[ban_a] = -inf;
+ *        out[ban_from:] = -inf; out[restore] = x[restore]; out[ban_b] = -inf; out[ban_from_post:] = -inf.
+ *      The three reference variants (max_idx = coarse_hw^2 - 1, kept as the reference has it: position max_idx is banned):
+ *        coarse position (all)    {cpad, -1, max_idx, ceos, -1, -1, ceos}     history = the sampled coarse positions, sos included
+ *        fine position (class,    {fpad, -1, -1, feos, fsos, -1, feos}        history = the transferred fine positions + the
+ *                       uncond)                                                         sampled ones (eos and pad included)
+ *        fine position (class2)   {fpad, -1, -1, feos, -1, feos + 1, feos}
+ *        content (class, class2)  {pad, -1, eos, -1, -1, -1, -1}
+ *        content (uncond)         {pad, eos, -1, -1, sos, -1, -1}
+ *   3. top_k (0 = off, else 1..V): out[out < k-th largest] = -inf (exact radix select; ties at the threshold are all kept).
+ *   4. p = softmax(out): max, expf, ONE fixed-order sum -- deterministic, within 1e-6 of torch (reduction order differs).
+ *   5. top_p (0 = off, else (0, 1]): order the row by p descending, equal p by ASCENDING index; keep an element iff the mass
+ *      of the elements strictly before it is < top_p (the first is always kept; masses in 48-bit fixed point), zero the
+ *      rest, p = p / sum(kept).
+ *   6. the token: sample != 0: argmax_j p[j] / q[b * V + j], q = caller-drawn Exp(1) variates [B, V] (what torch.multinomial
+ *      computes from its own exponential_ draw); sample == 0: argmax_j p[j]; the first index on ties.
+ *   7. tokens[b * tokens_row_stride] = token (int64; point tokens at column t of a [B, L] sequence buffer to append);
+ *      flag[b] += (token == flag_code) when flag_code >= 0 (flag: float32 [B], the reference's [B, 1] flag tensor);
+ *      out_logits / out_probs (nullable, [B, V]) receive out after step 3 and p after step 5.
+ *   No host synchronisation, no allocation: capturable in a HIP graph.
+ *
+ * Position transfer, transfer_sampled_coarse_position_to_{sampled,remain}_fine_position (dqtransformer_class.py:464-516):
+ *   coarse_position [B, Lc] (row stride >= Lc): column 0 the sos, then sampled coarse cells up to the first coarse EOS (cells
+ *   outside [0, hc*hc) are skipped, repeats mark one cell).  variant DVQ_TRANSFER_SAMPLED marks those cells,
+ *   DVQ_TRANSFER_REMAIN the others.
+ *   count  counts[b] = marked cells of row b, *max_count = their batch maximum (one int the caller may read back:
+ *          L = (sos_mode != NONE) + 4 * max_count + 1 is the width pad_sequence gives).
+ *   fill   out [B, L]: [sos] + the fine positions of the marked cells in `order` (0 region-first: the 4 positions of each
+ *          cell together, cells row-major; 1 row-first: fine pixels row-major), as position_sequence_fine[...] lists them,
+ *          then fine_position_eos, then fine_position_pad.  sos_mode DVQ_TRANSFER_SOS_CONST writes sos_code (class, uncond),
+ *          DVQ_TRANSFER_SOS_COPY copies coarse_position[b, 0] (class2_entropy :468, :496), DVQ_TRANSFER_SOS_NONE none
+ *          (activate_sos_for_fine_sequence = False).  Entries beyond L are dropped.
+ *   hc * hc <= 1024 coarse cells of 2 x 2 fine positions each (fine_hw = 2 * coarse_hw, as the permuter; the Python
+ *   SamplingRules rejects other ratios).  Integer work: bit-exact.
+ */
+#define DVQ_TRANSFER_SAMPLED   0
+#define DVQ_TRANSFER_REMAIN    1
+#define DVQ_TRANSFER_SOS_NONE  0
+#define DVQ_TRANSFER_SOS_CONST 1
+#define DVQ_TRANSFER_SOS_COPY  2
+DVQ_API int dvq_sample_head_f32(const float *logits, int64_t logits_row_stride, int B, int V, float temperature,
+                                const int64_t *rules, const int64_t *history, int64_t history_row_stride, int history_len,
+                                float *flag, int top_k, float top_p, int sample, const float *q, int64_t *tokens,
+                                int64_t tokens_row_stride, float *out_logits, float *out_probs, void *stream);
+DVQ_API int dvq_sample_transfer_count_i64(const int64_t *coarse_position, int64_t row_stride, int B, int Lc, int hc,
+                                          int64_t coarse_position_eos, int variant, int32_t *counts, int32_t *max_count,
+                                          void *stream);
+DVQ_API int dvq_sample_transfer_fill_i64(const int64_t *coarse_position, int64_t row_stride, int B, int Lc, int hc,
+                                         int64_t coarse_position_eos, int variant, int order, int sos_mode, int64_t sos_code,
+                                         int64_t fine_position_eos, int64_t fine_position_pad, int L, int64_t *out,
+                                         void *stream);
 
 /*
  * Wire format of the image-parallel exchange (one all-gather per batch; the reference gathers nothing --
