@@ -58,7 +58,7 @@ def _can_fuse_vqgan(quantize, quant_conv, h):
     return (isinstance(quantize, VectorQuantizer2) and not quantize.training and quantize.remap is None
             and quantize.assign_mode == _lib.MODE_FILTER and quantize.e_dim == 256 and h.shape[1] == 256
             and quantize.embedding.weight.is_cuda and quantize.embedding.weight.dtype == torch.float32
-            and quant_conv.out_channels == 256 and quantize.n_e < (1 << 20) and _can_fuse_conv(quantize, quant_conv, h)
+            and _can_fuse_conv(quantize, quant_conv, h) and quant_conv.out_channels == 256 and quantize.n_e < (1 << 20)
             and not (torch.is_grad_enabled() and quantize.embedding.weight.requires_grad))
 
 

@@ -16,49 +16,31 @@ import torch
 from torch import nn
 
 from . import _lib
+from ._prepared import PreparedImage
 
 _lib_handle = _lib.lib
 
 
-class _ConvPrep:
+class _ConvPrep(PreparedImage):
     """hi / lo fp16 tile images of one conv weight, rebuilt when the weight tensor changes (storage / version)"""
-
-    def __init__(self):
-        self.key, self.buf = None, None
-        self._retired = []                   # replaced image buffers other streams may still be reading
-        self._built = None                   # (stream handle, event) of the last build: other streams wait for it once
 
     def get(self, conv):
         w = conv.weight
         bias = conv.bias
         D = w.shape[0]
         key = (w.data_ptr(), w._version, None if bias is None else (bias.data_ptr(), bias._version), D, w.device)
-        if key != self.key:
+        if key == self.key and self._built is None:      # steady state (PreparedImage.lookup's, without its frame)
+            return self.buf
+        buf = self.lookup(key, w.device)
+        if buf is None:
             nbytes = _lib_handle.dvq_qconv_prep_bytes(D)
             if nbytes == 0:
                 raise _lib.DvqError("quant_conv: unsupported channel count %d" % D)
-            # a FRESH buffer per rebuild: streams that still have kernels queued against the old images keep reading the old buffer
-            # (kept alive here until two more rebuilds have happened)
-            if self.buf is not None:
-                self._retired = (self._retired + [self.buf])[-2:]
-            self.buf = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
             w2 = _lib.require_cuda_f32(w.detach().reshape(D, D), "quant_conv.weight")
             b2 = None if bias is None else _lib.require_cuda_f32(bias.detach(), "quant_conv.bias")
-            with _lib.on_device(w.device):
-                _lib.check(_lib_handle.dvq_qconv_prepare_f32(w2.data_ptr(), _lib.ptr(b2), D, self.buf.data_ptr(),
-                                                             self.buf.numel(), _lib.stream_ptr(w.device)),
-                           "dvq_qconv_prepare_f32")
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(w.device))
-                self._built = (_lib.stream_ptr(w.device), ev)
-            self.key = key
-        elif self._built is not None and not torch.cuda.is_current_stream_capturing():
-            if self._built[0] != _lib.stream_ptr(w.device):
-                if self._built[1].query():
-                    self._built = None               # long done: nothing to order any more
-                else:
-                    torch.cuda.current_stream(w.device).wait_event(self._built[1])
-        return self.buf
+            buf = self.rebuild(key, w.device, nbytes, lambda buf, size, stream: _lib.check(_lib_handle.dvq_qconv_prepare_f32(
+                w2.data_ptr(), _lib.ptr(b2), D, buf, size, stream), "dvq_qconv_prepare_f32"))
+        return buf
 
 
 _PREPS = {}
@@ -72,7 +54,7 @@ def _prep_of(conv):
         p = (weakref.ref(conv), _ConvPrep())
         _PREPS[id(conv)] = p
     if conv.training:
-        p[1].key = None                      # optimizers may write through .data
+        p[1].invalidate()                    # optimizers may write through .data
     return p[1]
 
 
@@ -80,7 +62,7 @@ def invalidate(conv):
     """call after writing conv.weight / conv.bias through `.data` in eval mode"""
     p = _PREPS.get(id(conv))
     if p is not None:
-        p[1].key = None
+        p[1].invalidate()
 
 
 def usable(conv):

@@ -20,6 +20,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import _lib
+from ._prepared import InvalidatesPrepared, PreparedImage
 
 _lib_handle = _lib.lib
 
@@ -28,7 +29,8 @@ class _Workspace:
     """One workspace of the filter-path ops (loss partials, queue counters, record stamps, lists, records) and whether it is
     CLEAN: every filter-path op leaves it clean (its last consumer workgroup puts the live counters back to zero), so from the
     second op on the steady state passes `DVQ_MODE_WS_CLEAN` and no zeroing kernel is launched (include/dvq.h).  One workspace
-    per (stream, entry point, shape): the flag is shape-bound.
+    per (stream, workspace layout, shape): the flag is shape-bound, and the entry points that share a layout function (plain /
+    quant_conv fused / folded of the dense, the dual and the triple op) share the workspace, _CodebookPrep.workspace.
     `begin` marks it dirty until `end` has seen the call return DVQ_OK; the profiling mode MODE_FILTER_PASS1 leaves it dirty."""
     __slots__ = ("t", "clean")
 
@@ -56,7 +58,7 @@ class _Workspace:
         return self.t[sl]
 
 
-class _CodebookPrep:
+class _CodebookPrep(PreparedImage):
     """Per-codebook device buffers of the assign kernels (tile images, exact norms), rebuilt
     whenever the codebook tensor changes: the key is (storage, autograd version, shape, device),
     and `invalidate()` drops it.  Writes through `.data` do NOT bump the version counter
@@ -65,109 +67,83 @@ class _CodebookPrep:
     other `.data` writer must call `module.invalidate_codebook_cache()` itself.
 
     Workspaces (queue counters, records, loss partials) are kept PER STREAM, so two streams driving
-    the same quantizer never share a queue.  The image itself is ONE buffer: the stream that (re)builds it records an
-    event, every other stream waits for that event before its next use, and a rebuild first waits for the uses other
-    streams have queued (encode.StreamSlots with a training-mode quantizer therefore serialises on the rebuild --
-    correct, not fast; inference builds the image once)."""
+    the same quantizer never share a queue.  The image itself is ONE buffer shared by the streams as PreparedImage lays down.
+    Particular to this site: in training mode (`track_users`) the image is rebuilt at every forward, IN PLACE, and the rebuild
+    first waits for the uses other streams have queued (`used`; encode.StreamSlots with a training-mode quantizer therefore
+    serialises on the rebuild -- correct, not fast; inference builds the image once)."""
 
     def __init__(self):
-        self.key = None
-        self.buf = None
-        self._built = None       # (stream handle, event) of the last build
+        super().__init__()
         self.track_users = False # set by training-mode forwards: the image may be rebuilt while other streams read it
         self._users = {}         # stream handle -> event after that stream's last use
-        self._ws = {}            # (B, D, HW, K, mode, device, stream) -> uint8 tensor
+        self._ws = {}            # (B, D, HW, K, mode, device, stream) -> _Workspace
         self._last_ws = None
-        self._retired = []       # images replaced outside training: kept alive for readers other streams may still have queued
-        self._fold = {}          # id(conv) -> (key, buffer, (stream, event)): the conv folded into this codebook (vq_fold.hip)
+        self._fold = {}          # id(conv) -> PreparedImage: the conv folded into this codebook (vq_fold.hip)
+        self._padded = None      # (key, [K, Dp] zero-padded copy of the codebook): padded_codebook
 
     def invalidate(self):
-        self.key = None
+        super().invalidate()
         self._padded = None
 
     def get(self, codebook):
         K, D = codebook.shape
-        key = (codebook.data_ptr(), codebook._version, K, D, codebook.device)
-        if key == self.key:
-            # steady state: no Stream object is made (torch.cuda.current_stream() alone is ~5 us of every call)
-            b = self._built
-            if b is None:
-                return self.buf
-            if b[0] == _lib.stream_ptr(codebook.device):     # built on this stream: ordered; forget the event once it has completed
-                if not torch.cuda.is_current_stream_capturing() and b[1].query():
-                    self._built = None
-                return self.buf
-        cur = torch.cuda.current_stream(codebook.device)
-        if key != self.key:
-            nbytes = _lib_handle.dvq_codebook_prep_bytes(K, D)
-            if nbytes == 0:
-                raise _lib.DvqError("unsupported codebook shape K=%d D=%d" % (K, D))
-            if self.buf is None or self.buf.numel() < nbytes or self.buf.device != codebook.device or not self.track_users:
-                # outside training (load_state_dict, invalidate, .to()) no use events exist: the new image goes to a FRESH
-                # buffer and the old one is kept for whatever other streams still have queued against it
-                if self.buf is not None:
-                    self._retired = (self._retired + [self.buf])[-4:]
-                self.buf = torch.empty(nbytes, dtype=torch.uint8, device=codebook.device)
-            for h, ev in self._users.items():        # other streams may still be reading the old image
-                if h != cur.cuda_stream:
-                    cur.wait_event(ev)
-            self._users.clear()
-            self._retired = (self._retired + [ent[1] for ent in self._fold.values()])[-4:]
-            self._fold.clear()
-            _lib.check(_lib_handle.dvq_codebook_prepare_f32(
-                codebook.data_ptr(), K, D, self.buf.data_ptr(), self.buf.numel(),
-                cur.cuda_stream), "dvq_codebook_prepare_f32")
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            self._built = (cur.cuda_stream, ev)
-            self.key = key
-        elif self._built is not None and self._built[0] != cur.cuda_stream and not torch.cuda.is_current_stream_capturing():
-            # (a capture is always preceded by uncaptured warm-up calls on the capturing stream: ordered there)
-            if self._built[1].query():
-                self._built = None               # long done: nothing to order any more
-            else:
-                cur.wait_event(self._built[1])
-        return self.buf
+        dev = codebook.device
+        key = (codebook.data_ptr(), codebook._version, K, D, dev)
+        if key == self.key and self._built is None:  # steady state (PreparedImage.lookup's, without its frame)
+            return self.buf
+        buf = self.lookup(key, dev)
+        if buf is not None:
+            return buf
+        nbytes = _lib_handle.dvq_codebook_prep_bytes(K, D)
+        if nbytes == 0:
+            raise _lib.DvqError("unsupported codebook shape K=%d D=%d" % (K, D))
+        cur = torch.cuda.current_stream(dev)
+        for h, ev in self._users.items():            # training: other streams may still be reading the image rebuilt in place
+            if h != cur.cuda_stream:
+                cur.wait_event(ev)
+        self._users.clear()
+        self._drop_folds()                           # the fold images derive from this one: retired with it
+        # outside training (load_state_dict, invalidate, .to()) no use events exist: the new image goes to a fresh buffer
+        return self.rebuild(key, dev, nbytes, lambda buf, size, stream: _lib.check(_lib_handle.dvq_codebook_prepare_f32(
+            codebook.data_ptr(), K, D, buf, size, stream), "dvq_codebook_prepare_f32"), in_place=self.track_users)
+
+    def _drop_folds(self):
+        """forget the fold images; their buffers, and the ones they had retired themselves, stay alive in this image's list"""
+        for f in self._fold.values():
+            self.adopt(f)
+        self._fold.clear()
 
     def fold(self, codebook, conv):
         """the image of `codebook` with the 1x1 `conv` folded in (dvq_fold_prepare_f32: E W, seeds, bound constants), built once
         per (codebook, conv weight) pair; rebuilt into a fresh buffer when either changes.  Inference only."""
-        from . import qconv as _qconv
         pbuf = self.get(codebook)
         w, bias = conv.weight, conv.bias
         K, D = codebook.shape
         key = (self.key, w.data_ptr(), w._version, None if bias is None else (bias.data_ptr(), bias._version))
-        cur = torch.cuda.current_stream(codebook.device)
-        ent = self._fold.get(id(conv))
-        if ent is None or ent[0] != key or conv.training:
+        img = self._fold.get(id(conv))
+        if img is None:
+            if len(self._fold) >= 4:
+                self._drop_folds()
+            img = self._fold[id(conv)] = PreparedImage()
+        if conv.training:
+            img.invalidate()                             # optimizers may write through .data
+        fbuf = img.buf if (key == img.key and img._built is None) else img.lookup(key, codebook.device)
+        if fbuf is None:
             nbytes = _lib_handle.dvq_fold_prep_bytes(K, D)
             if nbytes == 0:
                 raise _lib.DvqError("fold: unsupported codebook shape K=%d D=%d" % (K, D))
-            if ent is not None:
-                self._retired = (self._retired + [ent[1]])[-4:]
-            if len(self._fold) >= 4:
-                self._fold.clear()
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=codebook.device)
             w2 = _lib.require_cuda_f32(w.detach().reshape(D, D), "quant_conv.weight")
             b2 = None if bias is None else _lib.require_cuda_f32(bias.detach(), "quant_conv.bias")
-            _lib.check(_lib_handle.dvq_fold_prepare_f32(codebook.data_ptr(), K, D, pbuf.data_ptr(), w2.data_ptr(), _lib.ptr(b2),
-                                                        buf.data_ptr(), buf.numel(), cur.cuda_stream), "dvq_fold_prepare_f32")
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            ent = (key, buf, [cur.cuda_stream, ev])
-            self._fold[id(conv)] = ent
-        elif ent[2] is not None and ent[2][0] != cur.cuda_stream and not torch.cuda.is_current_stream_capturing():
-            if ent[2][1].query():
-                self._fold[id(conv)] = (ent[0], ent[1], None)
-            else:
-                cur.wait_event(ent[2][1])
-        return pbuf, ent[1]
+            fbuf = img.rebuild(key, codebook.device, nbytes, lambda buf, size, stream: _lib.check(
+                _lib_handle.dvq_fold_prepare_f32(codebook.data_ptr(), K, D, pbuf.data_ptr(), w2.data_ptr(), _lib.ptr(b2),
+                                                 buf, size, stream), "dvq_fold_prepare_f32"))
+        return pbuf, fbuf
 
     def padded_codebook(self, codebook, Dp):
         """[K, Dp] copy of `codebook` with zero channels appended (widths served by padding, _padded_width), rebuilt when the
         codebook tensor changes; `get()` then prepares THAT tensor"""
         key = (codebook.data_ptr(), codebook._version, tuple(codebook.shape), Dp)
-        ent = getattr(self, "_padded", None)
+        ent = self._padded
         if ent is None or ent[0] != key:
             Ep = codebook.new_zeros((codebook.shape[0], Dp))
             Ep[:, :codebook.shape[1]] = codebook.detach()
@@ -414,6 +390,100 @@ def _routed_outputs(h_fine, B, hc, wc, S, want_zq, want_loss, with_gate):
     return zq, codes, loss, indices, cmask, gate_out
 
 
+def _vq_assign_routed(nb, h_coarse, h_median, h_fine, codebook, prep, gate, entropy, threshold, beta, want_zq, want_loss, mode, out,
+                      conv, h_buf, fold):
+    """vq_assign_routed_dual (nb = 2, no h_median) / vq_assign_routed_triple (nb = 3).  The entry points of the two differ in the
+    branch pointers and, dual only, the entropy threshold after the gate kind and `gate_out` after the codebook mask."""
+    h_coarse = _lib.require_cuda_f32(h_coarse, "h_coarse")
+    dual = nb == 2
+    if not dual:
+        h_median = _lib.require_cuda_f32(h_median, "h_median")
+    h_fine = _lib.require_cuda_f32(h_fine, "h_fine")
+    codebook = _lib.require_cuda_f32(codebook, "codebook")
+    B, D, hc, wc = h_coarse.shape
+    K, Dc = codebook.shape
+    S = 2 if dual else 4
+    if h_fine.shape != (B, D, S * hc, S * wc) or Dc != D or not (dual or h_median.shape == (B, D, 2 * hc, 2 * wc)):
+        raise ValueError("shape mismatch: h_coarse %s %sh_fine %s codebook %s" %
+                         (tuple(h_coarse.shape), "" if dual else "h_median %s " % (tuple(h_median.shape),), tuple(h_fine.shape),
+                          tuple(codebook.shape)))
+    if dual and (gate is None) == (entropy is None):
+        raise ValueError("give exactly one of gate / entropy")
+    if entropy is not None:
+        g = _lib.require_cuda_f32(entropy, "entropy")
+        if g.shape != (B, hc, wc) or threshold is None:
+            raise ValueError("entropy must be [B, hc, wc] and come with a threshold")
+        kind, thr = _lib.GATE_ENTROPY, float(threshold)
+    else:
+        g, kind = _gate_for_routed(gate, nb)
+        if g.shape[:3] != (B, hc, wc):
+            raise ValueError("gate %s does not match h_coarse %s" % (tuple(gate.shape), tuple(h_coarse.shape)))
+        thr = 0.0
+    gate_out = None
+    if out is None:
+        zq, codes, loss, indices, cmask, gate_out = _routed_outputs(h_fine, B, hc, wc, S, want_zq, want_loss,
+                                                                    entropy is not None)
+    elif dual:
+        zq, codes, loss, indices, cmask, gate_out = out
+    else:
+        zq, codes, loss, indices, cmask = out
+    res = {"zq": zq, "codes": codes, "loss": loss, "indices": indices, "codebook_mask": cmask,
+           "gate": gate_out if entropy is not None else gate}
+    if B * hc * wc == 0:
+        if loss is not None:
+            loss.fill_(float("nan"))
+        return res
+    dev = h_fine.device
+    zq_p = 0 if zq is None else zq.data_ptr()                    # the nullable outputs, once for the six calls below
+    loss_p = 0 if loss is None else loss.data_ptr()
+    ws = prep.workspace(B, D, ("routed2" if dual else "routed3", hc, wc), K, mode, dev)
+    with _lib.on_device(dev):
+        if fold:                                 # the conv folded into the codebook (see vq_assign): codes [+ z_q], no loss
+            qbuf, pbuf, fbuf = _fold_args(conv, prep, codebook, loss is not None, mode)
+            if dual:
+                ws.check(mode, _lib_handle.dvq_vq_assign_routed_fold_dual_f32(
+                    g.data_ptr(), kind, thr, h_coarse.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(), fbuf.data_ptr(),
+                    codebook.data_ptr(), pbuf.data_ptr(), B, D, hc, wc, K, zq_p, codes.data_ptr(), indices.data_ptr(),
+                    cmask.data_ptr(), _lib.ptr(gate_out), *ws.begin(mode), _lib.stream_ptr(dev)),
+                    "dvq_vq_assign_routed_fold_dual_f32")
+            else:
+                ws.check(mode, _lib_handle.dvq_vq_assign_routed_fold_triple_f32(
+                    g.data_ptr(), kind, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(),
+                    fbuf.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(), B, D, hc, wc, K, zq_p, codes.data_ptr(),
+                    indices.data_ptr(), cmask.data_ptr(), *ws.begin(mode), _lib.stream_ptr(dev)),
+                    "dvq_vq_assign_routed_fold_triple_f32")
+        elif conv is not None:
+            qbuf, hb, h_all = _conv_args(conv, prep, h_fine.shape, dev, h_buf)
+            pbuf = prep.get(codebook)
+            if dual:
+                ws.check(mode, _lib_handle.dvq_vq_assign_routed_qconv_dual_f32(
+                    g.data_ptr(), kind, thr, h_coarse.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(), codebook.data_ptr(),
+                    pbuf.data_ptr(), B, D, hc, wc, K, float(beta), zq_p, codes.data_ptr(), loss_p,
+                    indices.data_ptr(), cmask.data_ptr(), _lib.ptr(gate_out), _lib.ptr(hb), int(h_all), *ws.begin(mode),
+                    _lib.stream_ptr(dev)), "dvq_vq_assign_routed_qconv_dual_f32")
+            else:
+                ws.check(mode, _lib_handle.dvq_vq_assign_routed_qconv_triple_f32(
+                    g.data_ptr(), kind, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(),
+                    codebook.data_ptr(), pbuf.data_ptr(), B, D, hc, wc, K, float(beta), zq_p, codes.data_ptr(),
+                    loss_p, indices.data_ptr(), cmask.data_ptr(), _lib.ptr(hb), int(h_all), *ws.begin(mode),
+                    _lib.stream_ptr(dev)), "dvq_vq_assign_routed_qconv_triple_f32")
+        else:
+            pbuf = prep.get(codebook)
+            if dual:
+                ws.check(mode, _lib_handle.dvq_vq_assign_routed_dual_f32(
+                    g.data_ptr(), kind, thr, h_coarse.data_ptr(), h_fine.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(),
+                    B, D, hc, wc, K, float(beta), zq_p, codes.data_ptr(), loss_p, indices.data_ptr(),
+                    cmask.data_ptr(), _lib.ptr(gate_out), *ws.begin(mode), _lib.stream_ptr(dev)),
+                    "dvq_vq_assign_routed_dual_f32")
+            else:
+                ws.check(mode, _lib_handle.dvq_vq_assign_routed_triple_f32(
+                    g.data_ptr(), kind, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), codebook.data_ptr(),
+                    pbuf.data_ptr(), B, D, hc, wc, K, float(beta), zq_p, codes.data_ptr(), loss_p,
+                    indices.data_ptr(), cmask.data_ptr(), *ws.begin(mode), _lib.stream_ptr(dev)),
+                    "dvq_vq_assign_routed_triple_f32")
+    return res
+
+
 def vq_assign_routed_dual(h_coarse, h_fine, codebook, prep, gate=None, entropy=None, threshold=None, beta=0.25,
                           want_zq=True, want_loss=True, mode=_lib.MODE_FILTER, out=None, conv=None, h_buf=None, fold=False):
     """Routing tail of DualGrainEncoder (EncoderDual.py:134-149) + VectorQuantize2.forward
@@ -425,65 +495,8 @@ def vq_assign_routed_dual(h_coarse, h_fine, codebook, prep, gate=None, entropy=N
     `out` = (zq, codes, loss, indices, codebook_mask, gate_out) preallocated (benchmark / graph capture).
     conv: the model's 1x1 quant_conv between select and quantizer, fused in (`dvq_vq_assign_routed_qconv_dual_f32`): the
     order every reference checkpoint runs (dqvae_dual_entropy.py:124-134), one kernel chain, h never written."""
-    h_coarse = _lib.require_cuda_f32(h_coarse, "h_coarse")
-    h_fine = _lib.require_cuda_f32(h_fine, "h_fine")
-    codebook = _lib.require_cuda_f32(codebook, "codebook")
-    B, D, hc, wc = h_coarse.shape
-    K = codebook.shape[0]
-    if tuple(h_fine.shape) != (B, D, 2 * hc, 2 * wc) or codebook.shape[1] != D:
-        raise ValueError("shape mismatch: h_coarse %s h_fine %s codebook %s" %
-                         (tuple(h_coarse.shape), tuple(h_fine.shape), tuple(codebook.shape)))
-    if (gate is None) == (entropy is None):
-        raise ValueError("give exactly one of gate / entropy")
-    if entropy is not None:
-        g = _lib.require_cuda_f32(entropy, "entropy")
-        if tuple(g.shape) != (B, hc, wc) or threshold is None:
-            raise ValueError("entropy must be [B, hc, wc] and come with a threshold")
-        kind, thr = _lib.GATE_ENTROPY, float(threshold)
-    else:
-        g, kind = _gate_for_routed(gate, 2)
-        if tuple(g.shape[:3]) != (B, hc, wc):
-            raise ValueError("gate %s does not match h_coarse %s" % (tuple(gate.shape), tuple(h_coarse.shape)))
-        thr = 0.0
-    if out is not None:
-        zq, codes, loss, indices, cmask, gate_out = out
-    else:
-        zq, codes, loss, indices, cmask, gate_out = _routed_outputs(h_fine, B, hc, wc, 2, want_zq, want_loss,
-                                                                    entropy is not None)
-    res = {"zq": zq, "codes": codes, "loss": loss, "indices": indices, "codebook_mask": cmask,
-           "gate": gate_out if entropy is not None else gate}
-    if B * hc * wc == 0:
-        if loss is not None:
-            loss.fill_(float("nan"))
-        return res
-    ws = prep.workspace(B, D, ("routed2", hc, wc), K, mode, h_fine.device)
-    if fold:                                     # the conv folded into the codebook (see vq_assign): codes [+ z_q], no loss
-        with _lib.on_device(h_fine.device):
-            qbuf, pbuf, fbuf = _fold_args(conv, prep, codebook, loss is not None, mode)
-            ws.check(mode, _lib_handle.dvq_vq_assign_routed_fold_dual_f32(
-                g.data_ptr(), kind, thr, h_coarse.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(), fbuf.data_ptr(),
-                codebook.data_ptr(), pbuf.data_ptr(), B, D, hc, wc, K, _lib.ptr(zq), codes.data_ptr(), indices.data_ptr(),
-                cmask.data_ptr(), _lib.ptr(gate_out), *ws.begin(mode), _lib.stream_ptr(h_fine.device)),
-                "dvq_vq_assign_routed_fold_dual_f32")
-        return res
-    if conv is not None:
-        with _lib.on_device(h_fine.device):
-            qbuf, hb, h_all = _conv_args(conv, prep, h_fine.shape, h_fine.device, h_buf)
-            pbuf = prep.get(codebook)
-            ws.check(mode, _lib_handle.dvq_vq_assign_routed_qconv_dual_f32(
-                g.data_ptr(), kind, thr, h_coarse.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(), codebook.data_ptr(),
-                pbuf.data_ptr(), B, D, hc, wc, K, float(beta), _lib.ptr(zq), codes.data_ptr(), _lib.ptr(loss),
-                indices.data_ptr(), cmask.data_ptr(), _lib.ptr(gate_out), _lib.ptr(hb), int(h_all), *ws.begin(mode),
-                _lib.stream_ptr(h_fine.device)), "dvq_vq_assign_routed_qconv_dual_f32")
-        return res
-    with _lib.on_device(h_fine.device):
-        pbuf = prep.get(codebook)
-        ws.check(mode, _lib_handle.dvq_vq_assign_routed_dual_f32(
-            g.data_ptr(), kind, thr, h_coarse.data_ptr(), h_fine.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(),
-            B, D, hc, wc, K, float(beta), _lib.ptr(zq), codes.data_ptr(), _lib.ptr(loss), indices.data_ptr(),
-            cmask.data_ptr(), _lib.ptr(gate_out), *ws.begin(mode), _lib.stream_ptr(h_fine.device)),
-            "dvq_vq_assign_routed_dual_f32")
-    return res
+    return _vq_assign_routed(2, h_coarse, None, h_fine, codebook, prep, gate, entropy, threshold, beta, want_zq, want_loss, mode, out,
+                             conv, h_buf, fold)
 
 
 def vq_assign_routed_triple(h_coarse, h_median, h_fine, codebook, prep, gate, beta=0.25, want_zq=True,
@@ -492,56 +505,8 @@ def vq_assign_routed_triple(h_coarse, h_median, h_fine, codebook, prep, gate, be
     unique tokens (`dvq_vq_assign_routed_triple_f32`): h_coarse [B, D, hc, wc], h_median [B, D, 2hc, 2wc],
     h_fine [B, D, 4hc, 4wc], gate [B, hc, wc, 3].  -> dict as vq_assign_routed_dual.
     `out` = (zq, codes, loss, indices, codebook_mask)."""
-    h_coarse = _lib.require_cuda_f32(h_coarse, "h_coarse")
-    h_median = _lib.require_cuda_f32(h_median, "h_median")
-    h_fine = _lib.require_cuda_f32(h_fine, "h_fine")
-    codebook = _lib.require_cuda_f32(codebook, "codebook")
-    B, D, hc, wc = h_coarse.shape
-    K = codebook.shape[0]
-    if (tuple(h_median.shape) != (B, D, 2 * hc, 2 * wc) or tuple(h_fine.shape) != (B, D, 4 * hc, 4 * wc)
-            or codebook.shape[1] != D):
-        raise ValueError("shape mismatch: h_coarse %s h_median %s h_fine %s codebook %s" %
-                         (tuple(h_coarse.shape), tuple(h_median.shape), tuple(h_fine.shape), tuple(codebook.shape)))
-    g, kind = _gate_for_routed(gate, 3)
-    if tuple(g.shape[:3]) != (B, hc, wc):
-        raise ValueError("gate %s does not match h_coarse %s" % (tuple(gate.shape), tuple(h_coarse.shape)))
-    if out is not None:
-        zq, codes, loss, indices, cmask = out
-    else:
-        zq, codes, loss, indices, cmask, _ = _routed_outputs(h_fine, B, hc, wc, 4, want_zq, want_loss, False)
-    res = {"zq": zq, "codes": codes, "loss": loss, "indices": indices, "codebook_mask": cmask, "gate": gate}
-    if B * hc * wc == 0:
-        if loss is not None:
-            loss.fill_(float("nan"))
-        return res
-    ws = prep.workspace(B, D, ("routed3", hc, wc), K, mode, h_fine.device)
-    if fold:
-        with _lib.on_device(h_fine.device):
-            qbuf, pbuf, fbuf = _fold_args(conv, prep, codebook, loss is not None, mode)
-            ws.check(mode, _lib_handle.dvq_vq_assign_routed_fold_triple_f32(
-                g.data_ptr(), kind, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(),
-                fbuf.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(), B, D, hc, wc, K, _lib.ptr(zq), codes.data_ptr(),
-                indices.data_ptr(), cmask.data_ptr(), *ws.begin(mode), _lib.stream_ptr(h_fine.device)),
-                "dvq_vq_assign_routed_fold_triple_f32")
-        return res
-    if conv is not None:
-        with _lib.on_device(h_fine.device):
-            qbuf, hb, h_all = _conv_args(conv, prep, h_fine.shape, h_fine.device, h_buf)
-            pbuf = prep.get(codebook)
-            ws.check(mode, _lib_handle.dvq_vq_assign_routed_qconv_triple_f32(
-                g.data_ptr(), kind, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(),
-                codebook.data_ptr(), pbuf.data_ptr(), B, D, hc, wc, K, float(beta), _lib.ptr(zq), codes.data_ptr(),
-                _lib.ptr(loss), indices.data_ptr(), cmask.data_ptr(), _lib.ptr(hb), int(h_all), *ws.begin(mode),
-                _lib.stream_ptr(h_fine.device)), "dvq_vq_assign_routed_qconv_triple_f32")
-        return res
-    with _lib.on_device(h_fine.device):
-        pbuf = prep.get(codebook)
-        ws.check(mode, _lib_handle.dvq_vq_assign_routed_triple_f32(
-            g.data_ptr(), kind, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), codebook.data_ptr(),
-            pbuf.data_ptr(), B, D, hc, wc, K, float(beta), _lib.ptr(zq), codes.data_ptr(), _lib.ptr(loss),
-            indices.data_ptr(), cmask.data_ptr(), *ws.begin(mode), _lib.stream_ptr(h_fine.device)),
-            "dvq_vq_assign_routed_triple_f32")
-    return res
+    return _vq_assign_routed(3, h_coarse, h_median, h_fine, codebook, prep, gate, None, None, beta, want_zq, want_loss, mode, out,
+                             conv, h_buf, fold)
 
 
 def embed_gather(codebook, idx):
@@ -654,9 +619,10 @@ def _vq_straight_through(z, weight, mask, prep, K, coef_z, coef_e, mode):
     return zq, loss[1], codes
 
 
-class VQEmbedding(nn.Embedding):
+class VQEmbedding(InvalidatesPrepared, nn.Embedding):
     """EMA codebook; same parameters/buffers as the reference class (quantize2_mask.py:10-132):
     weight [K+1, D] (row K is the padding row), cluster_size_ema [K], embed_ema [K, D]."""
+    _prepared = ("_prep",)
 
     def __init__(self, n_embed, embed_dim, ema=True, decay=0.99, restart_unused_codes=True, eps=1e-5):
         super().__init__(n_embed + 1, embed_dim, padding_idx=n_embed)
@@ -679,15 +645,6 @@ class VQEmbedding(nn.Embedding):
     def invalidate_codebook_cache(self):
         """call after writing the codebook through `.data` (which does not bump the version counter)"""
         self._prep.invalidate()
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        super()._load_from_state_dict(*args, **kwargs)
-        self._prep.invalidate()
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._prep.invalidate()
-        return out
 
     @torch.no_grad()
     def compute_distances(self, inputs):
@@ -988,9 +945,10 @@ class VectorQuantize2List(_CodebookOps, nn.Module):
 
 
 
-class VectorQuantizer2(nn.Module):
+class VectorQuantizer2(InvalidatesPrepared, nn.Module):
     """Reference modules/vector_quantization/quantize_vqgan.py:213-341 (taming-style quantizer,
     used by the fixed-granularity VQModel with beta=0.25, remap=None, legacy=False)."""
+    _prepared = ("_prep",)
 
     def __init__(self, n_e, e_dim, beta, remap=None, unknown_index="random", sane_index_shape=False,
                  legacy=True):
@@ -1019,15 +977,6 @@ class VectorQuantizer2(nn.Module):
     def invalidate_codebook_cache(self):
         """call after writing embedding.weight through `.data` in eval mode"""
         self._prep.invalidate()
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        super()._load_from_state_dict(*args, **kwargs)
-        self._prep.invalidate()
-
-    def _apply(self, fn, *args, **kwargs):
-        out = super()._apply(fn, *args, **kwargs)
-        self._prep.invalidate()
-        return out
 
     def remap_to_used(self, inds):
         """full-codebook indices [B, ...] -> positions in the `used` list (first occurrence); indices that

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import _lib
+from ._prepared import InvalidatesPrepared, PreparedImage
 
 _lib_handle = _lib.lib
 
@@ -233,65 +234,42 @@ def _needs_autograd(module, *tensors):
     return any(t.requires_grad for t in tensors) or any(p.requires_grad for p in module.parameters())
 
 
-class _GateWeightPrep:
+class _GateWeightPrep(PreparedImage):
     """The hidden-layer weight of a router's gate MLP as split fp16 matrix-core tile images
     (`dvq_router_gate_prepare_f32`), rebuilt only when the weight changes: keyed on (data_ptr, _version, shape,
     device) like quantize._CodebookPrep, with the same caveat -- writes through `.data` do not bump the version, so
     the router modules call invalidate() from `_load_from_state_dict`, `_apply` and every training-mode forward."""
 
-    def __init__(self):
-        self.key = None
-        self.buf = None
-        self._retired = []
-        self._built = None                   # (stream handle, event) of the last build: other streams wait for it once
-
-    def invalidate(self):
-        self.key = None
-
     def get(self, w1, nb, C, gn=None, owners=None):
         """gn: (weights, biases) of the branches' GroupNorms, coarse -> fine (None: no normalisation): their per-branch maxima
-        are prepared into the same buffer (`dvq_router_gate_prepare_norm_f32`) and refreshed when a parameter's version changes.
+        are prepared into the same buffer (`dvq_router_gate_prepare_norm_f32`); a changed GroupNorm parameter is part of the
+        key, so it rebuilds the whole prep (simplest).
         owners: the module PARAMETERS the tensors were derived from (w1's, then the GroupNorms'): the cache is keyed on THEIR
         (data_ptr, _version, dtype) -- a converted copy (non-fp32 or non-contiguous parameters) is a fresh temporary on every
         call, whose address and version say nothing"""
         hidden = w1.shape[0]
         ow = owners if owners is not None else [w1] + (list(gn[0] + gn[1]) if gn is not None else [])
-        key = (ow[0].data_ptr(), ow[0]._version, ow[0].dtype, tuple(w1.shape), w1.device)
-        gkey = None if gn is None else tuple((t.data_ptr(), t._version, t.dtype) for t in ow[1:])
-        if key == self.key and gkey != getattr(self, "gkey", None):
-            self.key = None                              # (simplest: a changed GroupNorm parameter rebuilds the whole prep)
-        if key != self.key:
+        key = (ow[0].data_ptr(), ow[0]._version, ow[0].dtype, tuple(w1.shape), w1.device,
+               None if gn is None else tuple((t.data_ptr(), t._version, t.dtype) for t in ow[1:]))
+        if key == self.key and self._built is None:      # steady state (PreparedImage.lookup's, without its frame)
+            return self.buf
+        buf = self.lookup(key, w1.device)
+        if buf is None:
             nbytes = _lib_handle.dvq_router_gate_prep_bytes(nb, C, hidden)
             if nbytes == 0:
                 raise _lib.DvqError("unsupported gate shape nb=%d C=%d hidden=%d" % (nb, C, hidden))
-            # a FRESH buffer per rebuild (other streams may still have kernels queued against the old images; the last two
-            # replaced buffers are kept alive)
-            if self.buf is not None:
-                self._retired = (self._retired + [self.buf])[-2:]
-            self.buf = torch.empty(nbytes, dtype=torch.uint8, device=w1.device)
-            with _lib.on_device(w1.device):
-                _lib.check(_lib_handle.dvq_router_gate_prepare_f32(
-                    w1.data_ptr(), nb, C, hidden, self.buf.data_ptr(), self.buf.numel(), _lib.stream_ptr(w1.device)),
-                    "dvq_router_gate_prepare_f32")
+
+            def prepare(buf, size, stream):
+                _lib.check(_lib_handle.dvq_router_gate_prepare_f32(w1.data_ptr(), nb, C, hidden, buf, size, stream),
+                           "dvq_router_gate_prepare_f32")
                 if gn is not None:
                     gw, gb = gn
                     p = lambda t: t.data_ptr()
                     _lib.check(_lib_handle.dvq_router_gate_prepare_norm_f32(
                         nb, C, hidden, p(gw[0]), p(gb[0]), p(gw[1]) if nb == 3 else None, p(gb[1]) if nb == 3 else None,
-                        p(gw[-1]), p(gb[-1]), self.buf.data_ptr(), self.buf.numel(), _lib.stream_ptr(w1.device)),
-                        "dvq_router_gate_prepare_norm_f32")
-                ev = torch.cuda.Event()
-                ev.record(torch.cuda.current_stream(w1.device))
-                self._built = (_lib.stream_ptr(w1.device), ev)
-            self.key = key
-            self.gkey = gkey
-        elif self._built is not None and not torch.cuda.is_current_stream_capturing():
-            if self._built[0] != _lib.stream_ptr(w1.device):     # built on another stream: order this one behind it, once
-                if self._built[1].query():
-                    self._built = None
-                else:
-                    torch.cuda.current_stream(w1.device).wait_event(self._built[1])
-        return self.buf
+                        p(gw[-1]), p(gb[-1]), buf, size, stream), "dvq_router_gate_prepare_norm_f32")
+            buf = self.rebuild(key, w1.device, nbytes, prepare)
+        return buf
 
 
 def fused_router_gate(gate, gate_type, norms, branches, weight_prep=None):
@@ -342,8 +320,9 @@ def fused_router_gate(gate, gate_type, norms, branches, weight_prep=None):
     return out
 
 
-class _GateCacheMixin:
-    """invalidation hooks of the cached gate-weight images (see _GateWeightPrep)"""
+class _GateCacheMixin(InvalidatesPrepared):
+    """the cached gate-weight images of a feature router (see _GateWeightPrep) and their invalidation hooks"""
+    _prepared = ("_gate_weight_prep",)
 
     def _gate_prep(self):
         if self.training:
@@ -352,14 +331,6 @@ class _GateCacheMixin:
 
     def invalidate_gate_cache(self):
         self._gate_weight_prep.invalidate()
-
-    def _load_from_state_dict(self, *args, **kwargs):
-        self._gate_weight_prep.invalidate()
-        return super()._load_from_state_dict(*args, **kwargs)
-
-    def _apply(self, fn, *args, **kwargs):
-        self._gate_weight_prep.invalidate()
-        return super()._apply(fn, *args, **kwargs)
 
 
 def _make_gate(gate_type, width, splits, allow_relu):

@@ -76,14 +76,20 @@ extern "C" {
 /* Flag, OR-ed into `mode` of the filter-path ops (every dvq_vq_assign_* entry point; ignored in DVQ_MODE_EXACT): the caller
  * guarantees that this workspace is CLEAN FOR THIS CALL'S LAYOUT and that no other stream is using it.  Clean means one of:
  *   (a) the whole workspace was zero-filled (hipMemsetAsync / torch.zeros over all of its bytes) and no op has used it since, or
- *   (b) the last call that used it was a filter-path op WITHOUT DVQ_MODE_FILTER_PASS1 that returned DVQ_OK, through the SAME
- *       entry point and with the SAME shape arguments (B, D, HW or hc / wc, K) as this call.
+ *   (b) the last call that used it was a filter-path op WITHOUT DVQ_MODE_FILTER_PASS1 that returned DVQ_OK, through an entry
+ *       point of the SAME WORKSPACE LAYOUT and with the SAME shape arguments (B, D, HW or hc / wc, K) as this call.  The entry
+ *       points of one group place the live words by one layout function and may hand a clean workspace to each other:
+ *         dense   dvq_vq_assign_nchw_f32, dvq_vq_assign_qconv_f32, dvq_vq_assign_fold_f32, and dvq_vq_assign_flat_f32 as the
+ *                 dense op with B = N, HW = 1   (dvq_vq_assign_workspace_bytes)
+ *         dual    dvq_vq_assign_routed_dual_f32, _routed_qconv_dual_f32, _routed_fold_dual_f32
+ *         triple  dvq_vq_assign_routed_triple_f32, _routed_qconv_triple_f32, _routed_fold_triple_f32
+ *                 (dvq_vq_assign_routed_workspace_bytes with num_branches = 2 / 3)
  * (b) is shape-bound because the live words -- the 1-KiB counter block and the resolver's chunk tickets -- sit BEHIND the loss
  * partials, whose size is a function of B * HW, and the number of tickets is a function of the queue capacity (also B * HW): an
  * op leaves exactly ITS live words zero (its last consumer workgroup puts every counter back), not those of another shape's
  * layout.  A workspace that is merely large enough but was last used with other shape arguments is NOT clean: passing the flag
- * then lets pass 1 index its lists with stale counters (out-of-bounds device writes).  Keep one workspace per (stream, entry
- * point, shape) -- what the Python classes do, quantize._CodebookPrep.workspace -- or drop the flag when the shape changes.
+ * then lets pass 1 index its lists with stale counters (out-of-bounds device writes).  Keep one workspace per (stream, layout
+ * group, shape) -- what the Python classes do, quantize._CodebookPrep.workspace -- or drop the flag when the shape changes.
  * With the flag no zeroing kernel is launched: one kernel boundary (~5 us) less per op.  Without it the op zeroes what it needs
  * first and any bytes are fine (the behaviour of versions before 0.5.0). */
 #define DVQ_MODE_WS_CLEAN 0x100

@@ -164,6 +164,21 @@ def test_cpu_tensors_fail_loudly():
         route_select_dual(torch.zeros(1, 2, 2, 2), torch.zeros(1, 4, 2, 2), torch.zeros(1, 4, 4, 4))
 
 
+def test_vqgan_fusion_check_rejects_a_quant_conv_that_is_no_conv():
+    """encode._can_fuse_vqgan asks whether quant_conv is a fusable nn.Conv2d BEFORE it reads a Conv2d attribute: behind an
+    nn.Identity (or any other module) the answer is False and encode_fixed keeps the generic quant_conv(h) path.  The codebook
+    weight is a stand-in that says it is on the GPU -- a CPU weight would end the check before it reaches quant_conv."""
+    from types import SimpleNamespace
+    from dynamicvectorquantization_amd.encode import _can_fuse_vqgan
+    from dynamicvectorquantization_amd.quantize import VectorQuantizer2
+    q = VectorQuantizer2(64, 256, 0.25).eval()
+    del q.embedding
+    q.embedding = SimpleNamespace(weight=SimpleNamespace(is_cuda=True, dtype=torch.float32, requires_grad=False))
+    with torch.no_grad():
+        assert _can_fuse_vqgan(q, torch.nn.Identity(), torch.zeros(1, 256, 4, 4)) is False
+        assert _can_fuse_vqgan(q, torch.nn.Sequential(torch.nn.Conv2d(256, 256, 1)), torch.zeros(1, 256, 4, 4)) is False
+
+
 def test_state_dict_keys_match_reference():
     """checkpoint compatibility: same keys and shapes as the reference modules"""
     from dynamicvectorquantization_amd.quantize import VectorQuantize2, VectorQuantizer2

@@ -474,6 +474,57 @@ def test_conv_weight_images_are_ordered_across_streams(dev):
     assert torch.equal(c1, c2) and torch.equal(zq1, zq2) and torch.equal(l1, l2)
 
 
+@pytest.mark.parametrize("user", ["codebook", "fold", "gate_weight", "conv_weight"])
+def test_prepared_images_are_ordered_across_streams(dev, user):
+    """the four users of _prepared.PreparedImage -- codebook image, conv folded into the codebook, gate-weight images, conv-weight
+    images: after the parameter behind the image has changed, the first call rebuilds the image on ITS stream; a call on a second
+    stream right after it (no host synchronisation in between, as encode.StreamSlots drives a model) waits for the build's event.
+    Both calls give, bit for bit, what a fully synchronised run on freshly built images gives -- and not what the images of the
+    old parameter gave.  (As in the test above nothing here tries to make a race happen: the ordered outcome is the only one
+    seen.)"""
+    from dynamicvectorquantization_amd import qconv, synth
+    from dynamicvectorquantization_amd.quantize import _CodebookPrep, vq_assign
+    from dynamicvectorquantization_amd.router import DualGrainFeatureRouter
+    K, D, B = 1024, 256, 8
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    E = t(synth.codebook_trained(K, D))
+    x = t(synth.z_tokens(synth.codebook_trained(K, D), B, 32, 32, 995))
+    conv = _conv(dev, D, 996)
+    prep = [_CodebookPrep()]
+    if user == "gate_weight":
+        router = DualGrainFeatureRouter(D, "group-32", "2layer-fc-SiLu").to(dev).eval()
+        hc = t(synth.features(997, B, D, 16, 16))
+        param, new = router.gate[0].weight, t(synth.normal(998, (2 * D, 2 * D), 0.0, 1.0 / np.sqrt(2 * D)))
+        run = lambda: (router(h_fine=x, h_coarse=hc),)
+    elif user == "codebook":
+        param, new = E, t(synth.codebook_trained(K, D, seed=999))
+        run = lambda: vq_assign(x, E, prep[0], None)
+    else:
+        param, new = conv.weight, t(synth.normal(1000, (D, D, 1, 1), 0.0, 1.0 / np.sqrt(D)))
+        kw = dict(fold=True, want_loss=False) if user == "fold" else {}
+        run = lambda: [r for r in vq_assign(x, E, prep[0], None, conv=conv, **kw) if r is not None]
+    same = lambda a, b: all(torch.equal(u, v) for u, v in zip(a, b))
+    with torch.no_grad():
+        old = run()                                      # the images of the old parameter exist and are complete
+        torch.cuda.synchronize()
+        param.copy_(new)                                 # in place: same storage, next version
+        torch.cuda.synchronize()
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        with torch.cuda.stream(s1):
+            r1 = run()
+        with torch.cuda.stream(s2):
+            r2 = run()
+        torch.cuda.synchronize()
+        prep[0] = _CodebookPrep()                        # the synchronised run: one stream, every image built anew
+        qconv.invalidate(conv)
+        if user == "gate_weight":
+            router.invalidate_gate_cache()
+        ref = run()
+        torch.cuda.synchronize()
+    assert same(r1, ref) and same(r2, ref)
+    assert not same(old, ref)
+
+
 @pytest.mark.parametrize("routed", [False, True])
 def test_fused_conv_resolver_overflow_hands_h_to_the_exact_list(dev, oracle_mod, routed):
     """with the conv fused in, the tokens the RESOLVER sends to the exact list (more than RES_CAND = 512
