@@ -51,6 +51,7 @@ EXPORTS = (
     "dvq_rq_workspace_bytes", "dvq_rq_residual_offset", "dvq_rq_step_f32", "dvq_rq_loss_f32", "dvq_rq_backward_f32",
     "dvq_rq_embed_code_f32",
     "dvq_sample_head_f32", "dvq_sample_transfer_count_i64", "dvq_sample_transfer_fill_i64",
+    "dvq_decode_table_bytes", "dvq_decode_table_prepare_f32", "dvq_decode_head_f32",
 )
 
 
@@ -209,6 +210,12 @@ def _load():
     lib.dvq_sample_transfer_count_i64.argtypes = [vp, i64, i32, i32, i32, i64, i32, vp, vp, vp]
     lib.dvq_sample_transfer_fill_i64.restype = i32
     lib.dvq_sample_transfer_fill_i64.argtypes = [vp, i64, i32, i32, i32, i64, i32, i32, i32, i64, i64, i64, i32, vp, vp]
+    lib.dvq_decode_table_bytes.restype = sz
+    lib.dvq_decode_table_bytes.argtypes = [i32, i32]
+    lib.dvq_decode_table_prepare_f32.restype = i32
+    lib.dvq_decode_table_prepare_f32.argtypes = [vp, i32, i32, vp, vp, i32, vp, sz, vp]
+    lib.dvq_decode_head_f32.restype = i32
+    lib.dvq_decode_head_f32.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
     return lib
 
 

@@ -6,7 +6,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 900   // 0.9.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1000   // 0.10.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -74,6 +74,9 @@ int dvq_launch_transfer_fill(const long long *cp, long long cstride, int B, int 
                              hipStream_t st);
 int dvq_sample_max_vocab(void);
 int dvq_sample_max_cells(void);
+int dvq_launch_decode_table(const float *E, int rows, int D, const float *W, const float *bias, int C, float *T, hipStream_t st);
+int dvq_launch_decode_head(const long long *codes, int B, int HW, const float *T, int rows, int C, const float *F, const float *L,
+                           float *out, hipStream_t st);
 int dvq_launch_ema_accumulate(const float *z, const long long *codes, int D, int HW, long N, int K,
                               float *cluster_size, float *vectors_sum, hipStream_t st);
 int dvq_launch_entropy_map(const float *img, int B, int H, int W, float *out, hipStream_t st);
@@ -1120,6 +1123,46 @@ int dvq_sample_transfer_fill_i64(const int64_t *coarse_position, int64_t row_str
     return hip_rc(dvq_launch_transfer_fill((const long long *)coarse_position, row_stride, B, Lc, hc, coarse_position_eos,
                                            variant, order, sos_mode, sos_code, fine_position_eos, fine_position_pad, L,
                                            (long long *)out, (hipStream_t)stream), "transfer_fill");
+}
+
+#define DVQ_DECODE_MAX_C 1024   // channels of the decode head; also the widest codebook the table kernel keeps in LDS
+
+size_t dvq_decode_table_bytes(int rows, int C)
+{
+    if (rows <= 0 || C <= 0) return 0;
+    return ((size_t)rows * C * sizeof(float) + 255) / 256 * 256;
+}
+
+int dvq_decode_table_prepare_f32(const float *codebook, int rows, int D, const float *conv_weight, const float *conv_bias, int C,
+                                 void *table, size_t table_bytes, void *stream)
+{
+    const char *fn = "dvq_decode_table_prepare_f32";
+    if (!codebook) { dvq_set_error("%s: null codebook", fn); return DVQ_EINVAL; }
+    if (rows <= 0 || D <= 0 || C <= 0) { dvq_set_error("%s: rows=%d D=%d C=%d must be positive", fn, rows, D, C); return DVQ_EINVAL; }
+    if (!conv_weight) {                                          // no conv: the codebook is the table, nothing to build
+        if (conv_bias || C != D) { dvq_set_error("%s: without a conv weight there is no bias and C (%d) must equal D (%d)", fn, C, D); return DVQ_EINVAL; }
+        return DVQ_OK;
+    }
+    if (!table) { dvq_set_error("%s: null table", fn); return DVQ_EINVAL; }
+    if (D > DVQ_DECODE_MAX_C || C > DVQ_DECODE_MAX_C) { dvq_set_error("%s: D=%d / C=%d exceed %d", fn, D, C, DVQ_DECODE_MAX_C); return DVQ_EINVAL; }
+    if ((size_t)rows * C >= ((size_t)1 << 40)) { dvq_set_error("%s: table too large", fn); return DVQ_EINVAL; }
+    if (table_bytes < dvq_decode_table_bytes(rows, C)) { dvq_set_error("%s: table buffer %zu < %zu bytes", fn, table_bytes, dvq_decode_table_bytes(rows, C)); return DVQ_EWORKSPACE; }
+    if (((uintptr_t)table & 15) != 0) { dvq_set_error("%s: table must be 16-byte aligned", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_decode_table(codebook, rows, D, conv_weight, conv_bias, C, (float *)table, (hipStream_t)stream), "decode_table");
+}
+
+int dvq_decode_head_f32(const int64_t *codes, int B, int HW, const float *table, int rows, int C, const float *pos_first,
+                        const float *pos_second, float *h_in, void *stream)
+{
+    const char *fn = "dvq_decode_head_f32";
+    if (!codes || !table || !h_in) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (B <= 0 || HW <= 0 || rows <= 0 || C <= 0) { dvq_set_error("%s: B=%d HW=%d rows=%d C=%d must be positive", fn, B, HW, rows, C); return DVQ_EINVAL; }
+    if (C % 4 != 0 || C > DVQ_DECODE_MAX_C) { dvq_set_error("%s: C=%d must be a multiple of 4, at most %d", fn, C, DVQ_DECODE_MAX_C); return DVQ_EINVAL; }
+    if ((size_t)B * HW >= ((size_t)1 << 31) - 64 || (size_t)B * HW * C >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EINVAL; }
+    if (((uintptr_t)table & 15) != 0) { dvq_set_error("%s: table must be 16-byte aligned", fn); return DVQ_EINVAL; }
+    if ((((uintptr_t)h_in | (uintptr_t)pos_first | (uintptr_t)pos_second) & 3) != 0) { dvq_set_error("%s: misaligned float pointer", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_decode_head((const long long *)codes, B, HW, table, rows, C, pos_first, pos_second, h_in,
+                                         (hipStream_t)stream), "decode_head");
 }
 
 }  // extern "C"

@@ -28,6 +28,8 @@
  *     (quantize.py: _padded_width); divide the returned loss mean by D / D_padded.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.10.0 dvq_decode_table_bytes, dvq_decode_table_prepare_f32, dvq_decode_head_f32 (new): codes -> the input of the decoder's
+ *          conv_in (codebook gather, post_quant_conv and the decoder's position biases as one kernel).  Nothing else changed.
  *   0.9.0  dvq_sample_head_f32, dvq_sample_transfer_count_i64, dvq_sample_transfer_fill_i64 (new): the sampling step and the
  *          coarse -> fine position transfer of stage-2 generation.  top_k = 0 and top_p = 0 switch the filter off (the reference's
  *          None); any other k < 1 or p outside (0, 1] is DVQ_EINVAL.  Nothing else changed.
@@ -626,6 +628,35 @@ DVQ_API int dvq_sample_transfer_fill_i64(const int64_t *coarse_position, int64_t
                                          int64_t coarse_position_eos, int variant, int order, int sos_mode, int64_t sos_code,
                                          int64_t fine_position_eos, int64_t fine_position_pad, int L, int64_t *out,
                                          void *stream);
+
+/*
+ * Decode head: code indices -> the tensor the decoder's conv_in reads.  Replaces, after permuter.forward_back
+ * (models/stage2_dynamic/dqtransformer_uncond_entropy.py:174-178; stage-1 decode_code, models/stage1_dynamic/dqvae_triple_feat.py:84-87):
+ * quantize.get_codebook_entry (quantize2_mask.py:207-210), `.permute(0, 3, 1, 2)`, post_quant_conv
+ * (models/stage1_dynamic/dqvae_dual_entropy.py:136-137) and the position block of Decoder.forward
+ * (modules/dynamic_modules/DecoderPositional.py:109-118).
+ *
+ * dvq_decode_table_prepare_f32: table[r, o] = sum_k conv_weight[o, k] * codebook[r, k] + conv_bias[o], r < rows -- the 1x1 conv
+ * applied to every codebook row once (it acts per pixel, so conv(E[code]) is row `code` of this table).  `rows` is the row count of
+ * the weight tensor handed in: K + 1 for VQEmbedding (its padding row is a valid index of get_codebook_entry), K for
+ * VectorQuantizer2.  fp32: one fmaf chain per output, k ascending from 0, then one add of the bias; no atomics, the same bits every
+ * run; within 1e-5 * (sum_k |w||e| + |b|) of the float64 conv.  D, C <= 1024.  table: >= dvq_decode_table_bytes(rows, C), 16-byte
+ * aligned.  conv_weight == NULL (then conv_bias == NULL and C == D): there is no conv, nothing is built or written -- hand the
+ * codebook itself to dvq_decode_head_f32 as its table.  Run once per (codebook, conv) pair.
+ *
+ * dvq_decode_head_f32: h_in[b, c, p] = fl(fl(table[codes[b, p], c] + pos_first[c, p]) + pos_second[c, p]), p < HW -- the two adds
+ * round as the reference's two position modules do; an add whose table is NULL is skipped.
+ *   codes [B, HW] int64; a code outside [0, rows) writes NaNs to that token's C outputs (the rule of dvq_embed_gather_f32)
+ *   table [rows, C], 16-byte aligned; pos_first, pos_second nullable [C, HW]; h_in [B, C, HW] (NCHW)
+ *   C % 4 == 0, C <= 1024, any HW >= 1, any B with B * HW < 2^31 - 64: anything else is DVQ_EINVAL
+ * 16-byte loads and stores along the token axis when HW % 4 == 0 and pos_first, pos_second, h_in are 16-byte aligned, 4-byte ones
+ * otherwise: the same values.  One launch, no workspace, capturable in a HIP graph.
+ */
+DVQ_API size_t dvq_decode_table_bytes(int rows, int C);
+DVQ_API int dvq_decode_table_prepare_f32(const float *codebook, int rows, int D, const float *conv_weight,
+                                         const float *conv_bias, int C, void *table, size_t table_bytes, void *stream);
+DVQ_API int dvq_decode_head_f32(const int64_t *codes, int B, int HW, const float *table, int rows, int C,
+                                const float *pos_first, const float *pos_second, float *h_in, void *stream);
 
 /*
  * Wire format of the image-parallel exchange (one all-gather per batch; the reference gathers nothing --
