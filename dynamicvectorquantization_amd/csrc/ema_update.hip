@@ -14,6 +14,8 @@
 // a ds_add_f32 wave-instruction takes 192 cycles whatever its address pattern (tools/micro/lds_atomic_rate.hip: three
 // cycles per lane, 170 G adds/s over the chip, below the 233 G/s the L2 atomics reach here); profiles/archive/r03_ema_lds_negative.json.
 #include "dvq_common.h"
+#include <stdio.h>
+#include <stdlib.h>
 
 // COMBINE: tokens of a tile that chose the same code are summed in LDS first and reach the global sums as ONE row of
 // atomics (leader = the first such token; members as a 64-bit mask).  Equal codes inside 64 consecutive positions are the
@@ -527,11 +529,26 @@ __global__ __launch_bounds__(256) void ema_update_kernel(const float *__restrict
     }
 }
 
+// The reference computes `alpha = 1 - self.decay` in Python doubles and only then rounds it to fp32: 1 - 0.99 -> 0.01f.  decay crosses the
+// ABI as fp32, and 1 - (double)0.99f = 0.00999999046 is 1e-6 (relative) away from that -- enough to carry an embed_ema entry whose two
+// terms cancel, and the weight behind it, out of the 1e-5 contract (tests/test_train_step.py, K = 16384).  So the double the caller wrote is
+// recovered first: the shortest decimal that rounds to the fp32 received (0.99f -> 0.99).  A decay that is no short decimal gets what the
+// plain subtraction gave, within half an fp32 ulp of decay.
+static double decay_as_written(float decay)
+{
+    char buf[32];
+    for (int p = 1; p <= 9; ++p) {
+        snprintf(buf, sizeof buf, "%.*g", p, (double)decay);
+        if (strtof(buf, nullptr) == decay) return strtod(buf, nullptr);
+    }
+    return (double)decay;
+}
+
 int dvq_launch_ema_update(const float *stats_sum, const float *stats_count, float decay, float eps, int K, int D,
                           const float *cs_old, float *cs_new, float *embed_ema, float *weight, int restart, const float *restart_rows,
                           const float *z, int HW, const long long *pick, hipStream_t st)
 {
-    const float alpha = (float)(1.0 - (double)decay);        // what `alpha = 1 - self.decay` (Python doubles) becomes as an fp32 scalar
+    const float alpha = (float)(1.0 - decay_as_written(decay));   // what `alpha = 1 - self.decay` (Python doubles) becomes as an fp32 scalar
     hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, st, stats_sum, stats_count, decay, alpha, eps, K,
                        D, cs_old, cs_new, embed_ema, weight, restart, restart_rows, z, HW, pick);
     return (int)hipGetLastError();

@@ -392,7 +392,8 @@ DVQ_API int dvq_restart_pick_i64(uint64_t seed, int64_t n, int k, int64_t *out, 
  * copy it over the buffer afterwards); embed_ema [K, D] is updated in place; weight: rows 0 .. K-1 of a [>= K, D] tensor are written.
  * restart: 0 none; 1 rows from restart_rows [K, D] (data-parallel: rank 0's, broadcast by the caller); 2 rows gathered from the NCHW
  * latents z [B, D, HW] at token index pick[j] in [0, B * HW) (dvq_restart_pick_i64).  fp32, the reference's operation order; the sum n is
- * accumulated in double: equal to the reference within rounding (1e-5).
+ * accumulated in double: equal to the reference within rounding (1e-5).  The reference's `1 - decay` is a Python double rounded to
+ * fp32 afterwards: it is formed from the shortest decimal that rounds to the fp32 `decay` received (0.99f -> 1 - 0.99 -> 0.01f).
  */
 DVQ_API int dvq_ema_update_f32(const float *stats_sum, const float *stats_count, float decay, float eps, int K, int D,
                                const float *cluster_size_ema, float *cluster_size_out, float *embed_ema, float *weight,
