@@ -220,9 +220,10 @@ __device__ unsigned long long *g_dvq_stamps = nullptr;
 // would have produced, up to which of two equal scores is called best (tokens that close are undecided either way).
 // Dynamic LDS of every form of pass 1 (the wide kernel's too): 4 ring slots of a code tile's image (D / 16 KiB each), the slots'
 // accumulator seeds per wave ([4][4 waves][64] floats) and a 2-KiB permutation scratch per wave -- the carve below
+#define DVQ_SEED_TABLE_TILES 32   // code tiles whose seeds fit the seeds area as one table ([32 tiles][32] floats = its 4 KiB)
 constexpr size_t dvq_pass1_lds_bytes(int D) { return 4 * (size_t)(D / 16) * 1024 + 4 * 4 * 64 * sizeof(float) + 4 * 2048; }
 
-template <int D, int SEL, bool CONV, bool FOLD, bool NT, bool FLAT = false, bool SPLIT = false>
+template <int D, int SEL, bool CONV, bool FOLD, bool NT, bool RES, bool FLAT = false, bool SPLIT = false>
 __device__ __forceinline__ void pass1_body(
     const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
     const float *__restrict__ E, const float *__restrict__ mask,
@@ -243,8 +244,12 @@ __device__ __forceinline__ void pass1_body(
     constexpr int TILE_STRIDE = IMG_BYTES + 256;
     constexpr int CPW = (S16 + NW - 1) / NW;
     static_assert(CPW * NW == S16 && CPW <= 4, "a wave's chunks of a code tile are contiguous and within the instruction offset");
-    constexpr int PER_TILE = CPW + 1;
     constexpr int NBUF = 4;
+    // RES: the accumulator seeds of ALL of the workgroup's code tiles are resident in the seeds area ([T <= SEED_TILES][32] floats,
+    // loaded once in the prologue; the launcher picks the form); else a tile's seeds travel with its image, a copy per wave
+    constexpr int SEED_TILES = NBUF * NW * 64 / 32;
+    static_assert(SEED_TILES == DVQ_SEED_TABLE_TILES, "the launcher's limit is the table's size");
+    constexpr int PER_TILE = RES ? CPW : CPW + 1;            // DMA instructions per wave and ring tile
     // FLAT: the per-wave transposition image of half a row per token (see the prologue)
     constexpr int FLAT_RSH = D * 2 + 16;                     // bytes per token in the image
     constexpr int FLAT_TRW = 32 * FLAT_RSH;                  // bytes per wave
@@ -254,7 +259,7 @@ __device__ __forceinline__ void pass1_body(
     static_assert(NBUF * IMG_BYTES + NBUF * NW * 64 * 4 + NW * 2048 == dvq_pass1_lds_bytes(D), "the launch's LDS is this carve");
     static_assert(!FLAT || NW * FLAT_TRW <= dvq_pass1_lds_bytes(D), "the images fit the kernel's LDS");
     extern __shared__ __attribute__((aligned(16))) char lds[];
-    float *enraw = (float *)(lds + NBUF * IMG_BYTES);        // [NBUF][NW][64] accumulator seeds, per-wave copy
+    float *enraw = (float *)(lds + NBUF * IMG_BYTES);        // accumulator seeds: RES [SEED_TILES][32], else [NBUF][NW][64] (per-wave copies)
     DVQ_STAMP(0);
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -268,12 +273,12 @@ __device__ __forceinline__ void pass1_body(
     const float sB = meta->scale_b;
     char *scr = lds + NBUF * IMG_BYTES + NBUF * NW * 64 * 4 + wave * 2048;   // this wave's permutation scratch
 
-    // DMA of code tile t into its ring slot, in PER_TILE pieces (q < CPW: 1 KiB of the image, q == CPW:
-    // this wave's copy of the seeds).  Past the end: harmless repeat, so the counts stay constant.
+    // DMA of code tile t into its ring slot, in PER_TILE pieces (q < CPW: 1 KiB of the image; without the resident table
+    // q == CPW: this wave's copy of the seeds).  Past the end: harmless repeat, so the counts stay constant.
     auto issue_piece = [&](int t, int q) {
         const int tt = (t < T) ? t : T - 1;
         const char *src = img + (size_t)tt * TILE_STRIDE;
-        if (q < CPW) {
+        if (RES || q < CPW) {
             // this wave's CPW chunks are contiguous (S16 = NW * CPW for every supported D): one base, the chunk as the
             // instruction offset, which applies to the global and the LDS address alike
             const char *s0 = src + wave * (CPW * 1024) + lane * 16;
@@ -292,6 +297,23 @@ __device__ __forceinline__ void pass1_body(
 #pragma unroll
         for (int q = 0; q < PER_TILE; ++q) issue_piece(t, q);
     };
+    // RES: the seed table, once per workgroup: the 32 seeds in use of every tile's 256-byte tail, gathered by the per-lane source
+    // address (a wave-instruction = two tiles -> 256 contiguous LDS bytes; 4 instructions per wave; past the end: harmless
+    // repeat).  Issued in FRONT of the first ring tile: the counted wait at the head of tile 0 (all but the youngest tile's
+    // pieces) covers the older table pieces of this wave, the barrier behind it everybody's.
+    auto issue_seeds = [&]() {
+        if constexpr (RES) {
+#pragma unroll
+            for (int k = 0; k < SEED_TILES / 2 / NW; ++k) {
+                // wave-uniform base (scalar registers) + one 32-bit lane offset: the pair's first tile, and its second one for the
+                // upper lane half where that tile exists
+                const int pair = wave * (SEED_TILES / 2 / NW) + k;
+                const int t0 = (2 * pair < T) ? 2 * pair : T - 1;
+                const unsigned voff = (unsigned)c * 4u + ((t0 + 1 < T) ? (unsigned)h * (unsigned)TILE_STRIDE : 0u);
+                glds4(img + (size_t)t0 * TILE_STRIDE + IMG_BYTES + voff, enraw + pair * 64);
+            }
+        }
+    };
     const int tile_id = SPLIT ? (int)(blockIdx.x / (unsigned)ksplit) : xcd_swizzle(blockIdx.x, gridDim.x);
     // SEL == 2 parks the coarser branches in the ring slots from `pre` on: 2 slots = D x 128 B for the 2x-coarser
     // branch (dual: slots 2, 3; triple: slots 1, 2), slot 3 for the triple's 4x-coarser branch (D x 32 B)
@@ -299,7 +321,7 @@ __device__ __forceinline__ void pass1_body(
 
     const int n_raw = (tile_id * NW + wave) * 32 + c;
     const int n = (n_raw < N) ? n_raw : -1;
-    auto token_base = [&]() -> size_t {
+    auto token_base = [&](int HW, int h) -> size_t {         // (HW and h as arguments: the epilogue passes re-derived copies, below)
         const long nn = (n >= 0) ? n : N - 1;
         if constexpr (FLAT) return (size_t)nn * D + 8 * h;
         const long bimg = nn / HW;
@@ -310,14 +332,14 @@ __device__ __forceinline__ void pass1_body(
     // smallest of the wave, or the image's base) + a 32-bit lane offset in ONE vector register + the channel's stride in a scalar
     // register -- no vector instruction per access (global_load / global_store took one 64-bit vector add each: 270 of a block's
     // ~8000 instructions).  D * HW < 2^29 (checked by the launcher) keeps every byte offset below 2^31.
-    auto wave_base = [&](const float *p0) -> __amdgpu_buffer_rsrc_t {     // resource at p0 + (lane 0's token_base())
-        const size_t tb = token_base();
+    auto wave_base = [&](const float *p0, int hw, int hh) -> __amdgpu_buffer_rsrc_t {     // resource at p0 + (lane 0's token_base())
+        const size_t tb = token_base(hw, hh);
         const size_t tb0 = ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tb >> 32)) << 32) |
                            (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tb & 0xFFFFFFFFu));
         return __builtin_amdgcn_make_buffer_rsrc((void *)(p0 + tb0), 0, -1, 0x00020000);
     };
-    auto lane_off = [&]() -> unsigned {                      // byte offset of this lane's token_base() from lane 0's
-        const size_t tb = token_base();
+    auto lane_off = [&](int hw, int hh) -> unsigned {        // byte offset of this lane's token_base() from lane 0's
+        const size_t tb = token_base(hw, hh);
         const size_t tb0 = ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tb >> 32)) << 32) |
                            (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tb & 0xFFFFFFFFu));
         return (unsigned)(tb - tb0) * 4u;
@@ -465,7 +487,7 @@ __device__ __forceinline__ void pass1_body(
             __builtin_amdgcn_sched_barrier(0);               // in place, one k-step's bias at a time (hoisted bias reads spill)
         }
         if (cv.h_all && n >= 0) {                            // tests: the conv's output for every token
-            float *hp = cv.h_buf + token_base();
+            float *hp = cv.h_buf + token_base(HW, h);
 #pragma unroll
             for (int s = 0; s < S16; ++s)
 #pragma unroll
@@ -473,6 +495,7 @@ __device__ __forceinline__ void pass1_body(
         }
         __builtin_amdgcn_s_barrier();                        // every wave is done with the weight slots and the bias:
         asm volatile("" ::: "memory");                       // the ring and the seeds area go to the code tiles
+        issue_seeds();
         for (int t = 0; t < 3; ++t) issue(t);
         __builtin_amdgcn_sched_barrier(0);                   // (the conversion below must not be hoisted over this: all of zf is ready)
     };
@@ -513,6 +536,7 @@ __device__ __forceinline__ void pass1_body(
             if constexpr (CONV) {
                 conv_prologue(zp, st);
             } else {
+            issue_seeds();
             for (int t = 0; t < pre; ++t) issue(t);
             __builtin_amdgcn_s_setprio(2);
 #pragma unroll
@@ -522,6 +546,7 @@ __device__ __forceinline__ void pass1_body(
             __builtin_amdgcn_s_setprio(0);
             }
         } else {
+            issue_seeds();
             for (int t = 0; t < pre; ++t) issue(t);
             // workgroup = output rows y0 .. y0 + 3 of image b (wave = row, lane = column); both are wave-uniform
             const int bw = __builtin_amdgcn_readfirstlane(b);
@@ -564,7 +589,7 @@ __device__ __forceinline__ void pass1_body(
             by_products(sel_g);
         }
     } else if constexpr (CONV) {
-        conv_prologue(z + token_base(), (size_t)HW);
+        conv_prologue(z + token_base(HW, h), (size_t)HW);
     } else if constexpr (FLAT) {
         // Row-major latents.  Read as what they are -- every wave-instruction fetches whole 128-byte lines (a token's HALF row,
         // D * 2 bytes, is contiguous: lane = 16-byte piece) -- and turned into the (token, 8 channels of a k-step) register
@@ -600,11 +625,13 @@ __device__ __forceinline__ void pass1_body(
             }
         }
         __syncthreads();                                     // every wave has read its image: the region becomes the code ring
+        issue_seeds();                                       // (and the seeds area, which the images may cover)
         for (int t = 0; t < pre; ++t) issue(t);
     } else {
+        issue_seeds();
         for (int t = 0; t < pre; ++t) issue(t);
-        const __amdgpu_buffer_rsrc_t zr = wave_base(z);
-        const unsigned zo = lane_off();
+        const __amdgpu_buffer_rsrc_t zr = wave_base(z, HW, h);
+        const unsigned zo = lane_off(HW, h);
         __builtin_amdgcn_s_setprio(2);
 #pragma unroll
         for (int s = 0; s < S16; ++s)
@@ -747,9 +774,10 @@ __device__ __forceinline__ void pass1_body(
             if (t > 0) top2(t - 1);
             __builtin_amdgcn_sched_barrier(0);
             {
-                // accumulator seeds of tile t: this wave's own DMA copy (landed by the wait above), read behind the fragments
+                // accumulator seeds of tile t, read behind the fragments: from the resident table (landed before tile 0's barrier),
+                // or from this wave's own DMA copy (landed by the wait above)
                 const unsigned seed_a = (unsigned)(size_t)(const __attribute__((address_space(3))) char *)(
-                                            enraw + ((t & (NBUF - 1)) * NW + wave) * 64 + 4 * q16);
+                                            RES ? enraw + t * 32 + 4 * q16 : enraw + ((t & (NBUF - 1)) * NW + wave) * 64 + 4 * q16);
                 f32x4 e0, e1;
                 asm volatile("ds_read_b128 %0, %1" : "=v"(e0) : "v"(seed_a));
                 asm volatile("ds_read_b128 %0, %1 offset:64" : "=v"(e1) : "v"(seed_a));
@@ -757,7 +785,7 @@ __device__ __forceinline__ void pass1_body(
                 acc16[0][0] = e0; acc16[0][1] = e0; acc16[1][0] = e1; acc16[1][1] = e1;
             }
             __builtin_amdgcn_sched_barrier(0);
-#define DVQ_PIECE(Q) issue_piece(t + 3, Q);
+#define DVQ_PIECE(Q) if constexpr ((Q) < PER_TILE) { issue_piece(t + 3, Q); }
 #define DVQ_MM(src, F, WAIT, NEXT)                                                                             \
             asm volatile("s_waitcnt lgkmcnt(" #WAIT ")" ::: "memory");                                            \
             __builtin_amdgcn_sched_barrier(0);                                                                    \
@@ -901,7 +929,10 @@ __device__ __forceinline__ void pass1_body(
         if (h == 0) codes[n] = (long long)code;
         m_tok = (SEL != 0) ? __builtin_fabsf(sel_mask) : ((mask != nullptr) ? mask[n] : 1.0f);
         if (zq != nullptr || partials != nullptr) {
-            const float *ep = E + (size_t)code * D + 8 * h;
+            // (the lane half re-derived from the lane id: `8 * h` of the prologue does not live in a VGPR through the code loop)
+            int h_e = h;                                     // (where it frees the register; elsewhere it costs some)
+            if constexpr (FOLD || (FLAT && SPLIT)) h_e = (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >> 5);
+            const float *ep = E + (size_t)code * D + 8 * h_e;
             // gathers per batch: 2 k-steps (A/B on MI355X: 2 beats 1, 4, 8 and a 3-deep pipeline) where other workgroups hide the
             // latency; the split form's merging workgroup is alone on its CU and takes 8 (two round trips instead of eight)
             constexpr int SB = SPLIT ? ((S16 < 8) ? S16 : 8) : ((S16 < 2) ? S16 : 2);
@@ -910,8 +941,10 @@ __device__ __forceinline__ void pass1_body(
             // exec-masked branch to an out-of-line block.
             auto finish = [&](auto store_tag) {
                 constexpr bool STORE = decltype(store_tag)::value;
-                const __amdgpu_buffer_rsrc_t qr = wave_base(STORE ? zq : (float *)E);
-                const unsigned qo = lane_off();
+                int hw_e = HW;                               // opaque: the token's offset is recomputed from it here (a division
+                asm volatile("" : "+s"(hw_e));               // by HW, once) instead of keeping the prologue's reciprocal of HW in a
+                const __amdgpu_buffer_rsrc_t qr = wave_base(STORE ? zq : (float *)E, hw_e, h_e);       // VGPR through the code loop
+                const unsigned qo = lane_off(hw_e, h_e);
                 int hw4 = HW * 4;                            // opaque: the 128 scalar offsets are recomputed here (two scalar
                 asm volatile("" : "+s"(hw4));                // instructions each) instead of living in spilled SGPRs since the prologue
 #pragma unroll
@@ -1901,7 +1934,8 @@ __global__ __launch_bounds__(DVQ_RES_WAVES * 64, DVQ_RES_WAVES > 4 ? 1 : 2) void
     DVQ_RSTAMP(6);
 }
 
-template <int D, int SEL, bool CONV, bool FOLD = false>
+// RES (every form below): pass1_body's resident seed table, for launches whose workgroups take at most 32 code tiles each
+template <int D, int SEL, bool CONV, bool FOLD, bool RES>
 __global__ __launch_bounds__(256, 2) void vq_assign_filter_kernel(
     const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
     const float *__restrict__ E, const float *__restrict__ mask,
@@ -1909,11 +1943,11 @@ __global__ __launch_bounds__(256, 2) void vq_assign_filter_kernel(
     double *__restrict__ partials, int *__restrict__ counters, int *__restrict__ exact_list,
     char *__restrict__ records, int rec_cap, const DvqRouted rv, const DvqConv cv)
 {
-    pass1_body<D, SEL, CONV, FOLD, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records, rec_cap, rv, cv);
+    pass1_body<D, SEL, CONV, FOLD, true, RES>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records, rec_cap, rv, cv);
 }
 
 // row-major latents [N, D] (FLAT, see pass1_body)
-template <int D, bool FOLD>
+template <int D, bool FOLD, bool RES>
 __global__ __launch_bounds__(256, 2) void vq_assign_filter_flat_kernel(
     const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
     const float *__restrict__ E, const float *__restrict__ mask,
@@ -1921,7 +1955,7 @@ __global__ __launch_bounds__(256, 2) void vq_assign_filter_flat_kernel(
     double *__restrict__ partials, int *__restrict__ counters, int *__restrict__ exact_list,
     char *__restrict__ records, int rec_cap, const DvqRouted rv, const DvqConv cv)
 {
-    pass1_body<D, 0, false, FOLD, true, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records, rec_cap, rv, cv);
+    pass1_body<D, 0, false, FOLD, true, RES, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records, rec_cap, rv, cv);
 }
 
 // small batches: `ksplit` workgroups per token block, each on its slice of the code tiles (SPLIT, see pass1_body).  Dense (FLAT:
@@ -1929,7 +1963,7 @@ __global__ __launch_bounds__(256, 2) void vq_assign_filter_flat_kernel(
 // codebook_mask / gate), with the 1x1 conv as the prologue (CONV: every slice's workgroup computes the block's h itself,
 // 3 x 8.4 MFLOP, nothing to share; the conv's inputs are read with the non-temporal hint) or on the conv-folded codebook (FOLD:
 // loss-free inference / stage-2 tokenisation of single images)
-template <int D, int SEL, bool CONV, bool FOLD, bool FLAT>
+template <int D, int SEL, bool CONV, bool FOLD, bool FLAT, bool RES>
 __global__ __launch_bounds__(256, 2) void vq_assign_filter_split_kernel(
     const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
     const float *__restrict__ E, const float *__restrict__ mask,
@@ -1937,12 +1971,12 @@ __global__ __launch_bounds__(256, 2) void vq_assign_filter_split_kernel(
     double *__restrict__ partials, int *__restrict__ counters, int *__restrict__ exact_list,
     char *__restrict__ records, int rec_cap, const DvqRouted rv, const DvqConv cv, f32x4 *__restrict__ split, int ksplit)
 {
-    pass1_body<D, SEL, CONV, FOLD, CONV, FLAT, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records,
+    pass1_body<D, SEL, CONV, FOLD, CONV, RES, FLAT, true>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records,
                                                      rec_cap, rv, cv, split, ksplit);
 }
 
 // the same kernel with plain loads of the latents, for batches that fit the memory-side cache (dense or staged select, no conv)
-template <int D, int SEL, bool FOLD>
+template <int D, int SEL, bool FOLD, bool RES>
 __global__ __launch_bounds__(256, 2) void vq_assign_filter_cached_kernel(
     const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
     const float *__restrict__ E, const float *__restrict__ mask,
@@ -1950,7 +1984,7 @@ __global__ __launch_bounds__(256, 2) void vq_assign_filter_cached_kernel(
     double *__restrict__ partials, int *__restrict__ counters, int *__restrict__ exact_list,
     char *__restrict__ records, int rec_cap, const DvqRouted rv, const DvqConv cv)
 {
-    pass1_body<D, SEL, false, FOLD, false>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records, rec_cap, rv, cv);
+    pass1_body<D, SEL, false, FOLD, false, RES>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records, rec_cap, rv, cv);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -2296,30 +2330,34 @@ struct P1Args {
     hipStream_t st;
 };
 
-// One launch site per kernel family.  `if constexpr` keeps to the kernels the plans use: 20 plain, 4 cached, 6 flat, 17 split, 1 wide.
-template <int D, int SEL, bool CONV, bool FOLD, bool FLAT>
+// One launch site per kernel family.  `if constexpr` keeps to the kernels the plans use: 20 plain, 4 cached, 6 flat, 17 split, each
+// with and without the resident seed table (RES), and 1 wide.
+template <int D, int SEL, bool CONV, bool FOLD, bool FLAT, bool RES>
 static int launch_pass1_form(const P1Plan &p, const P1Args &a)
 {
     const unsigned nb = (unsigned)((a.N + 127) / 128);
     const size_t lds = dvq_pass1_lds_bytes(D);
+    // two row-major forms at D = 256 keep the per-tile seed piece at every K: with the table their register allocation spills
+    // 2 - 3 dwords more (flat FOLD 6 -> 9, split flat 7 -> 9)
+    constexpr bool RES_FLAT = RES && !(D == 256 && FOLD), RES_SPLIT = RES && !(D == 256 && FLAT);
 #define DVQ_P1_ARGS a.z, a.img16, a.meta, a.E, a.mask, a.HW, a.K, a.N, a.zq, a.codes, a.partials, a.w.counters, a.w.exact_list, \
                     a.w.records, a.w.cap / DVQ_QSHARDS
     switch (p.form) {
     case P1Form::plain:
         if constexpr (!FLAT)
-            return dvq_launch_lds<vq_assign_filter_kernel<D, SEL, CONV, FOLD>>(dim3(nb), dim3(256), lds, a.st, DVQ_P1_ARGS, a.rv, a.cv);
+            return dvq_launch_lds<vq_assign_filter_kernel<D, SEL, CONV, FOLD, RES>>(dim3(nb), dim3(256), lds, a.st, DVQ_P1_ARGS, a.rv, a.cv);
         break;
     case P1Form::cached:
         if constexpr (D == 256 && SEL != 1 && !CONV && !FLAT)
-            return dvq_launch_lds<vq_assign_filter_cached_kernel<D, SEL, FOLD>>(dim3(nb), dim3(256), lds, a.st, DVQ_P1_ARGS, a.rv, a.cv);
+            return dvq_launch_lds<vq_assign_filter_cached_kernel<D, SEL, FOLD, RES>>(dim3(nb), dim3(256), lds, a.st, DVQ_P1_ARGS, a.rv, a.cv);
         break;
     case P1Form::flat:
         if constexpr (FLAT)
-            return dvq_launch_lds<vq_assign_filter_flat_kernel<D, FOLD>>(dim3(nb), dim3(256), lds, a.st, DVQ_P1_ARGS, a.rv, a.cv);
+            return dvq_launch_lds<vq_assign_filter_flat_kernel<D, FOLD, RES_FLAT>>(dim3(nb), dim3(256), lds, a.st, DVQ_P1_ARGS, a.rv, a.cv);
         break;
     case P1Form::split:
         if constexpr (SEL != 2 && !(FLAT && FOLD))
-            return dvq_launch_lds<vq_assign_filter_split_kernel<D, SEL, CONV, FOLD, FLAT>>(dim3(nb * p.ks), dim3(256), lds, a.st,
+            return dvq_launch_lds<vq_assign_filter_split_kernel<D, SEL, CONV, FOLD, FLAT, RES_SPLIT>>(dim3(nb * p.ks), dim3(256), lds, a.st,
                                                                                          DVQ_P1_ARGS, a.rv, a.cv, a.w.split, p.ks);
         break;
     case P1Form::wide:
@@ -2332,21 +2370,29 @@ static int launch_pass1_form(const P1Plan &p, const P1Args &a)
     return -1000;
 }
 
-// the plan's flags as template arguments
-template <int D>
-static int launch_pass1(const P1Plan &p, const P1Args &a)
+// the plan's flags as template arguments.  RES: a workgroup's code tiles (the split form: its largest slice) fit the seed table that
+// pass1_body keeps in the seeds area, 32 tiles = 1024 codes; larger codebooks take the per-tile seed piece
+template <int D, bool RES>
+static int launch_pass1_res(const P1Plan &p, const P1Args &a)
 {
     if (p.conv) {
         if constexpr (D == 256)
-            return p.sel ? launch_pass1_form<D, 1, true, false, false>(p, a) : launch_pass1_form<D, 0, true, false, false>(p, a);
+            return p.sel ? launch_pass1_form<D, 1, true, false, false, RES>(p, a) : launch_pass1_form<D, 0, true, false, false, RES>(p, a);
         return -1000;
     }
-    if (p.flat) return p.fold ? launch_pass1_form<D, 0, false, true, true>(p, a) : launch_pass1_form<D, 0, false, false, true>(p, a);
+    if (p.flat) return p.fold ? launch_pass1_form<D, 0, false, true, true, RES>(p, a) : launch_pass1_form<D, 0, false, false, true, RES>(p, a);
     switch (p.sel) {
-    case 0:  return p.fold ? launch_pass1_form<D, 0, false, true, false>(p, a) : launch_pass1_form<D, 0, false, false, false>(p, a);
-    case 1:  return p.fold ? launch_pass1_form<D, 1, false, true, false>(p, a) : launch_pass1_form<D, 1, false, false, false>(p, a);
-    default: return p.fold ? launch_pass1_form<D, 2, false, true, false>(p, a) : launch_pass1_form<D, 2, false, false, false>(p, a);
+    case 0:  return p.fold ? launch_pass1_form<D, 0, false, true, false, RES>(p, a) : launch_pass1_form<D, 0, false, false, false, RES>(p, a);
+    case 1:  return p.fold ? launch_pass1_form<D, 1, false, true, false, RES>(p, a) : launch_pass1_form<D, 1, false, false, false, RES>(p, a);
+    default: return p.fold ? launch_pass1_form<D, 2, false, true, false, RES>(p, a) : launch_pass1_form<D, 2, false, false, false, RES>(p, a);
     }
+}
+template <int D>
+static int launch_pass1(const P1Plan &p, const P1Args &a)
+{
+    const int tiles = dvq_num_tiles(a.K);
+    const int per_wg = (p.form == P1Form::split) ? (tiles + p.ks - 1) / p.ks : tiles;
+    return per_wg <= DVQ_SEED_TABLE_TILES ? launch_pass1_res<D, true>(p, a) : launch_pass1_res<D, false>(p, a);
 }
 
 static int launch_resolver(int D, const char *img, const DvqF16Meta *meta, const float *en_all, const float *E,

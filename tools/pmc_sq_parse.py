@@ -4,11 +4,11 @@ acc = collections.defaultdict(lambda: collections.defaultdict(list))
 for f in sorted(glob.glob(out + "/p*/**/*counter_collection.csv", recursive=True)):
     for row in csv.DictReader(open(f)):
         k = row["Kernel_Name"]
-        short = ("pass1_dense" if "vq_assign_filter_kernel<256, 0, false, false>" in k else
-                 "pass1_select_staged_SEL2" if "vq_assign_filter_kernel<256, 2, false, false>" in k else
-                 "pass1_select_per_lane_SEL1" if "vq_assign_filter_kernel<256, 1, false, false>" in k else
-                 "pass1_conv_fused_CONV" if "vq_assign_filter_kernel<256, 1, true, false>" in k else
-                 "pass1_fold_SEL2" if "vq_assign_filter_kernel<256, 2, false, true>" in k else
+        short = ("pass1_dense" if "vq_assign_filter_kernel<256, 0, false, false, true>" in k else
+                 "pass1_select_staged_SEL2" if "vq_assign_filter_kernel<256, 2, false, false, true>" in k else
+                 "pass1_select_per_lane_SEL1" if "vq_assign_filter_kernel<256, 1, false, false, true>" in k else
+                 "pass1_conv_fused_CONV" if "vq_assign_filter_kernel<256, 1, true, false, true>" in k else
+                 "pass1_fold_SEL2" if "vq_assign_filter_kernel<256, 2, false, true, true>" in k else
                  "resolve_fold" if "vq_resolve_kernel<256, true>" in k else
                  ("resolve" if "vq_resolve" in k else ("exact" if "vq_assign_exact" in k else None)))
         if short is None:

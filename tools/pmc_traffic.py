@@ -26,9 +26,9 @@ kernels = {}
 def find(per, prefix):
     ks = [k for k in per if k.startswith(prefix)]
     return ks[0] if ks else None
-for label, prefix in (("dense_pass1", "vq_assign_filter_kernel<256, 0, false, false>"), ("fused_pass1", "vq_assign_filter_kernel<256, 2, false, false>"),
-                      ("fused_pass1_per_lane_select", "vq_assign_filter_kernel<256, 1, false, false>"),
-                      ("model_pass1", "vq_assign_filter_kernel<256, 1, true, false>"), ("fold_pass1", "vq_assign_filter_kernel<256, 2, false, true>"),
+for label, prefix in (("dense_pass1", "vq_assign_filter_kernel<256, 0, false, false, true>"), ("fused_pass1", "vq_assign_filter_kernel<256, 2, false, false, true>"),
+                      ("fused_pass1_per_lane_select", "vq_assign_filter_kernel<256, 1, false, false, true>"),
+                      ("model_pass1", "vq_assign_filter_kernel<256, 1, true, false, true>"), ("fold_pass1", "vq_assign_filter_kernel<256, 2, false, true, true>"),
                       ("resolver", "vq_resolve_kernel<256, false>"), ("fold_resolver", "vq_resolve_kernel<256, true>")):
     kf, kw = find(fetch, prefix), find(write, prefix)
     if kf is None or kw is None:
@@ -61,10 +61,10 @@ if "model_pass1" in kernels:
                     "line_granular_floor_bytes": floor,
                     "ratio_to_line_granular_floor": kernels["model_pass1"]["hbm_bytes_per_launch"] / floor,
                     "note": "per-lane select form (the ring slots the staged form parks the coarse branch in carry the conv's weights)"}
-# the routed pass 1's fetch split by what it is.  Dispatches of vq_assign_filter_kernel<256, 2, false, false>
+# the routed pass 1's fetch split by what it is.  Dispatches of vq_assign_filter_kernel<256, 2, false, false, true>
 # in tools/pmc_workload.py order: [0:4] the whole op (3), then [4:8] pass 1 alone (6), [8:12] codes only (7: no e-row gather), [12:16] codes only against K = 32 (8: one code tile)
-kf = find(fetch, "vq_assign_filter_kernel<256, 2, false, false>")
-kw = find(write, "vq_assign_filter_kernel<256, 2, false, false>")
+kf = find(fetch, "vq_assign_filter_kernel<256, 2, false, false, true>")
+kw = find(write, "vq_assign_filter_kernel<256, 2, false, false, true>")
 if kf is not None and len(fetch[kf]) >= 16:
     grp = lambda per, k, i: sum(per[k][4 * i + 1:4 * i + 4]) / 3.0 * 1024.0
     full, codes_only, k32 = (grp(fetch, kf, i) * factor for i in (1, 2, 3))

@@ -27,8 +27,8 @@ if has rocprof; then
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_configs -o t -- python3 $R/bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $O/trace_bench_configs.json 2>> $O/trace.err
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_entropy -o t -- python3 $R/tools/entropy_time.py > /dev/null 2>> $O/trace.err
   cd $R
-  python3 tools/rocprof_meta.py $O/trace_s1 $O/r06_bench_kernel_stats.csv routed weak "vq_assign_filter_kernel<256, 2, false, false>" | tee $O/rocprof_meta.log
-  python3 tools/rocprof_meta.py $O/trace_model $O/r06_bench_model_kernel_stats.csv model weak "vq_assign_filter_kernel<256, 1, true, false>" bench_kernel_stats.model.meta.json | tee -a $O/rocprof_meta.log
+  python3 tools/rocprof_meta.py $O/trace_s1 $O/r06_bench_kernel_stats.csv routed weak "vq_assign_filter_kernel<256, 2, false, false, true>" | tee $O/rocprof_meta.log
+  python3 tools/rocprof_meta.py $O/trace_model $O/r06_bench_model_kernel_stats.csv model weak "vq_assign_filter_kernel<256, 1, true, false, true>" bench_kernel_stats.model.meta.json | tee -a $O/rocprof_meta.log
   for p in configs entropy; do f=$(ls $O/trace_$p/*kernel_stats.csv $O/trace_$p/*/*kernel_stats.csv 2>/dev/null | head -1); [ -n "$f" ] && cp $f $O/r06_${p}_kernel_stats.csv; done
   bash tools/gate_trace.sh gpurun_out/r06/gate_trace > $O/gate_trace.txt 2>&1
 fi

@@ -62,7 +62,7 @@ torch.cuda.synchronize()
 pd = _CodebookPrep()
 s = 1e-3 * _pass1_ms(lambda: vq_assign_routed_dual(hc, hf, E, pd, entropy=ent, threshold=THR, mode=_lib.MODE_FILTER_PASS1,
                                                    out=(zq, codes, None, grain, cmask, gate)), pd, n=100)
-row("vq_assign_filter_kernel<256,2,false,false> (pass 1, select fused in, coarse branch through LDS)", "configs[2] B=256 K=1024", s, vq_bytes, vq_flops, F16,
+row("vq_assign_filter_kernel<256,2,false,false,true> (pass 1, select fused in, coarse branch through LDS)", "configs[2] B=256 K=1024", s, vq_bytes, vq_flops, F16,
     "the kernel alone (HIP events; workspace declared clean); VQ-forward byte count (the kernel also does the select's work); issue-bound code loop between two HBM-bound phases, at the socket's power cap (DESIGN 5.1)")
 from dynamicvectorquantization_amd import qconv as _qc
 _q, _ = np.linalg.qr(synth.normal(6012, (D, D), 0.0, 1.0).astype(np.float64))
@@ -72,11 +72,11 @@ with torch.no_grad():
 pc = _CodebookPrep()
 s = 1e-3 * _pass1_ms(lambda: vq_assign_routed_dual(hc, hf, E, pc, entropy=ent, threshold=THR, mode=_lib.MODE_FILTER_PASS1, conv=conv,
                                                    out=(zq, codes, None, grain, cmask, gate)), pc, n=100)
-row("vq_assign_filter_kernel<256,1,true,false> (pass 1 with the select AND the 1x1 quant_conv fused in: the model order)", "configs[2] B=256 K=1024", s, vq_bytes,
+row("vq_assign_filter_kernel<256,1,true,false,true> (pass 1 with the select AND the 1x1 quant_conv fused in: the model order)", "configs[2] B=256 K=1024", s, vq_bytes,
     vq_flops + 3 * 2.0 * D * D * N, F16, "flops incl. the conv's three split-fp16 terms")
 pdn = _CodebookPrep()
 s = 1e-3 * _pass1_ms(lambda: vq_assign(hf, E, pdn, cmask, mode=_lib.MODE_FILTER_PASS1, out=(zq, codes, None)), pdn, n=100)
-row("vq_assign_filter_kernel<256,0,false,false> (dense pass 1)", "B=256 K=1024", s, vq_bytes, vq_flops, F16, "the kernel alone")
+row("vq_assign_filter_kernel<256,0,false,false,true> (dense pass 1)", "B=256 K=1024", s, vq_bytes, vq_flops, F16, "the kernel alone")
 s_full = timeit(lambda: vq_assign(hf, E, prep, cmask, mode=_lib.MODE_FILTER, out=(zq, codes, loss)))
 row("dense filter op (pass 1 + resolver + list/finalize; no zero kernel in the steady state)", "B=256 K=1024", s_full, vq_bytes, vq_flops, F16)
 s = timeit(lambda: vq_assign(hf, E, prep, cmask, mode=_lib.MODE_EXACT, out=(zq, codes, loss)), n=10, warm=3)
