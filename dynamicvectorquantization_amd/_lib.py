@@ -52,6 +52,7 @@ EXPORTS = (
     "dvq_rq_embed_code_f32",
     "dvq_sample_head_f32", "dvq_sample_transfer_count_i64", "dvq_sample_transfer_fill_i64",
     "dvq_decode_table_bytes", "dvq_decode_table_prepare_f32", "dvq_decode_head_f32",
+    "dvq_vq_soft_assign_workspace_bytes", "dvq_vq_soft_assign_flat_f32",
 )
 
 
@@ -216,6 +217,10 @@ def _load():
     lib.dvq_decode_table_prepare_f32.argtypes = [vp, i32, i32, vp, vp, i32, vp, sz, vp]
     lib.dvq_decode_head_f32.restype = i32
     lib.dvq_decode_head_f32.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    lib.dvq_vq_soft_assign_workspace_bytes.restype = sz
+    lib.dvq_vq_soft_assign_workspace_bytes.argtypes = [i64, i32, i32]
+    lib.dvq_vq_soft_assign_flat_f32.restype = i32
+    lib.dvq_vq_soft_assign_flat_f32.argtypes = [vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp, vp, sz, vp]
     return lib
 
 

@@ -6,7 +6,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 1000   // 0.10.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1100   // 0.11.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -108,6 +108,8 @@ int dvq_launch_rq_backward(const float *g_out, const float *g_loss, int B, int h
                            const void *ws, float *g_x, hipStream_t st);
 int dvq_launch_rq_embed(const float *const *E, const int *K, int depth, const long long *codes, int B, int h, int w, int rH, int rW,
                         int Dl, int mode, int j, float *out, hipStream_t st);
+int dvq_launch_soft_assign(const float *x, const float *prep, int D, int K, long N, float temp, const float *q, float *soft,
+                           float *dist, float *sbuf, long long *codes, hipStream_t st);
 size_t dvq_qconv_prep_bytes_impl(int D);
 int dvq_launch_qconv_prep(const float *Wt, const float *bias, int D, void *prep, hipStream_t st);
 int dvq_launch_qconv(const float *x, const DvqRouted *rv, const void *prep, int D, int HW, long N, float *hout,
@@ -1163,6 +1165,34 @@ int dvq_decode_head_f32(const int64_t *codes, int B, int HW, const float *table,
     if ((((uintptr_t)h_in | (uintptr_t)pos_first | (uintptr_t)pos_second) & 3) != 0) { dvq_set_error("%s: misaligned float pointer", fn); return DVQ_EINVAL; }
     return hip_rc(dvq_launch_decode_head((const long long *)codes, B, HW, table, rows, C, pos_first, pos_second, h_in,
                                          (hipStream_t)stream), "decode_head");
+}
+
+// ---- fused soft code assignment (vq_soft.hip) ---------------------------------------------------------------------------
+size_t dvq_vq_soft_assign_workspace_bytes(int64_t N, int D, int K)
+{
+    if (N <= 0 || N >= ((int64_t)1 << 31) || K <= 0 || !dim_ok(D)) return 0;
+    return ((size_t)N * (size_t)K * sizeof(float) + 255) / 256 * 256;
+}
+
+int dvq_vq_soft_assign_flat_f32(const float *x, const float *codebook, const void *prep, int64_t N, int D, int K, float temp,
+                                const float *q, float *soft, float *dist, int64_t *codes, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_vq_soft_assign_flat_f32";
+    if (!x || !codebook || !prep || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (N <= 0 || N >= ((int64_t)1 << 31) || K <= 0) { dvq_set_error("%s: N=%lld K=%d out of range", fn, (long long)N, K); return DVQ_EINVAL; }
+    if (!(temp > 0.0f) || !(temp < __builtin_inff())) { dvq_set_error("%s: temp=%g must be finite and positive", fn, (double)temp); return DVQ_EINVAL; }
+    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    if ((size_t)N * (size_t)K >= ((size_t)1 << 40)) { dvq_set_error("%s: N * K too large", fn); return DVQ_EUNSUPPORTED; }
+    if ((((uintptr_t)x | (uintptr_t)q | (uintptr_t)soft | (uintptr_t)dist) & 3) != 0 || ((uintptr_t)prep & 255) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
+    float *sbuf = soft;
+    if (!soft && q) {                                            // the draw alone: the scores live in the workspace
+        const size_t need = dvq_vq_soft_assign_workspace_bytes(N, D, K);
+        if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes (soft == NULL with q)", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EINVAL; }
+        if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+        sbuf = (float *)ws;
+    }
+    return hip_rc(dvq_launch_soft_assign(x, (const float *)prep, D, K, (long)N, temp, q, soft, dist, sbuf, (long long *)codes,
+                                         (hipStream_t)stream), "vq_soft_assign");
 }
 
 }  // extern "C"

@@ -368,6 +368,54 @@ def vq_assign(z, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=T
     return zq, codes, loss
 
 
+def soft_assign(x, codebook, prep, temp=1.0, q=None, want_soft=True, want_dist=False):
+    """x [..., D] channel-last f32 cuda, codebook [K, D] -> (soft [..., K] or None, codes [...] i64, dist [..., K] or None), one
+    kernel (`dvq_vq_soft_assign_flat_f32`).
+
+    dist = the assign's distances bit for bit (fp32 FMA chain over k, ATen-order norms, fl(fl(xn + en) - 2 dot)); soft =
+    softmax((-dist) / temp) over the K codes (row max, expf, one fixed-order sum: the same bits every run).  codes: q None --
+    the first-index argmin, the code `vq_assign` returns; q [..., K] (Exp(1) variates drawn by the caller, e.g.
+    `torch.empty(N, K).exponential_(1)`) -- argmax of soft / q, first index on ties, which is what `torch.multinomial(soft, 1)`
+    computes from its own exponential_ draw.  want_soft=False with q: codes alone, the scores pass through a cached workspace.
+    Widths served by zero padding (_padded_width) run at the next kernel width, exactly."""
+    x = _lib.require_cuda_f32(x, "x")
+    codebook = _lib.require_cuda_f32(codebook, "codebook")
+    K, D = codebook.shape
+    if x.dim() < 1 or x.shape[-1] != D:
+        raise ValueError("last dim %s != codebook dim %d" % (tuple(x.shape[-1:]), D))
+    temp = float(temp)
+    if not (temp > 0.0 and math.isfinite(temp)):
+        raise ValueError("temp must be finite and positive, got %r" % temp)
+    lead = tuple(x.shape[:-1])
+    flat = x.reshape(-1, D)
+    N = flat.shape[0]
+    dev = x.device
+    if q is not None:
+        q = _lib.require_cuda_f32(q, "q")
+        if q.numel() != N * K:
+            raise ValueError("q has %d elements, expected N*K = %d" % (q.numel(), N * K))
+    soft = torch.empty(lead + (K,), dtype=torch.float32, device=dev) if want_soft else None
+    dist = torch.empty(lead + (K,), dtype=torch.float32, device=dev) if want_dist else None
+    codes = torch.empty(lead, dtype=torch.int64, device=dev)
+    if N == 0:
+        return soft, codes, dist
+    Dp = _padded_width(D)
+    if Dp != D:
+        xp = flat.new_zeros((N, Dp))
+        xp[:, :D] = flat
+        flat, codebook = xp, prep.padded_codebook(codebook, Dp)
+    with _lib.on_device(dev):
+        pbuf = prep.get(codebook)
+        ws_ptr, ws_bytes = 0, 0
+        if soft is None and q is not None:
+            ws = prep.workspace(N, Dp, 1, K, "soft", dev, nbytes=_lib_handle.dvq_vq_soft_assign_workspace_bytes(N, Dp, K))
+            ws_ptr, ws_bytes = ws.t.data_ptr(), ws.t.numel()
+        _lib.check(_lib_handle.dvq_vq_soft_assign_flat_f32(
+            flat.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(), N, Dp, K, temp, _lib.ptr(q), _lib.ptr(soft), _lib.ptr(dist),
+            codes.data_ptr(), ws_ptr, ws_bytes, _lib.stream_ptr(dev)), "dvq_vq_soft_assign_flat_f32")
+    return soft, codes, dist
+
+
 def _gate_for_routed(gate, G):
     """-> (tensor, gate_kind) for a router output [B, hc, wc, G] (f32 logits or int64)"""
     if not gate.is_cuda:
@@ -813,7 +861,21 @@ class _CodebookOps:
     @torch.no_grad()
     def get_soft_codes(self, x, temp=1.0, stochastic=False):
         """x [..., D] channel-last -> (softmax(-d / temp) over the K codes [..., K], hard code [...]):
-        a multinomial draw per token when `stochastic`, else the nearest code (quantize2_mask.py:193-205)."""
+        a multinomial draw per token when `stochastic`, else the nearest code (quantize2_mask.py:193-205).  f32 inputs on the
+        GPU: one `soft_assign` kernel on the assign's bit-exact distances; the draw takes its Exp(1) variates from torch's
+        generator exactly as torch.multinomial does, so torch.manual_seed governs it.  Anything else: the torch chain."""
+        cb = self.codebook
+        if x.is_cuda and x.dtype == torch.float32 and cb.weight.is_cuda and cb.weight.dtype == torch.float32:
+            if self.training:
+                cb._prep.invalidate()                    # training: optimizers / EMA may write through .data
+            cb._prep.track_users = self.training
+            q = None
+            if stochastic:
+                q = torch.empty(x.numel() // x.shape[-1], cb.n_embed, dtype=torch.float32, device=x.device).exponential_(1)
+            soft, code, _ = soft_assign(x, cb.codes, cb._prep, temp, q)
+            if self.training:
+                cb._prep.used(x.device)
+            return soft, code
         d = self.codebook.compute_distances(x)
         soft = torch.softmax(d / (-temp), dim=-1)
         if stochastic:

@@ -21,7 +21,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import _lib
-from .quantize import VQEmbedding, _padded_width, vq_assign
+from .quantize import VQEmbedding, _padded_width, soft_assign, vq_assign
 
 try:
     from collections.abc import Iterable
@@ -59,9 +59,9 @@ def _books(mod, depth):
     return [mod.codebooks[0] if mod.shared_codebook else mod.codebooks[i] for i in range(depth)]
 
 
-def _rq_forward(mod, x, want_grad, want_loss, training, on_depth=None):
-    """the per-depth loop of the module docstring -> (out, loss or None, codes, workspace).  `on_depth(i, r_i)` (get_soft_codes)
-    sees each residual right after its assign."""
+def _rq_forward(mod, x, want_grad, want_loss, training, assign=None):
+    """the per-depth loop of the module docstring -> (out, loss or None, codes, workspace).  `assign(i, codebook, r_i)` ->
+    codes [N] (get_soft_codes) replaces the hard assign of each depth."""
     g = _RQGeom(mod, x)
     x = _lib.require_cuda_f32(x, "x")
     dev = x.device
@@ -101,11 +101,12 @@ def _rq_forward(mod, x, want_grad, want_loss, training, on_depth=None):
             weight = cb.weight
             if not (weight.is_cuda and weight.dtype == torch.float32 and weight.is_contiguous()):
                 raise _lib.DvqError("RQBottleneck: codebook %d must be a contiguous f32 tensor on the GPU" % i)
-            vq_assign(r, weight[:-1], cb._prep, want_zq=False, want_loss=False, mode=mod.assign_mode, out=(None, c, None))
+            if assign is None:
+                vq_assign(r, weight[:-1], cb._prep, want_zq=False, want_loss=False, mode=mod.assign_mode, out=(None, c, None))
+            else:
+                c = assign(i, cb, r)
             if training:
                 cb._prep.used(dev)
-            if on_depth is not None:
-                on_depth(i, r)
             _lib.check(_lib_handle.dvq_rq_step_f32(
                 x.data_ptr(), r.data_ptr(), weight.data_ptr(), cb.n_embed, c.data_ptr(), *g.args(), i, depth, int(want_grad),
                 codes.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "dvq_rq_step_f32")
@@ -275,28 +276,23 @@ class RQBottleneck(nn.Module):
 
     @torch.no_grad()
     def get_soft_codes(self, x, temp=1.0, stochastic=False):
-        """(:372-400) -> (softmax(-dist / temp) per depth [B, h, w, d, K], codes [B, h, w, d]).  Distances of the soft codes
-        are a vendor GEMM at tolerance level (VQEmbedding.compute_distances).  Hard codes: the kernel chain's, equal to forward's
-        (eval); stochastic: a torch.multinomial draw per token on the residual chain, as the reference does it."""
-        depth = self.code_shape[-1]
-        books = _books(self, depth)
+        """(:372-400) -> (softmax(-dist / temp) per depth [B, h, w, d, K], codes [B, h, w, d]).  Per depth one `soft_assign`
+        on the residual (the assign's bit-exact distances, the softmax and the code in one kernel), then `dvq_rq_step_f32` with
+        that depth's code.  Hard codes: the first-index argmin, equal to forward's (eval); stochastic: argmax of soft / q with
+        q drawn per depth from torch's generator as torch.multinomial draws it, on the residual chain of the DRAWN codes, as
+        the reference does it."""
+        g = _RQGeom(self, x)
         soft = []
-        if not stochastic:
-            g = _RQGeom(self, x)
 
-            def keep(i, r):
-                d = books[i].compute_distances(r)
-                soft.append(F.softmax(-d / temp, dim=-1).reshape(g.B, g.h, g.w, 1, -1))
+        def assign(i, cb, r):
+            q = None
+            if stochastic:
+                q = torch.empty(g.N, cb.n_embed, dtype=torch.float32, device=r.device).exponential_(1)
+            s, code, _ = soft_assign(r, cb.weight[:-1], cb._prep, temp, q)
+            soft.append(s.reshape(g.B, g.h, g.w, 1, -1))
+            return code
 
-            codes = _rq_forward(self, x, False, False, False, on_depth=keep)[2]
-            return torch.cat(soft, dim=-2), codes
-        r = self.to_code_shape(x).detach().clone()
-        code_list = []
-        for cb in books:
-            d = cb.compute_distances(r)
-            s = F.softmax(-d / temp, dim=-1)
-            code = torch.multinomial(s.reshape(-1, s.shape[-1]), 1).reshape(*s.shape[:-1])
-            r -= cb.embed(code)
-            code_list.append(code.unsqueeze(-1))
-            soft.append(s.unsqueeze(-2))
-        return torch.cat(soft, dim=-2), torch.cat(code_list, dim=-1)
+        codes = _rq_forward(self, x, False, False, False, assign=assign)[2]
+        if not soft:                                  # empty batch
+            return x.new_zeros((g.B, g.h, g.w, g.depth, self.codebooks[0].n_embed)), codes
+        return torch.cat(soft, dim=-2), codes

@@ -28,6 +28,8 @@
  *     (quantize.py: _padded_width); divide the returned loss mean by D / D_padded.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.11.0 dvq_vq_soft_assign_workspace_bytes, dvq_vq_soft_assign_flat_f32 (new): get_soft_codes as one kernel -- the assign's
+ *          bit-exact distances, softmax(-d / temp), the hard code or the multinomial draw.  Nothing else changed.
  *   0.10.0 dvq_decode_table_bytes, dvq_decode_table_prepare_f32, dvq_decode_head_f32 (new): codes -> the input of the decoder's
  *          conv_in (codebook gather, post_quant_conv and the decoder's position biases as one kernel).  Nothing else changed.
  *   0.9.0  dvq_sample_head_f32, dvq_sample_transfer_count_i64, dvq_sample_transfer_fill_i64 (new): the sampling step and the
@@ -658,6 +660,36 @@ DVQ_API int dvq_decode_table_prepare_f32(const float *codebook, int rows, int D,
                                          const float *conv_bias, int C, void *table, size_t table_bytes, void *stream);
 DVQ_API int dvq_decode_head_f32(const int64_t *codes, int B, int HW, const float *table, int rows, int C,
                                 const float *pos_first, const float *pos_second, float *h_in, void *stream);
+
+/*
+ * Soft code assignment: distances, soft codes and the code of get_soft_codes in ONE kernel.
+ * Replaces: VQEmbedding.compute_distances (quantize2_mask.py:29-48), F.softmax(-distances / temp) and argmin /
+ *           torch.multinomial of VectorQuantize2.get_soft_codes (quantize2_mask.py:193-205) and, once per depth,
+ *           RQBottleneck.get_soft_codes (quantize_rqvae.py:372-400): four to six passes over a dense [N, K] matrix.
+ *   x        [N, D] row-major; codebook [>= K, D], prep from dvq_codebook_prepare_f32 of the SAME K rows
+ *   temp     finite, > 0
+ *   q        nullable [N, K]: caller-drawn Exp(1) variates (the convention of dvq_sample_head_f32)
+ *   soft     nullable [N, K]; dist nullable [N, K]; codes [N] int64
+ *   ws       only read when soft == NULL and q != NULL: >= dvq_vq_soft_assign_workspace_bytes(N, D, K) (the scores of the
+ *            draw pass through it), 256-byte aligned; NULL / 0 otherwise
+ * Per token n:
+ *   d[n, j]  = the assign's distance bit for bit: sequential-k fp32 FMA chain, ATen-order norms, fl(fl(xn + en) - 2 dot)
+ *   s[n, j]  = (-d[n, j]) / temp (IEEE division, the reference's `-distances / temp`)
+ *   soft     = softmax(s) over j: row max, expf, ONE fixed-order sum (accumulated in double), expf / sum -- deterministic:
+ *              two runs give the same bits; equal to torch's softmax of the same distances up to expf and summation order
+ *   codes[n] = q == NULL: the first-index argmin of d, NaN = minimum -- the code dvq_vq_assign_flat_f32 returns;
+ *              q given:   argmax_j soft[n, j] / q[n, j], the first index on ties (what torch.multinomial(soft, 1) computes from
+ *                         its own exponential_ draw); a NaN ratio never wins, every ratio NaN gives 0
+ * D in {64, 128, 256} (DVQ_EUNSUPPORTED otherwise; other widths by zero padding, as for the assign); K whatever
+ * dvq_codebook_prepare_f32 accepts; 1 <= N < 2^31, N * K < 2^40.  DVQ_EINVAL: null x / codebook / prep / codes, temp not
+ * finite or <= 0, a missing or too small workspace when one is needed.  Rows are read back with 16-byte accesses when
+ * K % 4 == 0 and soft, q, ws are 16-byte aligned, 4-byte ones otherwise: the same values.
+ * One launch, no host synchronisation, no allocation: capturable in a HIP graph.  Vector stores only.
+ */
+DVQ_API size_t dvq_vq_soft_assign_workspace_bytes(int64_t N, int D, int K);
+DVQ_API int dvq_vq_soft_assign_flat_f32(const float *x, const float *codebook, const void *prep, int64_t N, int D, int K,
+                                        float temp, const float *q, float *soft, float *dist, int64_t *codes,
+                                        void *ws, size_t ws_bytes, void *stream);
 
 /*
  * Wire format of the image-parallel exchange (one all-gather per batch; the reference gathers nothing --
