@@ -62,7 +62,7 @@ class DvqError(RuntimeError):
 
 def build(force=False):
     """Compile csrc/*.hip for gfx950 with hipcc (csrc/Makefile) into csrc/libdvq.so."""
-    args = ["make", "-C", CSRC, "-j4"]
+    args = ["make", "-C", CSRC, "-j8"]
     if force:
         args.append("-B")
     subprocess.check_call(args, stdout=subprocess.DEVNULL)

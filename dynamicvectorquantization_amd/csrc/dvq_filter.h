@@ -1,5 +1,5 @@
-// dvq_filter.h -- declarations shared by the fp16-filter assign kernels (vq_assign_filter.hip: pass 1,
-// resolver), the conv-folded codebook (vq_fold.hip), the routing prepass of the exact routed mode (vq_assign_routed.hip), the 1x1 conv with the select
+// dvq_filter.h -- declarations shared by the fp16-filter assign kernels (dvq_pass1.h: pass 1; vq_resolve.hip:
+// the resolver), the conv-folded codebook (vq_fold.hip), the routing prepass of the exact routed mode (vq_assign_routed.hip), the 1x1 conv with the select
 // fused in (qconv.hip) and the exact kernel's routed list mode (vq_assign_exact.hip).
 #pragma once
 #include "dvq_common.h"

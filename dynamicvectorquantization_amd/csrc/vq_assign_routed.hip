@@ -3,7 +3,7 @@
 // Routed assign (dvq_vq_assign_routed_{dual,triple}_f32): the routing tail of the reference encoders
 // (EncoderDual.py:134-149, EncoderTriple.py:148-176) and VectorQuantize2.forward
 // (quantize2_mask.py:157-191) as ONE op that never materialises h_dual / h_triple.  In DVQ_MODE_FILTER the select
-// is fused into pass 1 (vq_assign_filter.hip), which derives every position's grain from the gate and writes the
+// is fused into pass 1 (dvq_pass1.h), which derives every position's grain from the gate and writes the
 // by-products itself.  DVQ_MODE_EXACT scores every position with the exact kernel, which re-derives a position's
 // source from `indices`; this prepass writes them first:
 //   routed_prepass_kernel   one workgroup per image: argmax of the gate (or entropy > threshold) per coarse cell

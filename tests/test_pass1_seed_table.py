@@ -1,5 +1,5 @@
 """GPU (-m gpu): pass 1's accumulator seeds come from a table resident in LDS when a workgroup's code tiles fit it (K <= 1024, or a
-slice that small of the split form) and travel with every tile otherwise (csrc/vq_assign_filter.hip, pass1_body RES).  The seeds
+slice that small of the split form) and travel with every tile otherwise (csrc/dvq_pass1.h, pass1_body RES).  The seeds
 are the same fp32 values read from another address, so every form of pass 1 must still give the oracle's bits on both sides of
 the limit: K = 32 (one tile), K not a multiple of 32, K = 1024 (the table exactly fills the seeds area), K = 1056 / 2048 below
 131 072 tokens (the per-tile form must be taken and be right).  Ops: routed dual / triple (staged select), dense (cached / plain),

@@ -6,7 +6,8 @@ k-step g are loaded with `asm volatile("global_load_dword ... nt")` three k-step
 s_waitcnt; hipcc believes the destination registers are defined at the asm statement, so nothing it schedules between the load and
 its covering wait may read, copy, spill or overwrite them.  The 8 loads of group g are covered by the (g + 1)-th vmcnt wait after
 the first load (compiler-inserted waits in between only make the counted ones stricter).  Run by __graft_entry__.build().
-  python tools/isa_hazard_check.py [file.s]      (without an argument: compiles csrc/vq_assign_filter.hip to gfx950 assembly first)"""
+  python tools/isa_hazard_check.py [file.s]      (without an argument: compiles the two D = 256 pass-1 units, csrc/vq_pass1_d256.hip and
+                                                  csrc/vq_pass1_d256_res.hip, which hold these kernels, to gfx950 assembly first)"""
 import os
 import re
 import subprocess
@@ -17,9 +18,17 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def assemble(out_path):
-    src = os.path.join(ROOT, "dynamicvectorquantization_amd", "csrc", "vq_assign_filter.hip")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
-                           "--cuda-device-only", "-S", "-o", out_path, src], stderr=subprocess.DEVNULL)
+    """the assembly of both units, one behind the other, in out_path (the two compiles run side by side)"""
+    units = ["vq_pass1_d256.hip", "vq_pass1_d256_res.hip"]
+    procs = [subprocess.Popen(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
+                               "--cuda-device-only", "-S", "-o", out_path + "." + u,
+                               os.path.join(ROOT, "dynamicvectorquantization_amd", "csrc", u)], stderr=subprocess.DEVNULL) for u in units]
+    for u, p in zip(units, procs):
+        if p.wait() != 0:
+            raise subprocess.CalledProcessError(p.returncode, p.args)
+    with open(out_path, "w") as out:
+        for u in units:
+            out.write(open(out_path + "." + u).read())
 
 
 def regs(tok):
@@ -81,7 +90,7 @@ def main():
         rep = check(sys.argv[1])
     else:
         with tempfile.TemporaryDirectory() as td:
-            p = os.path.join(td, "vq_assign_filter.s")
+            p = os.path.join(td, "vq_pass1_d256.s")
             assemble(p)
             rep = check(p)
     for name, bad, okc in rep:

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel register / spill / LDS table of one csrc/*.hip file, from hipcc -Rpass-analysis=kernel-resource-usage.
-usage: tools/kernel_resources.py vq_assign_filter.hip [substring ...]"""
+usage: tools/kernel_resources.py vq_pass1_d256_res.hip [substring ...]"""
 import os
 import re
 import subprocess

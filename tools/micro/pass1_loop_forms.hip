@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256, FORM == 0 ? 2 : 1) void loop_kernel(const char
 
 #define RD(dst, S) asm volatile("ds_read_b128 %0, %1 offset:%c2" : "=v"(dst) : "v"(tile_a), "i"((S) * 1024))
     if constexpr (FORM == 0) {
-        // ---- A: the product loop (vq_assign_filter.hip), 32 tokens per wave
+        // ---- A: the product loop (dvq_pass1.h), 32 tokens per wave
         float b1[2] = {-__builtin_inff(), -__builtin_inff()}, b2[2] = {-__builtin_inff(), -__builtin_inff()};
         int bt[2] = {0, 0};
         f32x4 acc[2][2];
