@@ -33,6 +33,7 @@ ACT_NONE, ACT_SILU, ACT_RELU = 0, 1, 2
 SAMPLE_MAX_V = 8192     # the sampling head's vocabulary limit (include/dvq.h: dvq_sample_head_f32)
 TRANSFER_SAMPLED, TRANSFER_REMAIN = 0, 1
 TRANSFER_SOS_NONE, TRANSFER_SOS_CONST, TRANSFER_SOS_COPY = 0, 1, 2
+METRIC_L2, METRIC_DOT = 0, 1   # dvq_vq_score_assign_f32: s = -distance / s = dot product
 
 EXPORTS = (
     "dvq_version", "dvq_last_error_string", "dvq_codebook_prep_bytes", "dvq_codebook_prepare_f32",
@@ -53,6 +54,7 @@ EXPORTS = (
     "dvq_sample_head_f32", "dvq_sample_transfer_count_i64", "dvq_sample_transfer_fill_i64",
     "dvq_decode_table_bytes", "dvq_decode_table_prepare_f32", "dvq_decode_head_f32",
     "dvq_vq_soft_assign_workspace_bytes", "dvq_vq_soft_assign_flat_f32",
+    "dvq_vq_score_assign_f32", "dvq_vq_apply_codes_nchw_f32", "dvq_vq_apply_codes_flat_f32",
 )
 
 
@@ -221,6 +223,12 @@ def _load():
     lib.dvq_vq_soft_assign_workspace_bytes.argtypes = [i64, i32, i32]
     lib.dvq_vq_soft_assign_flat_f32.restype = i32
     lib.dvq_vq_soft_assign_flat_f32.argtypes = [vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp, vp, sz, vp]
+    lib.dvq_vq_score_assign_f32.restype = i32
+    lib.dvq_vq_score_assign_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, vp]
+    lib.dvq_vq_apply_codes_nchw_f32.restype = i32
+    lib.dvq_vq_apply_codes_nchw_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, sz, vp]
+    lib.dvq_vq_apply_codes_flat_f32.restype = i32
+    lib.dvq_vq_apply_codes_flat_f32.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, sz, vp]
     return lib
 
 

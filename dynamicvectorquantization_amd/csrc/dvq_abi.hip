@@ -6,7 +6,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 1100   // 0.11.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1200   // 0.12.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -110,6 +110,11 @@ int dvq_launch_rq_embed(const float *const *E, const int *K, int depth, const lo
                         int Dl, int mode, int j, float *out, hipStream_t st);
 int dvq_launch_soft_assign(const float *x, const float *prep, int D, int K, long N, float temp, const float *q, float *soft,
                            float *dist, float *sbuf, long long *codes, hipStream_t st);
+int dvq_launch_score_assign(const float *z, const float *prep, int D, int HW, int K, long N, int metric, float temp, const float *u,
+                            long long *codes, hipStream_t st);
+int dvq_apply_codes_blocks(long N);
+int dvq_launch_apply_codes(const float *z, const float *E, const long long *codes, const float *mask, int D, int HW, int K, long N,
+                           float *zq, double *partials, hipStream_t st);
 size_t dvq_qconv_prep_bytes_impl(int D);
 int dvq_launch_qconv_prep(const float *Wt, const float *bias, int D, void *prep, hipStream_t st);
 int dvq_launch_qconv(const float *x, const DvqRouted *rv, const void *prep, int D, int HW, long N, float *hout,
@@ -1193,6 +1198,61 @@ int dvq_vq_soft_assign_flat_f32(const float *x, const float *codebook, const voi
     }
     return hip_rc(dvq_launch_soft_assign(x, (const float *)prep, D, K, (long)N, temp, q, soft, dist, sbuf, (long long *)codes,
                                          (hipStream_t)stream), "vq_soft_assign");
+}
+
+// ---- scored / sampled assign and quantisation from given codes (vq_sample.hip) ---------------------------------------------
+int dvq_vq_score_assign_f32(const float *x, const void *prep, int B, int D, int HW, int K, int metric, float temp,
+                            const float *u, int64_t u_numel, int64_t *codes, void *stream)
+{
+    const char *fn = "dvq_vq_score_assign_f32";
+    if (!x || !prep || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
+    if (metric != DVQ_METRIC_L2 && metric != DVQ_METRIC_DOT) { dvq_set_error("%s: unknown metric %d", fn, metric); return DVQ_EINVAL; }
+    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    const size_t N = (size_t)B * (size_t)HW;
+    if (N >= ((size_t)1 << 31) || N * (size_t)D >= ((size_t)1 << 40) || N * (size_t)K >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if ((((uintptr_t)x | (uintptr_t)u) & 3) != 0 || ((uintptr_t)prep & 255) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
+    if (u) {
+        if (!(temp > 0.0f) || !(temp < __builtin_inff())) { dvq_set_error("%s: temp=%g must be finite and positive when u is given", fn, (double)temp); return DVQ_EINVAL; }
+        if (u_numel < 0 || (size_t)u_numel != N * (size_t)K) { dvq_set_error("%s: u has %lld elements, expected N * K = %zu", fn, (long long)u_numel, N * (size_t)K); return DVQ_EINVAL; }
+    }
+    return hip_rc(dvq_launch_score_assign(x, (const float *)prep, D, HW, K, (long)N, metric, temp, u, (long long *)codes,
+                                          (hipStream_t)stream), "vq_score_assign");
+}
+
+int dvq_vq_apply_codes_nchw_f32(const float *z, const int64_t *codes, const float *codebook, const float *mask, int B, int D, int HW,
+                                int K, float beta, float *zq, float *loss, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_vq_apply_codes_nchw_f32";
+    if (!z || !codes || !codebook) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
+    if (D <= 0 || D % 16 != 0) { dvq_set_error("%s: D=%d must be a positive multiple of 16", fn, D); return DVQ_EUNSUPPORTED; }
+    const size_t N = (size_t)B * (size_t)HW;
+    if (N >= ((size_t)1 << 31) || N * (size_t)D >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if ((((uintptr_t)z | (uintptr_t)zq | (uintptr_t)mask) & 3) != 0 || ((uintptr_t)codebook & 15) != 0 || ((uintptr_t)codes & 7) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
+    if (!zq && !loss) { dvq_set_error("%s: nothing to compute (zq and loss are both null)", fn); return DVQ_EINVAL; }
+    double *partials = nullptr;
+    if (loss) {
+        const size_t need = dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_EXACT);
+        if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EWORKSPACE; }
+        if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+        partials = (double *)ws;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc = dvq_launch_apply_codes(z, codebook, (const long long *)codes, mask, D, HW, K, (long)N, zq, partials, st);
+    if (rc) return hip_rc(rc, "vq_apply_codes");
+    if (loss) {
+        rc = dvq_launch_loss_finalize(partials, dvq_apply_codes_blocks((long)N), 1.0 / ((double)N * D), beta, loss, st);
+        if (rc) return hip_rc(rc, "vq_loss_finalize");
+    }
+    return DVQ_OK;
+}
+
+int dvq_vq_apply_codes_flat_f32(const float *z, const int64_t *codes, const float *codebook, const float *mask, int64_t N, int D,
+                                int K, float beta, float *zq, float *loss, void *ws, size_t ws_bytes, void *stream)
+{
+    if (N <= 0 || N >= ((int64_t)1 << 31)) { dvq_set_error("dvq_vq_apply_codes_flat_f32: N=%lld out of range", (long long)N); return DVQ_EINVAL; }
+    return dvq_vq_apply_codes_nchw_f32(z, codes, codebook, mask, (int)N, D, 1, K, beta, zq, loss, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

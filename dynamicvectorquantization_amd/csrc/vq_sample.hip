@@ -1,0 +1,284 @@
+// vq_sample.hip -- scored / temperature-sampled code assignment and quantisation from given codes (gfx950): the learnable-codebook
+// quantizers MaskVectorQuantize / VectorQuantize.
+//
+// Replaces (reference modules/vector_quantization/quantize_codebook_mask.py:97-121, quantize.py:92-119, common_utils.py:19-35):
+// the [N, K] score matrix `dist` (L2: -sum x^2 - sum e^2 + 2 x E^T; cosine similarity: x_n E_n^T), `dist / temp`, the uniform
+// noise's two logs and two clamps, the add and the argmax -- about ten passes over N x K floats -- by ONE sweep that reads the
+// caller-drawn uniforms once and writes N codes; then the embedding gather, the (masked) loss and the straight-through add by one
+// streaming kernel.
+//
+// vq_score_assign_kernel: the tile loop is vq_assign_exact.hip's (and vq_soft.hip's: the same D/2 chained v_mfma_f32_32x32x2_f32 per
+// 32-code tile, the reference's sequential-k fp32 FMA chain, so every dot is the same bits): a wave keeps its 32 tokens' D channels in
+// registers -- read in place from NCHW [B, D, HW], or from row-major [N, D] as the case HW == 1 -- and the codebook streams through
+// LDS as the prepared tile images (double-buffered global -> LDS DMA, one barrier per tile).  MFMA rows = 32 codes, columns = 32
+// tokens: lane (c, h) holds token c and, per tile, the 16 codes 32 t + 8 g + 4 h + {0..3}, g < 4 -- four runs of four consecutive
+// codes, which is what lets a lane fetch its 16 uniforms of the tile as four 16-byte loads of row c of u, issued before the MFMA
+// chain that hides them, and keeps the running argmax lane-local (the two lane halves are merged once, after the loop).
+//   score   L2:  s = -d, d = fl(fl(xn + en) - 2 dot) (ATen-order norms): the reference's expression negated, bit for bit
+//           DOT: s = dot (operands L2-normalised by the caller)
+//   u == nullptr: code = argmax s;  u given: code = argmax fl(fl(s / temp) + g), g = -logf(max(-logf(max(u, 1e-20f)), 1e-20f))
+//   argmax with torch's rules: the first index among equal maxima, a NaN is the maximum and the first NaN wins.
+// Nothing of size N x K is written; no workspace; no atomics.
+//
+// vq_apply_codes_kernel: z_q = fl(z + fl(e - z)) and the loss partial sum((e - z)^2 m) of given codes, the arithmetic of the exact
+// assign's tail (vq_assign_exact.hip) in the streaming form of vq_backward.hip; double partials, one per workgroup, finalised in a
+// fixed order by vq_loss_finalize_kernel.
+#include "dvq_common.h"
+
+#define DVQ_METRIC_L2_ 0
+#define DVQ_METRIC_DOT_ 1
+
+// torch argmax step over candidates visited in ascending index: take if v > best, or v is NaN and best is not
+__device__ __forceinline__ bool argmax_take(float v, float best)
+{
+    return !(v <= best) && (best == best);
+}
+
+// merge two (value, index) candidates of disjoint ascending scans
+__device__ __forceinline__ void argmax_merge(float &v, int &i, float v2, int i2)
+{
+    const bool n1 = v != v, n2 = v2 != v2;
+    bool other;
+    if (n1 || n2)
+        other = n2 && (!n1 || i2 < i);
+    else
+        other = (v2 > v) || (v2 == v && i2 < i);
+    if (other) { v = v2; i = i2; }
+}
+
+// the reference's gumbel_noise of one uniform (common_utils.py:19-29): -log(clamp(-log(clamp(u, 1e-20)), 1e-20))
+__device__ __forceinline__ float gumbel_of(float u)
+{
+    const float a = -logf(fmaxf(u, 1e-20f));
+    return -logf(fmaxf(a, 1e-20f));
+}
+
+// NOISE: u [N, K] given.  VEC: K % 4 == 0 and u 16-byte aligned -- a lane's four codes of a run sit in one aligned 16-byte piece.
+template <int D, int METRIC, bool NOISE, bool VEC>
+__global__ __launch_bounds__(256, 2) void vq_score_assign_kernel(
+    const float *__restrict__ z, const float *__restrict__ tiles, int HW, int K, long N, float temp,
+    const float *__restrict__ u, long long *__restrict__ codes)
+{
+    constexpr int S = D / 2;                         // MFMA steps (2 k each)
+    constexpr int TILE_FLOATS = 32 * D + 64;
+    constexpr int CHUNKS_PER_WAVE = (32 * D * 4 / 1024) / 4;   // 1-KiB DMA pieces per wave per tile
+    extern __shared__ __attribute__((aligned(16))) float lds[];   // 2 * TILE_FLOATS
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int c = lane & 31, h = lane >> 5;
+    const long n = ((long)blockIdx.x * 4 + wave) * 32 + c;
+    const bool valid = n < N;
+    const long nn = valid ? n : N - 1;               // lanes past the end re-read the last token; they store nothing
+    const long b = nn / HW;
+    const float *zp = z + ((size_t)b * D + h) * HW + (size_t)(nn - b * HW);   // channel k = 2s + h at zp + 2s HW
+
+    float zr[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) zr[s] = zp[(size_t)2 * s * HW];
+
+    auto stage = [&](int t, float *buf) {
+        const char *src = (const char *)(tiles + (size_t)t * TILE_FLOATS);
+#pragma unroll
+        for (int i = 0; i < CHUNKS_PER_WAVE; ++i) {
+            int chunk = wave * CHUNKS_PER_WAVE + i;
+            glds16(src + chunk * 1024 + lane * 16, (char *)buf + chunk * 1024);
+        }
+        if (wave == 0) glds4(src + 32 * D * 4 + lane * 4, (char *)buf + 32 * D * 4);
+    };
+
+    const int T = dvq_num_tiles(K);
+    stage(0, lds);
+
+    // ---- xn: ATen-order sum of squares of this token (vq_assign_exact.hip); the DOT metric has no norms
+    float xn = 0.0f;
+    if constexpr (METRIC == DVQ_METRIC_L2_) {
+        float p[16], o[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) {
+            float a = sq_rn(zr[q]);
+#pragma unroll
+            for (int j = 1; j < S / 16; ++j) a = __fadd_rn(a, sq_rn(zr[q + 16 * j]));
+            p[q] = a;
+        }
+#pragma unroll
+        for (int q = 0; q < 16; ++q) o[q] = __shfl_xor(p[q], 32);
+        float tl[8];
+#pragma unroll
+        for (int l = 0; l < 8; ++l) {
+            float a4[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                int m = l + 8 * g;
+                float mine = p[m >> 1], other = o[m >> 1];
+                a4[g] = ((m & 1) == h) ? mine : other;
+            }
+            tl[l] = __fadd_rn(__fadd_rn(__fadd_rn(a4[0], a4[1]), a4[2]), a4[3]);
+        }
+        xn = tl[0];
+#pragma unroll
+        for (int l = 1; l < 8; ++l) xn = __fadd_rn(xn, tl[l]);
+    }
+
+    float best = -__builtin_inff();
+    int bidx = 0x7fffffff;
+    const float *urow = NOISE ? u + (size_t)nn * (size_t)K : nullptr;
+
+    for (int t = 0; t < T; ++t) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                      // tile t landed; everyone is done with tile t-1
+        float *buf = lds + (t & 1) * TILE_FLOATS;
+
+        // this tile's uniforms of the lane's token: in flight under the MFMA chain
+        float uu[16];
+        if constexpr (NOISE) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int code0 = t * 32 + 8 * g + 4 * h;
+                if constexpr (VEC) {
+                    f32x4 v = {0.5f, 0.5f, 0.5f, 0.5f};
+                    if (code0 < K) v = __builtin_nontemporal_load((const f32x4 *)(urow + code0));     // K % 4 == 0: all four < K
+                    uu[4 * g + 0] = v[0]; uu[4 * g + 1] = v[1]; uu[4 * g + 2] = v[2]; uu[4 * g + 3] = v[3];
+                } else {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        uu[4 * g + q] = (code0 + q < K) ? __builtin_nontemporal_load(urow + code0 + q) : 0.5f;
+                }
+            }
+        }
+        if (t + 1 < T) stage(t + 1, lds + ((t + 1) & 1) * TILE_FLOATS);
+
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        const float *ap = buf + c * 8 + h * 4;
+#pragma unroll
+        for (int kg = 0; kg < D / 8; ++kg) {
+            f32x4 a = *(const f32x4 *)(ap + kg * 256);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], zr[kg * 4 + 0], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], zr[kg * 4 + 1], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], zr[kg * 4 + 2], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], zr[kg * 4 + 3], acc, 0, 0, 0);
+        }
+        const float *entile = buf + 32 * D + 4 * h;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 en4 = {0.0f, 0.0f, 0.0f, 0.0f};
+            if constexpr (METRIC == DVQ_METRIC_L2_) en4 = *(const f32x4 *)(entile + 8 * g);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int r = g * 4 + q;
+                const int code = t * 32 + q + 8 * g + 4 * h;
+                float s;
+                if constexpr (METRIC == DVQ_METRIC_L2_) {
+                    const float bias = __fadd_rn(xn, en4[q]);
+                    s = -__builtin_fmaf(-2.0f, acc[r], bias);    // -(fl(bias - 2 dot)), 2 dot exact
+                } else {
+                    s = acc[r];
+                }
+                if constexpr (NOISE) s = __fadd_rn(s / temp, gumbel_of(uu[r]));
+                const bool take = argmax_take(s, best) && (code < K);
+                best = take ? s : best;
+                bidx = take ? code : bidx;
+            }
+        }
+    }
+
+    {   // merge the two lane halves of each token
+        const float ob = __shfl_xor(best, 32);
+        const int oi = __shfl_xor(bidx, 32);
+        argmax_merge(best, bidx, ob, oi);
+    }
+    if (valid && h == 0) codes[n] = (long long)(bidx == 0x7fffffff ? 0 : bidx);    // every score -inf -> index 0
+}
+
+template <int D, int METRIC>
+static int launch_score(const float *z, const float *tiles, int HW, int K, long N, float temp, const float *u, long long *codes,
+                        int vec, hipStream_t st)
+{
+    const size_t shmem = 2 * (32 * D + 64) * sizeof(float);
+    const dim3 grid((unsigned)((N + 127) / 128)), block(256);
+    if (u == nullptr)
+        return dvq_launch_lds<vq_score_assign_kernel<D, METRIC, false, false>>(grid, block, shmem, st, z, tiles, HW, K, N, temp, u, codes);
+    if (vec)
+        return dvq_launch_lds<vq_score_assign_kernel<D, METRIC, true, true>>(grid, block, shmem, st, z, tiles, HW, K, N, temp, u, codes);
+    return dvq_launch_lds<vq_score_assign_kernel<D, METRIC, true, false>>(grid, block, shmem, st, z, tiles, HW, K, N, temp, u, codes);
+}
+
+// z [B, D, HW] (HW == 1: row-major [N, D]); prep: the f32 tile images; u nullable [N, K]
+int dvq_launch_score_assign(const float *z, const float *prep, int D, int HW, int K, long N, int metric, float temp, const float *u,
+                            long long *codes, hipStream_t st)
+{
+    const int vec = (K % 4 == 0) && ((uintptr_t)u & 15) == 0;     // 16-byte pieces of a row of u: every row start aligned
+    const bool dot = metric == DVQ_METRIC_DOT_;
+    switch (D) {
+    case 64:  return dot ? launch_score<64, DVQ_METRIC_DOT_>(z, prep, HW, K, N, temp, u, codes, vec, st)
+                         : launch_score<64, DVQ_METRIC_L2_>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 128: return dot ? launch_score<128, DVQ_METRIC_DOT_>(z, prep, HW, K, N, temp, u, codes, vec, st)
+                         : launch_score<128, DVQ_METRIC_L2_>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 256: return dot ? launch_score<256, DVQ_METRIC_DOT_>(z, prep, HW, K, N, temp, u, codes, vec, st)
+                         : launch_score<256, DVQ_METRIC_L2_>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    default:  return -1000;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------
+// quantise from given codes: z_q = z + (e - z), loss partials
+// ---------------------------------------------------------------------------------------------
+// Mapping as vq_backward.hip: a wave owns 32 consecutive tokens, lane = (token, half); per step of 16 channels a lane handles 8
+// (two 16-byte gathers of its code's row, 8 loads / stores whose wave instructions cover 128-byte runs of NCHW).  A code outside
+// [0, K) leaves its token unquantised (z_q = z) and adds nothing to the loss.
+__global__ __launch_bounds__(256) void vq_apply_codes_kernel(
+    const float *__restrict__ z, const float *__restrict__ E, const long long *__restrict__ codes,
+    const float *__restrict__ mask, int D, int HW, int K, long N, float *__restrict__ zq, double *__restrict__ partials)
+{
+    __shared__ double red[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int c = lane & 31, h = lane >> 5;
+    const long n = ((long)blockIdx.x * 4 + wave) * 32 + c;
+    float lsum = 0.0f;
+    if (n < N) {
+        const long b = n / HW;
+        const int hw = (int)(n - b * HW);
+        const size_t base = ((size_t)b * D + 8 * h) * HW + hw;
+        const long long cj = codes[n];
+        const bool ok = cj >= 0 && cj < K;
+        const float *ep = E + (size_t)(ok ? cj : 0) * D + 8 * h;
+        const float m = (mask != nullptr) ? mask[n] : 1.0f;
+        const float *zp = z + base;
+        float *op = (zq != nullptr) ? zq + base : nullptr;
+        const int S16 = D / 16;
+#pragma unroll 2
+        for (int s = 0; s < S16; ++s) {
+            const f32x4 e0 = *(const f32x4 *)(ep + 16 * s), e1 = *(const f32x4 *)(ep + 16 * s + 4);
+            float zz[8];
+#pragma unroll
+            for (int j = 0; j < 8; ++j) zz[j] = __builtin_nontemporal_load(zp + (size_t)(16 * s + j) * HW);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float e = (j < 4) ? e0[j & 3] : e1[j & 3];
+                const float diff = ok ? __fsub_rn(e, zz[j]) : 0.0f;
+                if (op != nullptr) __builtin_nontemporal_store(__fadd_rn(zz[j], diff), op + (size_t)(16 * s + j) * HW);
+                lsum = __fadd_rn(lsum, __fmul_rn(__fmul_rn(diff, diff), m));
+            }
+        }
+    }
+    if (partials != nullptr) {                   // (uniform: a kernel argument)
+        double ds = (double)lsum;
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) ds += __shfl_xor(ds, off);
+        if (lane == 0) red[wave] = ds;
+        __syncthreads();
+        if (threadIdx.x == 0) partials[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+    }
+}
+
+int dvq_apply_codes_blocks(long N) { return (int)((N + 127) / 128); }
+
+int dvq_launch_apply_codes(const float *z, const float *E, const long long *codes, const float *mask, int D, int HW, int K, long N,
+                           float *zq, double *partials, hipStream_t st)
+{
+    hipLaunchKernelGGL(vq_apply_codes_kernel, dim3((unsigned)dvq_apply_codes_blocks(N)), dim3(256), 0, st, z, E, codes, mask, D, HW,
+                       K, N, zq, partials);
+    return (int)hipGetLastError();
+}

@@ -416,6 +416,102 @@ def soft_assign(x, codebook, prep, temp=1.0, q=None, want_soft=True, want_dist=F
     return soft, codes, dist
 
 
+def _pad_channels(z, Dp):
+    """z [B, D, *spatial] -> [B, Dp, *spatial] with zero channels appended (_padded_width)"""
+    zp = z.new_zeros((z.shape[0], Dp) + tuple(z.shape[2:]))
+    zp[:, :z.shape[1]] = z
+    return zp
+
+
+def score_assign(x, codebook, prep, metric=_lib.METRIC_L2, temp=0.0, u=None):
+    """x [B, D, *spatial] f32 cuda read in place (NCHW; [N, D] is the row-major case), codebook [K, D] -> codes [B, *spatial] i64,
+    one kernel (`dvq_vq_score_assign_f32`).
+
+    Score of token n against code j: METRIC_L2 -- minus the assign's distance, bit for bit the reference's
+    `-sum x^2 - sum e^2 + 2 x E^T`; METRIC_DOT -- the dot product (same fp32 FMA chain; pass L2-normalised operands for the cosine
+    similarity).  u None: codes = argmax of the scores.  u [N, K] (uniforms drawn by the caller with
+    `torch.zeros(N, K).uniform_(0, 1)`, the reference's own draw) and temp > 0: codes = argmax(score / temp + gumbel(u)), which is
+    `common_utils.gumbel_sample(dist, temperature=temp)`.  torch.argmax's rules: first index on ties, NaN is the maximum.  Nothing of
+    size N x K is written.  Widths served by zero padding (_padded_width) run at the next kernel width, exactly."""
+    x = _lib.require_cuda_f32(x, "x")
+    codebook = _lib.require_cuda_f32(codebook, "codebook")
+    K, D = codebook.shape
+    if x.dim() < 2 or x.shape[1] != D:
+        raise ValueError("x must be [B, %d, ...] (channel dim %s != codebook dim %d)" % (D, tuple(x.shape[1:2]), D))
+    if metric not in (_lib.METRIC_L2, _lib.METRIC_DOT):
+        raise ValueError("unknown metric %r" % (metric,))
+    temp = float(temp)
+    B = x.shape[0]
+    HW = 1
+    for sdim in x.shape[2:]:
+        HW *= sdim
+    dev = x.device
+    u_numel = 0
+    if u is not None:
+        if not (temp > 0.0 and math.isfinite(temp)):
+            raise ValueError("temp must be finite and positive when u is given, got %r" % temp)
+        u = _lib.require_cuda_f32(u, "u")
+        u_numel = u.numel()
+    codes = torch.empty((B,) + tuple(x.shape[2:]), dtype=torch.int64, device=dev)
+    if B * HW == 0:
+        return codes
+    Dp = _padded_width(D)
+    if Dp != D:
+        x, codebook = _pad_channels(x, Dp), prep.padded_codebook(codebook, Dp)
+    with _lib.on_device(dev):
+        pbuf = prep.get(codebook)
+        _lib.check(_lib_handle.dvq_vq_score_assign_f32(
+            x.data_ptr(), pbuf.data_ptr(), B, Dp, HW, K, int(metric), temp, _lib.ptr(u), u_numel, codes.data_ptr(),
+            _lib.stream_ptr(dev)), "dvq_vq_score_assign_f32")
+    return codes
+
+
+def apply_codes(z, codes, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=True):
+    """quantise z [B, D, *spatial] ([N, D]: row-major) with GIVEN codes [B, *spatial] -> (zq or None, loss[2] or None), one
+    streaming kernel (`dvq_vq_apply_codes_nchw_f32` / `_flat_f32`): zq = z + (e - z) with e = codebook[codes], loss[0] =
+    mean((e - z)^2 * mask), loss[1] = beta * mean + mean.  Fed the codes `vq_assign` returns, zq is bit-identical to vq_assign's
+    and the loss agrees within 1e-5 relative.  `prep` only lends its per-stream workspace (the loss partials)."""
+    z = _lib.require_cuda_f32(z, "z")
+    codebook = _lib.require_cuda_f32(codebook, "codebook")
+    K, D = codebook.shape
+    if z.dim() < 2 or z.shape[1] != D:
+        raise ValueError("z must be [B, %d, ...] (channel dim %s != codebook dim %d)" % (D, tuple(z.shape[1:2]), D))
+    B = z.shape[0]
+    HW = 1
+    for sdim in z.shape[2:]:
+        HW *= sdim
+    if not codes.is_cuda or codes.dtype != torch.int64 or codes.numel() != B * HW:
+        raise ValueError("codes must be an int64 GPU tensor of B*H*W = %d elements" % (B * HW))
+    codes = codes.contiguous()
+    if mask is not None:
+        mask = _lib.require_cuda_f32(mask, "codebook_mask")
+        if mask.numel() != B * HW:
+            raise ValueError("codebook_mask has %d elements, expected B*H*W = %d" % (mask.numel(), B * HW))
+    dev = z.device
+    if B * HW == 0:
+        loss = torch.full((2,), float("nan"), dtype=torch.float32, device=dev) if want_loss else None
+        return (torch.empty_like(z) if want_zq else None), loss
+    if D % 16 != 0:                                         # (32-channel multiples are; anything else has no assign kernel either)
+        _padded_width(D)
+    zq = torch.empty_like(z) if want_zq else None
+    loss = torch.empty(2, dtype=torch.float32, device=dev) if want_loss else None
+    ws_ptr, ws_bytes = 0, 0
+    if want_loss:
+        ws = prep.workspace(B, D, HW, K, _lib.MODE_EXACT, dev)
+        ws.clean = False
+        ws_ptr, ws_bytes = ws.t.data_ptr(), ws.t.numel()
+    with _lib.on_device(dev):
+        if HW == 1:
+            _lib.check(_lib_handle.dvq_vq_apply_codes_flat_f32(
+                z.data_ptr(), codes.data_ptr(), codebook.data_ptr(), _lib.ptr(mask), B, D, K, float(beta), _lib.ptr(zq),
+                _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(dev)), "dvq_vq_apply_codes_flat_f32")
+        else:
+            _lib.check(_lib_handle.dvq_vq_apply_codes_nchw_f32(
+                z.data_ptr(), codes.data_ptr(), codebook.data_ptr(), _lib.ptr(mask), B, D, HW, K, float(beta), _lib.ptr(zq),
+                _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(dev)), "dvq_vq_apply_codes_nchw_f32")
+    return zq, loss
+
+
 def _gate_for_routed(gate, G):
     """-> (tensor, gate_kind) for a router output [B, hc, wc, G] (f32 logits or int64)"""
     if not gate.is_cuda:
@@ -665,6 +761,39 @@ def _vq_straight_through(z, weight, mask, prep, K, coef_z, coef_e, mode):
     if prep.track_users:
         prep.used(z.device)
     return zq, loss[1], codes
+
+
+class _VQGivenCodes(_VQStraightThrough):
+    """_VQStraightThrough with the codes GIVEN (score_assign's: sampled, or a cosine metric's) instead of found by vq_assign: the
+    forward is `apply_codes`; the backward formulas depend only on the codes, so they are the parent's
+    (`dvq_vq_backward_nchw_f32`, `dvq_vq_backward_codebook_nchw_f32`)."""
+
+    @staticmethod
+    def forward(ctx, z, weight, mask, codes, prep, K, coef_z, coef_e):
+        codebook = weight[:K]
+        zq, loss = apply_codes(z, codes, codebook.detach(), prep, mask, beta=(coef_z if coef_e == 1.0 else coef_e))
+        if prep.track_users:
+            prep.used(z.device)
+        ctx.compact = False
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            ctx.save_for_backward(z, codebook.detach().clone(), mask, codes)
+        ctx.wshape, ctx.coef_z, ctx.coef_e = tuple(weight.shape), coef_z, coef_e
+        return zq, loss[1]
+
+    @staticmethod
+    def backward(ctx, g_zq, g_loss):
+        gz, gw = _VQStraightThrough.backward(ctx, g_zq, g_loss, None)[:2]
+        return gz, gw, None, None, None, None, None, None
+
+
+def _vq_given_codes(z, weight, mask, codes, prep, K, coef_z, coef_e):
+    """_VQGivenCodes.apply when a graph is being recorded; the bare op otherwise (see _vq_straight_through)"""
+    if torch.is_grad_enabled() and (z.requires_grad or weight.requires_grad):
+        return _VQGivenCodes.apply(z, weight, mask, codes, prep, K, coef_z, coef_e)
+    zq, loss = apply_codes(z, codes, weight[:K].detach(), prep, mask, beta=(coef_z if coef_e == 1.0 else coef_e))
+    if prep.track_users:
+        prep.used(z.device)
+    return zq, loss[1]
 
 
 class VQEmbedding(InvalidatesPrepared, nn.Embedding):
@@ -1100,3 +1229,249 @@ class VectorQuantizer2(InvalidatesPrepared, nn.Module):
             z_q = z_q.view(shape)
             z_q = z_q.permute(0, 3, 1, 2).contiguous()
         return z_q
+
+
+def _batched_sample_vectors(samples, num):
+    """common_utils.batched_sample_vectors: `num` rows of each [n, d] slice of samples [h, n, d], without replacement when there
+    are enough (torch.randperm), with replacement otherwise (torch.randint)"""
+    out = []
+    for sample in samples.unbind(dim=0):
+        n = sample.shape[0]
+        if n >= num:
+            idx = torch.randperm(n, device=sample.device)[:num]
+        else:
+            idx = torch.randint(0, n, (num,), device=sample.device)
+        out.append(sample[idx])
+    return torch.stack(out, dim=0)
+
+
+def _noop(*args, **kwargs):
+    pass
+
+
+class _LearnableCodebookQuantizer(InvalidatesPrepared, nn.Module):
+    """What MaskVectorQuantize and VectorQuantize share -- in the reference the two classes are one text with and without the
+    codebook mask (modules/vector_quantization/quantize_codebook_mask.py, quantize.py): a codebook trained by back-propagation
+    (`embedding`, an nn.Embedding), temperature (gumbel-max) sampling of the code, L2 / cosine-similarity / cosine-distance scores,
+    optional k-means initialisation and orthogonal regularisation.
+
+    Dispatch of forward (f32 GPU tensors; anything else raises -- there is no torch fallback):
+      * L2, temp == 0: `vq_assign` in its default filter mode -- the op VectorQuantize2 runs, nothing new;
+      * L2, temp > 0: N x K uniforms from torch's generator (the reference's own draw), `score_assign`, `apply_codes`;
+      * cosine: tokens and weight normalised by the reference's torch calls in the reference's layout, a prep of the normalised
+        weight (cached on the weight's version), `score_assign` (METRIC_DOT; METRIC_L2 for use_cosine_distance), then `apply_codes`
+        against the RAW embedding rows, as the reference gathers them."""
+    _prepared = ("_prep", "_prep_norm")
+
+    def _setup(self, codebook_size, codebook_dim, kmeans_init, kmeans_iters, use_cosine_sim, use_cosine_distance, channel_last,
+               accept_image_fmap, commitment_beta, orthogonal_reg_weight):
+        self.codebook_size = codebook_size
+        self.codebook_dim = codebook_dim
+        self.accept_image_fmap = accept_image_fmap
+        self.channel_last = channel_last
+        self.use_cosine_sim = use_cosine_sim
+        self.use_cosine_distance = use_cosine_distance
+        self.beta = commitment_beta
+        self.embedding = nn.Embedding(self.codebook_size, self.codebook_dim)
+        if not kmeans_init:
+            self.embedding.weight.data.uniform_(-1.0 / self.codebook_size, 1.0 / self.codebook_size)
+        else:
+            self.embedding.weight.data.zero_()
+        self.kmeans_iters = kmeans_iters
+        self.register_buffer('initted', torch.Tensor([not kmeans_init]))
+        self.register_buffer('cluster_size', torch.zeros(1, codebook_size))
+        self.sample_fn = _batched_sample_vectors
+        self.all_reduce_fn = _noop
+        self.orthogonal_reg_weight = orthogonal_reg_weight
+        self._prep = _CodebookPrep()
+        self._prep_norm = _CodebookPrep()        # of the L2-normalised weight (cosine metrics)
+        self._norm_weight = None                 # (key, normalised weight): the tensor _prep_norm was built from
+        self.assign_mode = _lib.MODE_FILTER
+        self._initted_host = not kmeans_init     # host mirror of `initted`: no device read per forward once it is set
+
+    def invalidate_codebook_cache(self):
+        """call after writing embedding.weight through `.data` in eval mode"""
+        self._prep.invalidate()
+        self._prep_norm.invalidate()
+        self._norm_weight = None
+
+    def _invalidate_prepared(self):
+        super()._invalidate_prepared()
+        self._norm_weight = None
+        self._initted_host = False               # (a loaded state_dict / a moved module: read `initted` again)
+
+    # ---- k-means initialisation (common_utils.kmeans:116-156; always the L2 form: init_embed_ never passes use_cosine_sim)
+    @torch.no_grad()
+    def init_embed_(self, data):
+        """data [..., D]: Lloyd iterations from `self.sample_fn`'s rows -- per iteration the exact-mode assign (codes only) and the
+        counts / sums kernel of the EMA update (`dvq_ema_accumulate_nchw_f32`); empty clusters keep their mean.  Against the
+        reference's -cdist / scatter_add_ loop the sums differ in order (float atomics), so means agree within rounding."""
+        if self._initted_host:
+            return
+        if bool(self.initted.item()):
+            self._initted_host = True
+            return
+        K, D = self.codebook_size, self.codebook_dim
+        flat = _lib.require_cuda_f32(data.detach().reshape(-1, D), "x")
+        samples = flat.unsqueeze(0)                                   # [1, N, D], the reference's 'h n d'
+        means = self.sample_fn(samples, K)                            # [1, K, D]
+        N = flat.shape[0]
+        dev = flat.device
+        prep = _CodebookPrep()
+        stats = torch.empty(K * D + K, dtype=torch.float32, device=dev)
+        sums, counts = stats[:K * D].view(K, D), stats[K * D:]
+        bins = torch.zeros(1, K, dtype=torch.int64, device=dev)
+        for _ in range(self.kmeans_iters):
+            cb = means[0].contiguous()
+            _, buckets, _ = vq_assign(flat, cb, prep, want_zq=False, want_loss=False, mode=_lib.MODE_EXACT)
+            with _lib.on_device(dev):
+                _lib.check(_lib_handle.dvq_ema_accumulate_nchw_f32(
+                    flat.data_ptr(), buckets.data_ptr(), N, D, 1, K, counts.data_ptr(), sums.data_ptr(),
+                    _lib.stream_ptr(dev)), "dvq_ema_accumulate_nchw_f32")
+            bins = counts.round().to(torch.int64).unsqueeze(0)        # [1, K]
+            self.all_reduce_fn(bins)
+            zero_mask = bins == 0
+            new_means = sums.unsqueeze(0) / bins.masked_fill(zero_mask, 1).unsqueeze(-1)
+            self.all_reduce_fn(new_means)
+            means = torch.where(zero_mask.unsqueeze(-1), means, new_means)
+        self.embedding.weight.data.copy_(means.squeeze(0))
+        self.cluster_size.data.copy_(bins)
+        self.initted.data.copy_(torch.Tensor([True]))
+        self._initted_host = True
+        self.invalidate_codebook_cache()
+
+    # ---- the pieces of forward
+    def _draw_uniform(self, N, K, device):
+        """the reference's noise draw (common_utils.py:27-29 on a [N, K] `dist`): torch's generator of `device` advances exactly
+        as it does there"""
+        return torch.zeros(N, K, device=device).uniform_(0, 1)
+
+    def _normalised_weight(self):
+        w = self.embedding.weight
+        key = (w.data_ptr(), w._version, tuple(w.shape), w.device)
+        ent = self._norm_weight
+        if ent is None or ent[0] != key or self.training:
+            with torch.no_grad():
+                ent = self._norm_weight = (key, F.normalize(w.detach(), p=2, dim=-1).contiguous())
+            self._prep_norm.invalidate()
+        return ent[1]
+
+    def _quantize(self, x, temp, codebook_mask):
+        temp = float(temp)
+        if not (temp >= 0.0 and math.isfinite(temp)):
+            raise ValueError("temp must be finite and >= 0, got %r" % temp)
+        w = self.embedding.weight
+        x = _lib.require_cuda_f32(x, "x")
+        _lib.require_cuda_f32(w, "embedding.weight")
+        need_transpose = not self.channel_last and not self.accept_image_fmap
+        if self.accept_image_fmap:
+            if x.dim() != 4:
+                raise ValueError("accept_image_fmap=True expects x [B, C, H, W]")
+            z, channel_major = x, True                   # NCHW read in place by the kernels
+        elif need_transpose:                             # x is [B, D, N]: already channel-major
+            z, channel_major = x, True
+        else:                                            # channel_last: x [B, ..., D] -> tokens [N, D]
+            z, channel_major = x.reshape(-1, x.shape[-1]), False
+        K, D = self.codebook_size, self.codebook_dim
+        if z.shape[1] != D:
+            raise ValueError("channel dim %d != codebook_dim %d" % (z.shape[1], D))
+        _padded_width(D)                                 # other widths raise here, whatever the path
+        if not self._initted_host:
+            ztok = z.reshape(z.shape[0], D, -1).permute(0, 2, 1) if channel_major else z
+            self.init_embed_(ztok)
+        mask = None
+        if codebook_mask is not None:
+            mask = codebook_mask if codebook_mask.dtype == torch.float32 else codebook_mask.float()
+        if self.training:
+            self._prep.invalidate()                      # the optimizer may have stepped through .data
+        self._prep.track_users = self.training
+        cosine = self.use_cosine_sim or self.use_cosine_distance
+        if not cosine and temp == 0.0:
+            zq, loss, codes = _vq_straight_through(z, w, mask, self._prep, K, float(self.beta), 1.0, self.assign_mode)
+        else:
+            N = z.numel() // D
+            with torch.no_grad():
+                if cosine:
+                    # rearrange first, then normalise along the last axis: the reference's calls on the reference's layout
+                    rows = z.detach().reshape(z.shape[0], D, -1).permute(0, 2, 1).contiguous() if channel_major else z.detach()
+                    toks = F.normalize(rows, p=2, dim=-1).reshape(N, D)
+                    book, prep = self._normalised_weight(), self._prep_norm
+                    metric = _lib.METRIC_DOT if self.use_cosine_sim else _lib.METRIC_L2
+                else:
+                    toks, book, prep, metric = z.detach(), w.detach(), self._prep, _lib.METRIC_L2
+                prep.track_users = self.training
+                u = self._draw_uniform(N, K, z.device) if temp > 0.0 else None
+                codes = score_assign(toks, book, prep, metric, temp, u)
+                if prep.track_users:
+                    prep.used(z.device)
+                codes = codes.reshape((z.shape[0],) + tuple(z.shape[2:]))
+            zq, loss = _vq_given_codes(z, w, mask, codes, self._prep, K, float(self.beta), 1.0)
+        if mask is not None:
+            # ratio * beta * m + ratio * m (quantize_codebook_mask.py:118-119); the kernel's loss is beta * m + m
+            loss = loss * (1 / torch.mean(mask))
+        if self.orthogonal_reg_weight > 0.:
+            # eq (2) of arXiv 2112.00384 (quantize_codebook_mask.py:124-132): K x K, off the token path
+            wn = F.normalize(w, p=2, dim=-1)
+            diff = torch.mm(wn, torch.transpose(wn, 0, 1)) - torch.eye(K, K).type_as(wn)
+            loss = loss + self.orthogonal_reg_weight * torch.sum(diff ** 2) / (diff.size(0) ** 2)
+        if channel_major:
+            return zq, loss, codes
+        codes = codes.reshape(x.shape[:-1])
+        if codes.dim() > 2:                              # 'h ... d -> h (...) d'
+            codes = codes.reshape(x.shape[0], -1)
+        return zq.reshape(x.shape), loss, codes
+
+    @torch.no_grad()
+    def embed_code_with_depth(self, code, to_latent_shape=False):
+        code_slices = torch.chunk(code, chunks=code.shape[-1], dim=-1)
+        embeds = [self.embedding(code_slice) for code_slice in code_slices]
+        if to_latent_shape:
+            embeds = [self.to_latent_shape(embed.squeeze(-2)).unsqueeze(-2) for embed in embeds]
+        return torch.cat(embeds, dim=-2), None
+
+
+class MaskVectorQuantize(_LearnableCodebookQuantizer):
+    """Reference modules/vector_quantization/quantize_codebook_mask.py:15-165.
+      target: dynamicvectorquantization_amd.quantize.MaskVectorQuantize"""
+
+    def __init__(self, codebook_size, codebook_dim=None, kmeans_init=False, kmeans_iters=10, use_cosine_sim=False,
+                 channel_last=False, accept_image_fmap=True, commitment_beta=0.25, orthogonal_reg_weight=0.,
+                 activate_mask_quantize=True):
+        super().__init__()
+        self._setup(codebook_size, codebook_dim, kmeans_init, kmeans_iters, use_cosine_sim, False, channel_last,
+                    accept_image_fmap, commitment_beta, orthogonal_reg_weight)
+        self.activate_mask_quantize = activate_mask_quantize
+
+    def forward(self, x, temp=0., codebook_mask=None):
+        if not self.activate_mask_quantize:
+            codebook_mask = None
+        x_q, loss, embed_ind = self._quantize(x, temp, codebook_mask)
+        return x_q, loss, (None, None, embed_ind)
+
+    def get_codebook_entry(self, indices, shape, *kwargs):
+        z_q = self.embedding(indices)
+        if shape is not None:
+            z_q = z_q.view(shape)
+            z_q = z_q.permute(0, 3, 1, 2).contiguous()
+        return z_q
+
+
+class VectorQuantize(_LearnableCodebookQuantizer):
+    """Reference modules/vector_quantization/quantize.py:15-147.
+      target: dynamicvectorquantization_amd.quantize.VectorQuantize"""
+
+    def __init__(self, codebook_size, codebook_dim=None, kmeans_init=False, kmeans_iters=10, use_cosine_sim=False,
+                 use_cosine_distance=False, channel_last=False, accept_image_fmap=True, commitment_beta=0.25,
+                 orthogonal_reg_weight=0.):
+        super().__init__()
+        self._setup(codebook_size, codebook_dim, kmeans_init, kmeans_iters, use_cosine_sim,
+                    use_cosine_distance and not use_cosine_sim, channel_last, accept_image_fmap, commitment_beta,
+                    orthogonal_reg_weight)
+        self.use_cosine_distance = use_cosine_distance
+
+    def forward(self, x, temp=0.):
+        x_q, loss, embed_ind = self._quantize(x, temp, None)
+        return x_q, loss, (None, None, embed_ind)
+
+    def get_codebook_entry(self, indices, *kwargs):
+        return self.embedding(indices)

@@ -28,6 +28,8 @@
  *     (quantize.py: _padded_width); divide the returned loss mean by D / D_padded.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.12.0 dvq_vq_score_assign_f32, dvq_vq_apply_codes_nchw_f32, dvq_vq_apply_codes_flat_f32 (new), DVQ_METRIC_L2 / DVQ_METRIC_DOT: the
+ *          scored / temperature-sampled assign of MaskVectorQuantize / VectorQuantize and quantisation from given codes.  Nothing else changed.
  *   0.11.0 dvq_vq_soft_assign_workspace_bytes, dvq_vq_soft_assign_flat_f32 (new): get_soft_codes as one kernel -- the assign's
  *          bit-exact distances, softmax(-d / temp), the hard code or the multinomial draw.  Nothing else changed.
  *   0.10.0 dvq_decode_table_bytes, dvq_decode_table_prepare_f32, dvq_decode_head_f32 (new): codes -> the input of the decoder's
@@ -689,6 +691,51 @@ DVQ_API int dvq_decode_head_f32(const int64_t *codes, int B, int HW, const float
 DVQ_API size_t dvq_vq_soft_assign_workspace_bytes(int64_t N, int D, int K);
 DVQ_API int dvq_vq_soft_assign_flat_f32(const float *x, const float *codebook, const void *prep, int64_t N, int D, int K,
                                         float temp, const float *q, float *soft, float *dist, int64_t *codes,
+                                        void *ws, size_t ws_bytes, void *stream);
+
+/*
+ * Scored / temperature-sampled code assignment: the learnable-codebook quantizers MaskVectorQuantize / VectorQuantize.
+ * Replaces: `dist` (quantize_codebook_mask.py:97-108, quantize.py:92-110) and gumbel_sample(dist, temperature = temp)
+ *           (common_utils.py:19-35): the [N, K] score matrix, dist / temp, the uniform noise, two logs, two clamps, an add and
+ *           the argmax -- about ten passes over N x K floats; here one sweep that reads u once and writes N codes.
+ *   x        [B, D, HW] read in place (NCHW, HW = H*W); HW == 1 is the row-major case [N, D] with B = N
+ *   prep     dvq_codebook_prepare_f32 of the codebook the scores are against (for the cosine metrics: of the NORMALISED rows)
+ *   metric   DVQ_METRIC_L2:  s = -d, d = the assign's distance bit for bit (sequential-k fp32 FMA chain, ATen-order norms,
+ *                            fl(fl(xn + en) - 2 dot)): the reference's -sum x^2 - sum e^2 + 2 x E^T, negation included
+ *            DVQ_METRIC_DOT: s = dot, the same chain (use_cosine_sim: the caller passes L2-normalised tokens and rows;
+ *                            use_cosine_distance is DVQ_METRIC_L2 on normalised operands)
+ *   u        nullable [N, K], N = B * HW: uniforms drawn by the caller, torch.zeros(N, K).uniform_(0, 1) (the reference's own
+ *            draw: the generator is consumed identically); u_numel = its element count, checked against N * K
+ *   temp     finite, > 0 when u is given; ignored otherwise
+ *   codes    [N] int64:
+ *            u == NULL: argmax_j s[n, j]
+ *            u given:   argmax_j fl(fl(s[n, j] / temp) + g[n, j]),  g = -logf(max(-logf(max(u, 1e-20f)), 1e-20f))
+ *            with torch.argmax's rules: the first index among equal maxima; a NaN is the maximum and the first NaN wins
+ * D in {64, 128, 256} (DVQ_EUNSUPPORTED otherwise; other widths by zero padding, as for the assign).  DVQ_EINVAL: null x / prep /
+ * codes, an unknown metric, u with temp not finite or <= 0, u_numel != N * K.  u is read once, as 16-byte pieces when K % 4 == 0
+ * and u is 16-byte aligned, 4-byte ones otherwise: the same values.  Nothing of size N x K is written.
+ * One launch, no workspace, no atomics, no host synchronisation: capturable in a HIP graph.  Vector stores only.
+ */
+#define DVQ_METRIC_L2  0
+#define DVQ_METRIC_DOT 1
+DVQ_API int dvq_vq_score_assign_f32(const float *x, const void *prep, int B, int D, int HW, int K, int metric, float temp,
+                                    const float *u, int64_t u_numel, int64_t *codes, void *stream);
+
+/*
+ * Quantisation from GIVEN codes -- the rest of those forwards (quantize_codebook_mask.py:114-121,135; quantize.py:116-119,133):
+ * embedding gather, (masked) loss, straight-through add, as one streaming kernel (+ the loss finalize).
+ *   z [B, D, HW] (flat: [N, D]); codes [B, HW] int64 (a code outside [0, K): z_q = z, no loss term); codebook [>= K, D], 16-byte
+ *   aligned; mask nullable [B, HW]; zq nullable [B, D, HW] = fl(z + fl(e - z)); loss nullable [2]: loss[0] = mean((e - z)^2 * mask),
+ *   loss[1] = fl(fl(beta * mean) + mean) (partials in double, summed in one fixed order);
+ *   ws: only when loss is wanted, >= dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_EXACT), 256-byte aligned.
+ * Fed the codes dvq_vq_assign_nchw_f32 returns, zq is bit-identical to that op's and the loss agrees within 1e-5 relative.
+ * D a multiple of 16.
+ */
+DVQ_API int dvq_vq_apply_codes_nchw_f32(const float *z, const int64_t *codes, const float *codebook, const float *mask,
+                                        int B, int D, int HW, int K, float beta, float *zq, float *loss,
+                                        void *ws, size_t ws_bytes, void *stream);
+DVQ_API int dvq_vq_apply_codes_flat_f32(const float *z, const int64_t *codes, const float *codebook, const float *mask,
+                                        int64_t N, int D, int K, float beta, float *zq, float *loss,
                                         void *ws, size_t ws_bytes, void *stream);
 
 /*
