@@ -1,12 +1,13 @@
 // dvq_abi.hip -- the extern "C" boundary of libdvq.so (see include/dvq.h).
 // Argument validation + launch only: no allocation, no synchronisation, no torch types.
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 1200   // 0.12.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1300   // 0.13.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -115,6 +116,11 @@ int dvq_launch_score_assign(const float *z, const float *prep, int D, int HW, in
 int dvq_apply_codes_blocks(long N);
 int dvq_launch_apply_codes(const float *z, const float *E, const long long *codes, const float *mask, int D, int HW, int K, long N,
                            float *zq, double *partials, hipStream_t st);
+int dvq_launch_gumbel_bias(const float *bias, int K, int D, void *prep, hipStream_t st);
+int dvq_gumbel_blocks(long N);
+int dvq_launch_gumbel_assign(const float *z, const float *prep, const float *E, int C, int HW, int K, int d, long N, float tau,
+                             double log_kl_K, const float *q, float *zq, long long *codes, double *partials, hipStream_t st);
+int dvq_launch_gumbel_kl_finalize(const double *partials, int nparts, double inv_n, float *kl, hipStream_t st);
 size_t dvq_qconv_prep_bytes_impl(int D);
 int dvq_launch_qconv_prep(const float *Wt, const float *bias, int D, void *prep, hipStream_t st);
 int dvq_launch_qconv(const float *x, const DvqRouted *rv, const void *prep, int D, int HW, long N, float *hout,
@@ -1253,6 +1259,64 @@ int dvq_vq_apply_codes_flat_f32(const float *z, const int64_t *codes, const floa
 {
     if (N <= 0 || N >= ((int64_t)1 << 31)) { dvq_set_error("dvq_vq_apply_codes_flat_f32: N=%lld out of range", (long long)N); return DVQ_EINVAL; }
     return dvq_vq_apply_codes_nchw_f32(z, codes, codebook, mask, (int)N, D, 1, K, beta, zq, loss, ws, ws_bytes, stream);
+}
+
+// ---- GumbelQuantize: projection, Gumbel argmax, KL and z_q in one sweep (vq_gumbel.hip) -----------------------------------------
+size_t dvq_gumbel_prep_bytes(int K, int C)
+{
+    if (K <= 0 || !dim_ok(C)) return 0;
+    // the f32 tile images and norms of the codebook prep, and the 256 bytes in which its builder resets the fp16 section's bound
+    return (dvq_prep_f16_offset(K, C) + 255) / 256 * 256 + 256;
+}
+
+int dvq_gumbel_prepare_f32(const float *weight, const float *bias, int K, int C, void *prep, size_t prep_bytes, void *stream)
+{
+    const char *fn = "dvq_gumbel_prepare_f32";
+    if (!weight || !prep || K <= 0) { dvq_set_error("%s: null pointer or K <= 0", fn); return DVQ_EINVAL; }
+    if (!dim_ok(C)) { dvq_set_error("%s: C=%d unsupported (kernel widths 64, 128, 256)", fn, C); return DVQ_EUNSUPPORTED; }
+    if (prep_bytes < dvq_gumbel_prep_bytes(K, C)) { dvq_set_error("%s: prep buffer %zu < %zu bytes", fn, prep_bytes, dvq_gumbel_prep_bytes(K, C)); return DVQ_EWORKSPACE; }
+    if (((uintptr_t)prep & 255) != 0 || (((uintptr_t)weight | (uintptr_t)bias) & 3) != 0) { dvq_set_error("%s: misaligned pointer (prep: 256 bytes)", fn); return DVQ_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    int rc = dvq_launch_prep_f32(weight, K, C, prep, st);          // the codebook prep's image builder, norms in the en slot
+    if (rc) return hip_rc(rc, "codebook_prep_f32");
+    return hip_rc(dvq_launch_gumbel_bias(bias, K, C, prep, st), "gumbel_bias");    // ... which the bias then takes
+}
+
+size_t dvq_vq_gumbel_assign_workspace_bytes(int B, int HW)
+{
+    if (B <= 0 || HW <= 0) return 0;
+    const size_t N = (size_t)B * (size_t)HW;
+    return (((N + 127) / 128) * sizeof(double) + 255) / 256 * 256 + 256;
+}
+
+int dvq_vq_gumbel_assign_f32(const float *z, const void *prep, const float *embed, int B, int C, int HW, int K, int d, float tau,
+                             float kl_K, const float *q, float *zq, int64_t *codes, float *kl, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_vq_gumbel_assign_f32";
+    if (!z || !prep || !embed || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (B <= 0 || HW <= 0 || K <= 0 || d <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d d=%d must be positive", fn, B, HW, K, d); return DVQ_EINVAL; }
+    if (!dim_ok(C)) { dvq_set_error("%s: C=%d unsupported (kernel widths 64, 128, 256)", fn, C); return DVQ_EUNSUPPORTED; }
+    if (q && (!(tau > 0.0f) || !(tau < __builtin_inff()))) { dvq_set_error("%s: tau=%g must be finite and positive when q is given", fn, (double)tau); return DVQ_EINVAL; }
+    if (!(kl_K > 0.0f) || !(kl_K < __builtin_inff())) { dvq_set_error("%s: kl_K=%g must be finite and positive", fn, (double)kl_K); return DVQ_EINVAL; }
+    const size_t N = (size_t)B * (size_t)HW;
+    if (N >= ((size_t)1 << 31) || N * (size_t)C >= ((size_t)1 << 40) || N * (size_t)K >= ((size_t)1 << 40) || N * (size_t)d >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if ((((uintptr_t)z | (uintptr_t)embed | (uintptr_t)q | (uintptr_t)zq | (uintptr_t)kl) & 3) != 0 || ((uintptr_t)prep & 255) != 0 || ((uintptr_t)codes & 7) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
+    double *partials = nullptr;
+    if (kl) {
+        const size_t need = dvq_vq_gumbel_assign_workspace_bytes(B, HW);
+        if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes (kl is wanted)", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EINVAL; }
+        if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+        partials = (double *)ws;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc = dvq_launch_gumbel_assign(z, (const float *)prep, embed, C, HW, K, d, (long)N, tau, log((double)kl_K), q, zq,
+                                      (long long *)codes, partials, st);
+    if (rc) return hip_rc(rc, "vq_gumbel_assign");
+    if (kl) {
+        rc = dvq_launch_gumbel_kl_finalize(partials, dvq_gumbel_blocks((long)N), 1.0 / (double)N, kl, st);
+        if (rc) return hip_rc(rc, "vq_gumbel_kl_finalize");
+    }
+    return DVQ_OK;
 }
 
 }  // extern "C"

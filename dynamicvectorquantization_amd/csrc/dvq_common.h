@@ -95,6 +95,25 @@ __device__ __forceinline__ void argmin_merge(float &d, int &i, float d2, int i2)
     if (other) { d = d2; i = i2; }
 }
 
+// torch argmax step over candidates visited in ascending index (vq_sample.hip, vq_gumbel.hip): take if v > best, or v is NaN and
+// best is not
+__device__ __forceinline__ bool argmax_take(float v, float best)
+{
+    return !(v <= best) && (best == best);
+}
+
+// merge two (value, index) candidates of disjoint ascending scans
+__device__ __forceinline__ void argmax_merge(float &v, int &i, float v2, int i2)
+{
+    const bool n1 = v != v, n2 = v2 != v2;
+    bool other;
+    if (n1 || n2)
+        other = n2 && (!n1 || i2 < i);
+    else
+        other = (v2 > v) || (v2 == v && i2 < i);
+    if (other) { v = v2; i = i2; }
+}
+
 // Loss finalize fused into the last kernel of the filter path (vq_assign_exact_kernel in list
 // mode): the block that draws the last ticket sums partials[0 .. nparts) and writes loss[0..1].
 struct DvqLossTail {

@@ -28,24 +28,6 @@
 #define DVQ_METRIC_L2_ 0
 #define DVQ_METRIC_DOT_ 1
 
-// torch argmax step over candidates visited in ascending index: take if v > best, or v is NaN and best is not
-__device__ __forceinline__ bool argmax_take(float v, float best)
-{
-    return !(v <= best) && (best == best);
-}
-
-// merge two (value, index) candidates of disjoint ascending scans
-__device__ __forceinline__ void argmax_merge(float &v, int &i, float v2, int i2)
-{
-    const bool n1 = v != v, n2 = v2 != v2;
-    bool other;
-    if (n1 || n2)
-        other = n2 && (!n1 || i2 < i);
-    else
-        other = (v2 > v) || (v2 == v && i2 < i);
-    if (other) { v = v2; i = i2; }
-}
-
 // the reference's gumbel_noise of one uniform (common_utils.py:19-29): -log(clamp(-log(clamp(u, 1e-20)), 1e-20))
 __device__ __forceinline__ float gumbel_of(float u)
 {

@@ -28,6 +28,8 @@
  *     (quantize.py: _padded_width); divide the returned loss mean by D / D_padded.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.13.0 dvq_gumbel_prep_bytes, dvq_gumbel_prepare_f32, dvq_vq_gumbel_assign_workspace_bytes, dvq_vq_gumbel_assign_f32 (new): GumbelQuantize's
+ *          hard forward -- projection, Gumbel argmax, KL term and z_q -- as one sweep.  Nothing else changed.
  *   0.12.0 dvq_vq_score_assign_f32, dvq_vq_apply_codes_nchw_f32, dvq_vq_apply_codes_flat_f32 (new), DVQ_METRIC_L2 / DVQ_METRIC_DOT: the
  *          scored / temperature-sampled assign of MaskVectorQuantize / VectorQuantize and quantisation from given codes.  Nothing else changed.
  *   0.11.0 dvq_vq_soft_assign_workspace_bytes, dvq_vq_soft_assign_flat_f32 (new): get_soft_codes as one kernel -- the assign's
@@ -737,6 +739,50 @@ DVQ_API int dvq_vq_apply_codes_nchw_f32(const float *z, const int64_t *codes, co
 DVQ_API int dvq_vq_apply_codes_flat_f32(const float *z, const int64_t *codes, const float *codebook, const float *mask,
                                         int64_t N, int D, int K, float beta, float *zq, float *loss,
                                         void *ws, size_t ws_bytes, void *stream);
+
+/*
+ * GumbelQuantize (hard / straight-through forward): projection to K logits, Gumbel-max code, KL term and z_q in ONE sweep.
+ * Replaces: GumbelQuantize.forward (quantize_vqgan.py:171-200): the 1x1 `proj` conv, F.gumbel_softmax (the Exp(1) draw's log,
+ *           the add, the divide by tau, a softmax, the hard one-hot), the dense [N, K] x [K, d] einsum with a one-hot left operand,
+ *           a second softmax and a log for the KL term, an argmax -- about ten passes over [N, K] floats.  Here z and q are read
+ *           once; N codes, one scalar and z_q are written; nothing of size N x K is.
+ *
+ * dvq_gumbel_prepare_f32 -- once per (proj.weight, proj.bias): the codebook prep's f32 tile images of weight [K, C] (built by
+ *   the same kernel dvq_codebook_prepare_f32 runs), with bias [K] (nullable: zeros) where the images carry the row norms.
+ *   prep: >= dvq_gumbel_prep_bytes(K, C) (0: unsupported shape), 256-byte aligned.  Only dvq_vq_gumbel_assign_f32 reads it.
+ *
+ * dvq_vq_gumbel_assign_f32
+ *   z      [B, C, HW] read in place (NCHW); HW == 1 is the flat case [N, C] with B = N
+ *   embed  [K, d] row-major, d any positive value (read with 16-byte loads when d % 8 == 0 and embed is 16-byte aligned)
+ *   q      nullable [B, K, HW]: the Exp(1) variates F.gumbel_softmax draws (-empty_like(logits).exponential_().log()), drawn by
+ *          the caller in the logits' own layout -- torch's generator is consumed as in the reference
+ *   tau    finite, > 0 when q is given; ignored otherwise
+ *   kl_K   the factor inside the KL term's log (the module passes n_embed); finite, > 0
+ *   zq     nullable [B, d, HW]; codes [B, HW] int64; kl nullable [1]
+ *   ws     only when kl is wanted: >= dvq_vq_gumbel_assign_workspace_bytes(B, HW), 256-byte aligned
+ * Per token n:
+ *   l_k      = fl(dot(z_n, W_k) + b_k): the sequential-k fp32 FMA chain of dvq_vq_score_assign_f32, the bias added after it
+ *   codes[n] = q == NULL: argmax_k l_k;  q given: argmax_k fl(fl(l_k + g_k) / tau), g_k = -logf(q_k)
+ *              with torch.argmax's rules: the first index among equal maxima; a NaN is the maximum and the first NaN wins
+ *   KL_n     = sum_k p_k log(p_k kl_K + 1e-10), p = softmax(l), evaluated online as A / S - m - log S + log kl_K with the
+ *              running maximum m, S = sum e^(l - m), A = sum e^(l - m) l -- WITHOUT the 1e-10: each term differs by
+ *              p log(1 + 1e-10 / (p kl_K)) <= 1e-10 / kl_K, the sum by at most 1e-10 K / kl_K, i.e. 1e-10 per token when
+ *              kl_K = K, against KL values of order 0.01 to 10
+ *   kl[0]    = mean_n KL_n: one double partial per workgroup, added in one fixed order by a finalize kernel -- deterministic
+ *   zq[b, :, hw] = embed[codes[n], :], the codebook row ITSELF (bit-equal).  The reference's value is f embed[code] with
+ *              f = fl(fl(1 - y) + y), y the winner's soft probability in (0, 1]: |f - 1| <= 2^-23
+ * C in {64, 128, 256}: DVQ_EUNSUPPORTED otherwise.  DVQ_EINVAL: null z / prep / embed / codes, tau not finite or <= 0 when q is
+ * given, kl_K <= 0, a missing or too small workspace when kl is wanted, a misaligned pointer.  B * HW < 2^31.
+ * Two launches (the sweep, the finalize when kl is wanted) on one stream: no atomics, no host synchronisation, no allocation;
+ * capturable in a HIP graph as a single chain.  Vector stores only.
+ */
+DVQ_API size_t dvq_gumbel_prep_bytes(int K, int C);
+DVQ_API int dvq_gumbel_prepare_f32(const float *weight, const float *bias, int K, int C, void *prep, size_t prep_bytes,
+                                   void *stream);
+DVQ_API size_t dvq_vq_gumbel_assign_workspace_bytes(int B, int HW);
+DVQ_API int dvq_vq_gumbel_assign_f32(const float *z, const void *prep, const float *embed, int B, int C, int HW, int K, int d,
+                                     float tau, float kl_K, const float *q, float *zq, int64_t *codes, float *kl,
+                                     void *ws, size_t ws_bytes, void *stream);
 
 /*
  * Wire format of the image-parallel exchange (one all-gather per batch; the reference gathers nothing --
