@@ -56,6 +56,8 @@ EXPORTS = (
     "dvq_vq_soft_assign_workspace_bytes", "dvq_vq_soft_assign_flat_f32",
     "dvq_vq_score_assign_f32", "dvq_vq_apply_codes_nchw_f32", "dvq_vq_apply_codes_flat_f32",
     "dvq_gumbel_prep_bytes", "dvq_gumbel_prepare_f32", "dvq_vq_gumbel_assign_workspace_bytes", "dvq_vq_gumbel_assign_f32",
+    "dvq_vq_assign_narrow_workspace_bytes", "dvq_vq_assign_narrow_tile_codes", "dvq_vq_assign_narrow_nchw_f32",
+    "dvq_vq_assign_narrow_flat_f32",
 )
 
 
@@ -238,6 +240,14 @@ def _load():
     lib.dvq_vq_gumbel_assign_workspace_bytes.argtypes = [i32, i32]
     lib.dvq_vq_gumbel_assign_f32.restype = i32
     lib.dvq_vq_gumbel_assign_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]
+    lib.dvq_vq_assign_narrow_workspace_bytes.restype = sz
+    lib.dvq_vq_assign_narrow_workspace_bytes.argtypes = [i64]
+    lib.dvq_vq_assign_narrow_tile_codes.restype = i32
+    lib.dvq_vq_assign_narrow_tile_codes.argtypes = [i32]
+    lib.dvq_vq_assign_narrow_nchw_f32.restype = i32
+    lib.dvq_vq_assign_narrow_nchw_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]
+    lib.dvq_vq_assign_narrow_flat_f32.restype = i32
+    lib.dvq_vq_assign_narrow_flat_f32.argtypes = [vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp, sz, vp]
     return lib
 
 

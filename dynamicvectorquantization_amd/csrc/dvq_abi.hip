@@ -7,7 +7,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 1300   // 0.13.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1400   // 0.14.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -120,6 +120,10 @@ int dvq_launch_gumbel_bias(const float *bias, int K, int D, void *prep, hipStrea
 int dvq_gumbel_blocks(long N);
 int dvq_launch_gumbel_assign(const float *z, const float *prep, const float *E, int C, int HW, int K, int d, long N, float tau,
                              double log_kl_K, const float *q, float *zq, long long *codes, double *partials, hipStream_t st);
+int dvq_narrow_tile_codes(int D);
+int dvq_narrow_blocks(long N);
+int dvq_launch_narrow(const float *z, const float *E, const float *mask, int D, int HW, int K, long N, bool flat, float *zq,
+                      long long *codes, double *partials, hipStream_t st);
 int dvq_launch_gumbel_kl_finalize(const double *partials, int nparts, double inv_n, float *kl, hipStream_t st);
 size_t dvq_qconv_prep_bytes_impl(int D);
 int dvq_launch_qconv_prep(const float *Wt, const float *bias, int D, void *prep, hipStream_t st);
@@ -1317,6 +1321,58 @@ int dvq_vq_gumbel_assign_f32(const float *z, const void *prep, const float *embe
         if (rc) return hip_rc(rc, "vq_gumbel_kl_finalize");
     }
     return DVQ_OK;
+}
+
+// ---- narrow widths (D = 4, 8, 16): the exact VALU assign of vq_assign_narrow.hip, no prepared codebook image -----------------
+size_t dvq_vq_assign_narrow_workspace_bytes(int64_t N)
+{
+    if (N <= 0 || N >= ((int64_t)1 << 31)) return 0;
+    return ((size_t)dvq_narrow_blocks((long)N) * sizeof(double) + 255) / 256 * 256 + 256;
+}
+
+int dvq_vq_assign_narrow_tile_codes(int D) { return dvq_narrow_tile_codes(D); }
+
+static int narrow_common(const char *fn, const float *z, const float *codebook, const float *mask, int64_t N, int D, int HW, int K,
+                         bool flat, float beta, float *zq, int64_t *codes, float *loss, void *ws, size_t ws_bytes, void *stream)
+{
+    if (D <= 0) { dvq_set_error("%s: D=%d must be positive", fn, D); return DVQ_EINVAL; }
+    if (dvq_narrow_tile_codes(D) == 0) { dvq_set_error("%s: D=%d unsupported (the narrow kernel serves the widths 4, 8 and 16; 3 runs exactly at 4 with a zero channel appended to latents and codebook; 64, 128, 256 and their zero-padded widths are dvq_vq_assign_nchw_f32's)", fn, D); return DVQ_EUNSUPPORTED; }
+    if (N >= ((int64_t)1 << 31) || K >= (1 << 20)) { dvq_set_error("%s: tensor too large (N=%lld < 2^31, K=%d < 2^20)", fn, (long long)N, K); return DVQ_EUNSUPPORTED; }
+    if ((((uintptr_t)z | (uintptr_t)zq | (uintptr_t)mask | (uintptr_t)loss) & 3) != 0 || ((uintptr_t)codebook & 15) != 0 || ((uintptr_t)codes & 7) != 0) { dvq_set_error("%s: misaligned pointer (codebook: 16 bytes)", fn); return DVQ_EINVAL; }
+    if (flat && (((uintptr_t)z | (uintptr_t)zq) & 15) != 0) { dvq_set_error("%s: z and zq must be 16-byte aligned (rows are read and written with 16-byte accesses)", fn); return DVQ_EINVAL; }
+    double *partials = nullptr;
+    if (loss) {
+        const size_t need = dvq_vq_assign_narrow_workspace_bytes(N);
+        if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes (loss is wanted)", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EINVAL; }
+        if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+        partials = (double *)ws;
+    }
+    hipStream_t st = (hipStream_t)stream;
+    int rc = dvq_launch_narrow(z, codebook, mask, D, HW, K, (long)N, flat, zq, (long long *)codes, partials, st);
+    if (rc) return hip_rc(rc, "vq_assign_narrow");
+    if (loss) {
+        rc = dvq_launch_loss_finalize(partials, dvq_narrow_blocks((long)N), 1.0 / ((double)N * D), beta, loss, st);
+        if (rc) return hip_rc(rc, "vq_loss_finalize");
+    }
+    return DVQ_OK;
+}
+
+int dvq_vq_assign_narrow_nchw_f32(const float *z, const float *codebook, const float *mask, int B, int D, int HW, int K, float beta,
+                                  float *zq, int64_t *codes, float *loss, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_vq_assign_narrow_nchw_f32";
+    if (!z || !codebook || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
+    return narrow_common(fn, z, codebook, mask, (int64_t)B * HW, D, HW, K, false, beta, zq, codes, loss, ws, ws_bytes, stream);
+}
+
+int dvq_vq_assign_narrow_flat_f32(const float *z, const float *codebook, const float *mask, int64_t N, int D, int K, float beta,
+                                  float *zq, int64_t *codes, float *loss, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_vq_assign_narrow_flat_f32";
+    if (!z || !codebook || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (N <= 0 || K <= 0) { dvq_set_error("%s: N=%lld K=%d must be positive", fn, (long long)N, K); return DVQ_EINVAL; }
+    return narrow_common(fn, z, codebook, mask, N, D, 1, K, true, beta, zq, codes, loss, ws, ws_bytes, stream);
 }
 
 }  // extern "C"

@@ -18,8 +18,15 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, qconv
-from .quantize import VectorQuantize2, vq_assign_routed_dual, vq_assign_routed_triple
+from .quantize import NARROW_WIDTHS, VectorQuantize2, vq_assign_routed_dual, vq_assign_routed_triple
 from .router import DualGrainFixedEntropyRouter, route_select_dual, route_select_dual_entropy, route_select_triple
+
+
+def _refuse_narrow_fold(fold, feat):
+    """fold=True is an explicit request: at a narrow width (3, 4, 8, 16 channels: the exact narrow assign, which has no routed,
+    fused or folded form) it raises instead of quietly taking select -> quant_conv -> assign, which is what fold=False does"""
+    if fold and feat.dim() == 4 and (feat.shape[1] == 3 or feat.shape[1] in NARROW_WIDTHS):
+        raise _lib.DvqError("fold=True: the folded quant_conv needs a kernel width (64, 128, 256 channels), got %d" % feat.shape[1])
 
 
 def _can_route(quantize, quant_conv, *feats):
@@ -87,6 +94,7 @@ def encode_dual(router, quantize, h_fine, h_coarse, entropy=None, quant_conv=Non
       * a 1x1 quant_conv on 256 channels: the same ONE op with the conv as its prologue (h_dual and the conv's output are
         never written); other channel counts: select + conv as one kernel, then the dense assign;
     otherwise route select -> quant_conv -> dense assign as differentiable pieces."""
+    _refuse_narrow_fold(fold, h_coarse)
     fixed = isinstance(router, DualGrainFixedEntropyRouter) and entropy is not None and entropy.is_cuda
     if fold and _can_fold(quantize, quant_conv, h_coarse, h_fine):
         cb = quantize.codebook
@@ -142,6 +150,7 @@ def encode_dual(router, quantize, h_fine, h_coarse, entropy=None, quant_conv=Non
 def encode_triple(router, quantize, h_fine, h_median, h_coarse, quant_conv=None, temp=0.0, fold=False):
     """-> (quant, emb_loss, info, grain_indices, gate) as TripleGrainVQModel.encode (dqvae_triple_feat.py:68-77).
     fold=True: see encode_dual (emb_loss = None)."""
+    _refuse_narrow_fold(fold, h_coarse)
     gate = router(h_fine=h_fine, h_median=h_median, h_coarse=h_coarse, entropy=None)
     if fold and _can_fold(quantize, quant_conv, h_coarse, h_median, h_fine):
         cb = quantize.codebook
@@ -174,6 +183,7 @@ def encode_fixed(quantize, h, quant_conv=None, fold=False):
     """-> (quant, emb_loss, info) as VQModel.encode (fixed granularity, models/stage1/vqgan.py:68-72).  An eval-mode
     VectorQuantize2 behind a 1x1 conv on 256 channels runs as one op (the conv is the assign's prologue).
     fold=True: the conv folded into the codebook (emb_loss = None), see encode_dual."""
+    _refuse_narrow_fold(fold, h)
     if fold and quant_conv is not None and h.dim() == 4 and _can_fold(quantize, quant_conv, h):
         from .quantize import vq_assign
         cb = quantize.codebook

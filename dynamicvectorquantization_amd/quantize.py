@@ -253,22 +253,37 @@ def _restart_pick(n, k, device):
     return out
 
 
-KERNEL_WIDTHS = (64, 128, 256)          # channel counts the assign kernels are instantiated for
+KERNEL_WIDTHS = (64, 128, 256)          # channel counts the wide (matrix-core) assign kernels are instantiated for
+NARROW_WIDTHS = (4, 8, 16)              # channel counts of the exact narrow assign kernel (vq_assign_narrow.hip); 3 runs at 4
 
 
 def _padded_width(D):
-    """the kernel width a codebook of D channels runs at: D itself, or -- D a multiple of 32 below 256 -- the next kernel width
-    with ZERO channels appended to latents and codebook.  That is exact, not approximate: a zero channel adds fma(0, 0, acc) =
-    acc to the sequential dot chain and + 0 to a partial sum of the norm whose 32-way grouping does not depend on D, so distances,
+    """the kernel width a codebook of D channels runs at: D itself (64, 128, 256: the wide kernels; 4, 8, 16: the narrow kernel of
+    the hard L2 assign, vq_assign), or the next kernel width with ZERO channels appended to latents and codebook -- D a multiple
+    of 32 below 256 -> 64 / 128 / 256, D = 3 -> 4.  That is exact, not approximate: a zero channel adds fma(0, 0, acc) =
+    acc to the sequential dot chain and + 0 to a partial sum of the norm whose grouping does not depend on D, so distances,
     codes and z_q are the reference's bit for bit (pinned for D = 32, 96, 160, 192, 224 by oracle/validate_against_reference.py
-    and tests/test_gpu_parity.py).  Other widths (not a multiple of 32: ATen's reduction order for the tail is not pinned; above
-    256: no kernel) raise."""
-    if D in KERNEL_WIDTHS:
+    and tests/test_gpu_parity.py; for D = 3, 4, 8, 16 by tools/gen_golden_narrow.py and tests/test_narrow_width.py).  Other
+    widths (torch-CPU's reduction order there is not the oracle's -- D = 12 and 48 were probed and differ -- or not pinned;
+    above 256: no kernel) raise."""
+    if D in KERNEL_WIDTHS or D in NARROW_WIDTHS:
         return D
+    if D == 3:
+        return 4
     if D > 0 and D % 32 == 0 and D < KERNEL_WIDTHS[-1]:
         return min(w for w in KERNEL_WIDTHS if w >= D)
     raise _lib.DvqError("codebook_dim %d: the MI355X kernels serve 64, 128 and 256 channels, and 32, 96, 160, 192, 224 by exact "
-                        "zero padding; other widths are not supported (INTEGRATION.md)" % D)
+                        "zero padding; the hard L2 assign also serves the narrow widths 4, 8, 16, and 3 by one zero channel; other "
+                        "widths are not supported (INTEGRATION.md)" % D)
+
+
+def _wide_width(D, what):
+    """_padded_width for the ops that have no narrow kernel (soft / scored / sampled assign, given codes below 16 channels,
+    residual quantization): 3, 4, 8 and 16 channels raise, naming the op and the width"""
+    if D == 3 or D in NARROW_WIDTHS:
+        raise _lib.DvqError("%s: codebook_dim %d is a narrow width, which only the hard L2 assign (vq_assign) serves; this op needs "
+                            "64, 128 or 256 channels, or a multiple of 32 below 256 (INTEGRATION.md)" % (what, D))
+    return _padded_width(D)
 
 
 def _vq_assign_padded(z, codebook, prep, mask, beta, want_zq, want_loss, mode, out, Dp):
@@ -297,6 +312,8 @@ def vq_assign(z, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=T
 
     loss[0] = mean((e - z)^2 * mask), loss[1] = beta*mean + mean.  `out` may carry preallocated
     (zq, codes, loss) tensors (used by the benchmark / graph capture).
+    Narrow widths (D = 4, 8, 16; 3 by a zero channel): the exact kernel of `dvq_vq_assign_narrow_nchw_f32` / `_flat_f32`, same
+    outputs bit for bit with the reference's CPU path; `mode` is ignored there, conv= / fold= raise.
     conv: a 1x1 nn.Conv2d(256, 256) applied to z first INSIDE the assign kernel (`dvq_vq_assign_qconv_f32`: the model's
     quant_conv; its output never reaches memory).  h_buf: see _conv_args.
     fold=True (needs conv, want_loss=False): the conv FOLDED into the codebook (`dvq_vq_assign_fold_f32`; loss-free inference /
@@ -318,9 +335,9 @@ def vq_assign(z, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=T
         if mask.numel() != B * HW:
             raise ValueError("codebook_mask has %d elements, expected B*H*W = %d" % (mask.numel(), B * HW))
     Dp = _padded_width(D)
+    if (Dp != D or D in NARROW_WIDTHS) and (conv is not None or fold) and B * HW > 0:
+        raise _lib.DvqError("the fused / folded quant_conv needs a kernel width (64, 128, 256 channels), got %d" % D)
     if Dp != D and B * HW > 0:
-        if conv is not None or fold:
-            raise _lib.DvqError("the fused / folded quant_conv needs a kernel width (64, 128, 256 channels), got %d" % D)
         return _vq_assign_padded(z, codebook, prep, mask, beta, want_zq, want_loss, mode, out, Dp)
     if out is not None:
         zq, codes, loss = out
@@ -332,6 +349,22 @@ def vq_assign(z, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=T
         # empty batch: what the reference's torch ops give (empty codes / z_q, mean of nothing = NaN)
         if loss is not None:
             loss.fill_(float("nan"))
+        return zq, codes, loss
+    if D in NARROW_WIDTHS:
+        # the exact narrow kernel: no prepared image, no modes (`mode` is accepted and ignored); row-major [N, D] by the flat form
+        ws_ptr, ws_bytes = 0, 0
+        if loss is not None:
+            ws = prep.workspace(B, D, HW, K, "narrow", z.device, nbytes=_lib_handle.dvq_vq_assign_narrow_workspace_bytes(B * HW))
+            ws_ptr, ws_bytes = ws.t.data_ptr(), ws.t.numel()
+        with _lib.on_device(z.device):
+            if HW == 1:
+                _lib.check(_lib_handle.dvq_vq_assign_narrow_flat_f32(
+                    z.data_ptr(), codebook.data_ptr(), _lib.ptr(mask), B, D, K, float(beta), _lib.ptr(zq), codes.data_ptr(),
+                    _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(z.device)), "dvq_vq_assign_narrow_flat_f32")
+            else:
+                _lib.check(_lib_handle.dvq_vq_assign_narrow_nchw_f32(
+                    z.data_ptr(), codebook.data_ptr(), _lib.ptr(mask), B, D, HW, K, float(beta), _lib.ptr(zq), codes.data_ptr(),
+                    _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(z.device)), "dvq_vq_assign_narrow_nchw_f32")
         return zq, codes, loss
     ws = prep.workspace(B, D, HW, K, mode, z.device)
     if fold:
@@ -399,7 +432,7 @@ def soft_assign(x, codebook, prep, temp=1.0, q=None, want_soft=True, want_dist=F
     codes = torch.empty(lead, dtype=torch.int64, device=dev)
     if N == 0:
         return soft, codes, dist
-    Dp = _padded_width(D)
+    Dp = _wide_width(D, "soft_assign")
     if Dp != D:
         xp = flat.new_zeros((N, Dp))
         xp[:, :D] = flat
@@ -455,7 +488,7 @@ def score_assign(x, codebook, prep, metric=_lib.METRIC_L2, temp=0.0, u=None):
     codes = torch.empty((B,) + tuple(x.shape[2:]), dtype=torch.int64, device=dev)
     if B * HW == 0:
         return codes
-    Dp = _padded_width(D)
+    Dp = _wide_width(D, "score_assign")
     if Dp != D:
         x, codebook = _pad_channels(x, Dp), prep.padded_codebook(codebook, Dp)
     with _lib.on_device(dev):
@@ -492,7 +525,7 @@ def apply_codes(z, codes, codebook, prep, mask=None, beta=0.25, want_zq=True, wa
         loss = torch.full((2,), float("nan"), dtype=torch.float32, device=dev) if want_loss else None
         return (torch.empty_like(z) if want_zq else None), loss
     if D % 16 != 0:                                         # (32-channel multiples are; anything else has no assign kernel either)
-        _padded_width(D)
+        _wide_width(D, "apply_codes")
     zq = torch.empty_like(z) if want_zq else None
     loss = torch.empty(2, dtype=torch.float32, device=dev) if want_loss else None
     ws_ptr, ws_bytes = 0, 0
@@ -660,6 +693,8 @@ def embed_gather(codebook, idx):
         idx = idx.long()
     idx = idx.contiguous()
     K, D = codebook.shape
+    if D == 3:                                              # the one served width the gather kernel's 16-byte rows do not fit
+        return codebook[idx]
     out = torch.empty(tuple(idx.shape) + (D,), dtype=torch.float32, device=codebook.device)
     with _lib.on_device(codebook.device):
         _lib.check(_lib_handle.dvq_embed_gather_f32(codebook.data_ptr(), K, D, idx.data_ptr(), idx.numel(),

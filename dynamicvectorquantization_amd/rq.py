@@ -21,7 +21,7 @@ from torch import nn
 from torch.nn import functional as F
 
 from . import _lib
-from .quantize import VQEmbedding, _padded_width, soft_assign, vq_assign
+from .quantize import VQEmbedding, _wide_width, soft_assign, vq_assign
 
 try:
     from collections.abc import Iterable
@@ -47,7 +47,7 @@ class _RQGeom:
         self.D = rH * rW * Dl
         self.N = B * self.h * self.w
         self.depth = int(mod.code_shape[-1])
-        _padded_width(self.D)                         # DvqError for widths the assign does not serve
+        _wide_width(self.D, "RQBottleneck")           # DvqError for widths the residual kernels do not serve
         if self.depth > _lib.RQ_MAX_DEPTH:
             raise _lib.DvqError("RQBottleneck: depth %d above the kernels' limit %d" % (self.depth, _lib.RQ_MAX_DEPTH))
 

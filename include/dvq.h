@@ -26,8 +26,12 @@
  *     fma(0, 0, acc) = acc to the dot chain and + 0 to the norm's partial sums, whose 32-way
  *     grouping does not depend on D -- which is what the Python drop-in does
  *     (quantize.py: _padded_width); divide the returned loss mean by D / D_padded.
+ *     The NARROW widths 4, 8 and 16 (and 3, as 4 with one zero channel) have entry points of their own,
+ *     dvq_vq_assign_narrow_*_f32 below; every other entry point refuses them as before.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.14.0 dvq_vq_assign_narrow_workspace_bytes, dvq_vq_assign_narrow_tile_codes, dvq_vq_assign_narrow_nchw_f32,
+ *          dvq_vq_assign_narrow_flat_f32 (new): the exact assign at the narrow widths D = 4, 8, 16 (3 by one zero channel).  Nothing else changed.
  *   0.13.0 dvq_gumbel_prep_bytes, dvq_gumbel_prepare_f32, dvq_vq_gumbel_assign_workspace_bytes, dvq_vq_gumbel_assign_f32 (new): GumbelQuantize's
  *          hard forward -- projection, Gumbel argmax, KL term and z_q -- as one sweep.  Nothing else changed.
  *   0.12.0 dvq_vq_score_assign_f32, dvq_vq_apply_codes_nchw_f32, dvq_vq_apply_codes_flat_f32 (new), DVQ_METRIC_L2 / DVQ_METRIC_DOT: the
@@ -783,6 +787,42 @@ DVQ_API size_t dvq_vq_gumbel_assign_workspace_bytes(int B, int HW);
 DVQ_API int dvq_vq_gumbel_assign_f32(const float *z, const void *prep, const float *embed, int B, int C, int HW, int K, int d,
                                      float tau, float kl_K, const float *q, float *zq, int64_t *codes, float *kl,
                                      void *ws, size_t ws_bytes, void *stream);
+
+/*
+ * Nearest-codebook assignment at the NARROW widths D = 4, 8, 16: codes, z_q and the commitment loss in one exact kernel.
+ * Replaces: the same reference ops as dvq_vq_assign_nchw_f32 / dvq_vq_assign_flat_f32 -- VectorQuantize2.forward
+ *           (quantize2_mask.py:157-191 around VQEmbedding.compute_distances :29-48, find_nearest_embedding :50-55, embed :130-132)
+ *           and VectorQuantizer2.forward (quantize_vqgan.py:271-312) -- for taming-style checkpoints (embed_dim 3 or 4,
+ *           K = 8192 / 16384) and factorised low-dimensional codebooks.  No prepared codebook image: the kernel stages the
+ *           codebook rows itself and computes their norms while it does.
+ *   z        _nchw: [B, D, HW] read in place, any HW, 4-byte aligned;  _flat: row-major [N, D], 16-byte aligned
+ *   codebook [K, D], 16-byte aligned (for VQEmbedding pass weight[:-1])
+ *   mask     nullable [B, HW] / [N]
+ *   zq       nullable, the layout (and, _flat, the alignment) of z:  fl(z + fl(e - z))
+ *   codes    [B, HW] / [N] int64: first-index argmin, NaN = minimum (torch CPU semantics)
+ *   loss     nullable [2] f32: loss[0] = mean((e-z)^2*mask), loss[1] = fl(fl(beta*mean)+mean)
+ *   ws       only when loss is wanted: >= dvq_vq_assign_narrow_workspace_bytes(N) (N = B * HW; 0 for N <= 0), 256-byte aligned
+ * Every (token, code) distance is the reference's fp32 arithmetic bit for bit: acc = fma(z[k], e[k], acc) for k ascending from 0,
+ * d = fl(fl(xn + en) - 2 acc), with xn / en = torch-CPU's sum of squares at these widths (D <= 8: the sequential sum of the
+ * rounded squares; D = 16: t[l] = sq[l] + sq[l + 8], then t[0] + ... + t[7] left to right) -- pinned on the reference by
+ * tests/golden/narrow_D*.npz.  D = 3: append one zero channel to latents and codebook and run at 4 (exact: fma(0, 0, acc) = acc,
+ * + 0 in the norm); multiply loss[0] by 4 / 3.  The Python drop-in does this.
+ * The codebook is walked in LDS tiles of dvq_vq_assign_narrow_tile_codes(D) codes (0 for an unsupported D); K need not be a
+ * multiple.  Every workgroup walks the whole codebook for its tokens: 256 tokens per workgroup, 64 up to DVQ_NARROW_SMALL_N tokens
+ * (same arithmetic, same results; a small batch fills more of the chip).  K < 2^20, N < 2^31: DVQ_EUNSUPPORTED beyond, as is D outside {4, 8, 16}.  DVQ_EINVAL: null z / codebook / codes, a
+ * non-positive size, a misaligned pointer, a missing or too small workspace when loss is wanted.
+ * Two launches (the assign, the loss finalize when loss is wanted) on one stream: one double partial per workgroup added in a
+ * fixed order -- no atomics, the same bits every run; no host synchronisation, no allocation.  Vector stores only.
+ */
+#define DVQ_NARROW_SMALL_N 65536    /* up to this many tokens: 64 per workgroup (one wave); above: 256 (two waves, two tokens per lane) */
+DVQ_API size_t dvq_vq_assign_narrow_workspace_bytes(int64_t N);
+DVQ_API int dvq_vq_assign_narrow_tile_codes(int D);
+DVQ_API int dvq_vq_assign_narrow_nchw_f32(const float *z, const float *codebook, const float *mask, int B, int D, int HW, int K,
+                                          float beta, float *zq, int64_t *codes, float *loss, void *ws, size_t ws_bytes,
+                                          void *stream);
+DVQ_API int dvq_vq_assign_narrow_flat_f32(const float *z, const float *codebook, const float *mask, int64_t N, int D, int K,
+                                          float beta, float *zq, int64_t *codes, float *loss, void *ws, size_t ws_bytes,
+                                          void *stream);
 
 /*
  * Wire format of the image-parallel exchange (one all-gather per batch; the reference gathers nothing --
