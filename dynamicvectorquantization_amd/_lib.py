@@ -58,6 +58,7 @@ EXPORTS = (
     "dvq_gumbel_prep_bytes", "dvq_gumbel_prepare_f32", "dvq_vq_gumbel_assign_workspace_bytes", "dvq_vq_gumbel_assign_f32",
     "dvq_vq_assign_narrow_workspace_bytes", "dvq_vq_assign_narrow_tile_codes", "dvq_vq_assign_narrow_nchw_f32",
     "dvq_vq_assign_narrow_flat_f32",
+    "dvq_code_stats_f32", "dvq_code_stats_grain_f32",
 )
 
 
@@ -248,6 +249,10 @@ def _load():
     lib.dvq_vq_assign_narrow_nchw_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]
     lib.dvq_vq_assign_narrow_flat_f32.restype = i32
     lib.dvq_vq_assign_narrow_flat_f32.argtypes = [vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp, sz, vp]
+    lib.dvq_code_stats_f32.restype = i32
+    lib.dvq_code_stats_f32.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
+    lib.dvq_code_stats_grain_f32.restype = i32
+    lib.dvq_code_stats_grain_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
     return lib
 
 

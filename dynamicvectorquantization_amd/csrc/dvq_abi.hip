@@ -7,7 +7,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 1400   // 0.14.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1500   // 0.15.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -80,6 +80,10 @@ int dvq_launch_decode_head(const long long *codes, int B, int HW, const float *T
                            float *out, hipStream_t st);
 int dvq_launch_ema_accumulate(const float *z, const long long *codes, int D, int HW, long N, int K,
                               float *cluster_size, float *vectors_sum, hipStream_t st);
+int dvq_launch_code_stats(const long long *codes, long N, int K, long long *counts, long long *n_used, float *perplexity,
+                          float *onehot, hipStream_t st);
+int dvq_launch_code_stats_grain(const long long *codes, const long long *grain, int B, int H, int W, int hc, int wc, int G, int K,
+                                long long *counts, long long *n_tokens, long long *n_used, float *perplexity, hipStream_t st);
 int dvq_launch_entropy_map(const float *img, int B, int H, int W, float *out, hipStream_t st);
 size_t dvq_router_gate_ws_bytes(int nb, int B, int C, int hc, int wc, int groups, int Hid);
 size_t dvq_router_gate_prep_bytes_impl(int nb, int C, int Hid);
@@ -610,6 +614,31 @@ int dvq_ema_accumulate_nchw_f32(const float *z, const int64_t *codes, int B, int
     if (B <= 0 || D <= 0 || HW <= 0 || K <= 0) { dvq_set_error("dvq_ema_accumulate_nchw_f32: sizes must be positive"); return DVQ_EINVAL; }
     return hip_rc(dvq_launch_ema_accumulate(z, (const long long *)codes, D, HW, (long)B * HW, K, cluster_size, vectors_sum,
                                             (hipStream_t)stream), "ema_accumulate");
+}
+
+int dvq_code_stats_f32(const int64_t *codes, int64_t N, int K, int64_t *counts, int64_t *n_used, float *perplexity, float *onehot,
+                       void *stream)
+{
+    if (!counts || !n_used || !perplexity || (!codes && N > 0)) { dvq_set_error("dvq_code_stats_f32: null pointer"); return DVQ_EINVAL; }
+    if (K < 1 || N < 0) { dvq_set_error("dvq_code_stats_f32: K=%d N=%lld (K >= 1, N >= 0)", K, (long long)N); return DVQ_EINVAL; }
+    if (K >= (1 << 20)) { dvq_set_error("dvq_code_stats_f32: K=%d (K < 2^20)", K); return DVQ_EUNSUPPORTED; }
+    return hip_rc(dvq_launch_code_stats((const long long *)codes, (long)N, K, (long long *)counts, (long long *)n_used, perplexity, onehot,
+                                        (hipStream_t)stream), "code_stats");
+}
+
+int dvq_code_stats_grain_f32(const int64_t *codes, const int64_t *grain, int B, int H, int W, int hc, int wc, int G, int K,
+                             int64_t *counts, int64_t *n_tokens, int64_t *n_used, float *perplexity, void *stream)
+{
+    const char *fn = "dvq_code_stats_grain_f32";
+    if (!codes || !grain || !counts || !n_tokens || !n_used || !perplexity) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (B < 1 || hc < 1 || wc < 1 || K < 1 || (G != 2 && G != 3)) { dvq_set_error("%s: B=%d hc=%d wc=%d K=%d G=%d (sizes >= 1, G 2 or 3)", fn, B, hc, wc, K, G); return DVQ_EINVAL; }
+    const int S = 1 << (G - 1);
+    if (hc > (1 << 20) || wc > (1 << 20) || H != hc * S || W != wc * S) {
+        dvq_set_error("%s: codes %d x %d against a %d x %d grain map: G=%d needs exactly %d x the cells", fn, H, W, hc, wc, G, S); return DVQ_EINVAL;
+    }
+    if (K >= (1 << 20) || (int64_t)B * H * W >= ((int64_t)1 << 31)) { dvq_set_error("%s: K=%d B*H*W=%lld (K < 2^20, B*H*W < 2^31)", fn, K, (long long)B * H * W); return DVQ_EUNSUPPORTED; }
+    return hip_rc(dvq_launch_code_stats_grain((const long long *)codes, (const long long *)grain, B, H, W, hc, wc, G, K, (long long *)counts,
+                                              (long long *)n_tokens, (long long *)n_used, perplexity, (hipStream_t)stream), "code_stats_grain");
 }
 
 int dvq_restart_pick_i64(uint64_t seed, int64_t n, int k, int64_t *out, void *stream)

@@ -4,6 +4,7 @@ Mirrors (constructor kwargs, forward signature, return structure, state_dict key
   * VQEmbedding / VectorQuantize2  -- reference modules/vector_quantization/quantize2_mask.py:10-210
     (also covers quantize2.py: identical class without the mask argument)
   * VectorQuantizer2               -- reference modules/vector_quantization/quantize_vqgan.py:213-341
+  * VectorQuantizer, EMAVectorQuantizer (EmbeddingEMA) -- quantize_vqgan.py:9-107, :343-457; VectorQuantizer2Seq -- modules/vqvae/quantize2.py
 so a reference YAML selects them by changing only the `target:` string, e.g.
   target: dynamicvectorquantization_amd.quantize.VectorQuantize2
 
@@ -1715,3 +1716,283 @@ class GumbelQuantize(InvalidatesPrepared, nn.Module):
         if self.remap is not None:
             indices = self.unmap_to_all(indices)
         return self.embed(indices).permute(0, 3, 1, 2).contiguous()
+
+
+class CodeUsage:
+    """what `code_usage` returns: counts ([K] int64, or [G, K] per grain), perplexity (f32 scalar / [G]), n_used and n_tokens
+    (int64 scalar / [G]) and encodings ([N, K] f32 one-hot, or None) -- all GPU tensors, nothing is synchronised"""
+    __slots__ = ("counts", "perplexity", "n_used", "n_tokens", "encodings")
+
+    def __init__(self, counts, perplexity, n_used, n_tokens, encodings=None):
+        self.counts, self.perplexity, self.n_used, self.n_tokens, self.encodings = counts, perplexity, n_used, n_tokens, encodings
+
+    def __repr__(self):
+        return "CodeUsage(K=%d, counts %s, encodings %s)" % (self.counts.shape[-1], tuple(self.counts.shape),
+                                                             None if self.encodings is None else tuple(self.encodings.shape))
+
+
+def code_usage(codes, K, grain_indices=None, want_encodings=False):
+    """How a batch uses the codebook, in one sweep over the codes (`dvq_code_stats_f32`; csrc/code_stats.hip): codes -- an int64
+    GPU tensor of any shape, values outside [0, K) are ignored -- -> CodeUsage(counts [K], perplexity, n_used, n_tokens,
+    encodings).  perplexity = exp(-sum p log(p + 1e-10)), p = counts / N: the statistic VectorQuantizer / EMAVectorQuantizer
+    return, a pure function of the counts (the same bits on every run).  want_encodings: also the one-hot matrix [N, K] f32
+    (written once, streaming stores).
+
+    grain_indices [B, hc, wc] int64 (the `indices` a dual / triple granularity encoder returns, 0 = coarsest) with codes
+    [B, H, W], H / hc = W / wc = 2 (dual) or 4 (triple): the statistics PER GRAIN (`dvq_code_stats_grain_f32`), every region of
+    the token stream counted once as the permuter emits it -- counts [G, K], the others [G]; a grain without tokens has
+    perplexity 1.  want_encodings raises there.  CPU tensors raise DvqError, as everywhere in this package."""
+    if not isinstance(codes, torch.Tensor):
+        raise TypeError("codes must be a torch.Tensor")
+    if not codes.is_cuda:
+        raise _lib.DvqError("codes is on %s: the dvq kernels run on the GPU only (no CPU fallback)" % codes.device)
+    if codes.dtype != torch.int64:
+        raise TypeError("codes must be int64, got %s" % codes.dtype)
+    K = int(K)
+    if K < 1:
+        raise ValueError("K must be >= 1, got %d" % K)
+    codes = codes.contiguous()
+    dev = codes.device
+    if grain_indices is None:
+        N = codes.numel()
+        counts = torch.empty(K, dtype=torch.int64, device=dev)
+        n_used = torch.empty((), dtype=torch.int64, device=dev)
+        perp = torch.empty((), dtype=torch.float32, device=dev)
+        onehot = torch.empty((N, K), dtype=torch.float32, device=dev) if want_encodings else None
+        with _lib.on_device(dev):
+            _lib.check(_lib_handle.dvq_code_stats_f32(codes.data_ptr(), N, K, counts.data_ptr(), n_used.data_ptr(), perp.data_ptr(),
+                                                      _lib.ptr(onehot), _lib.stream_ptr(dev)), "dvq_code_stats_f32")
+        return CodeUsage(counts, perp, n_used, torch.full((), N, dtype=torch.int64, device=dev), onehot)
+    if want_encodings:
+        raise ValueError("want_encodings is not available with grain_indices (the one-hot matrix is per token, not per region)")
+    g = grain_indices
+    if not isinstance(g, torch.Tensor) or not g.is_cuda:
+        raise _lib.DvqError("grain_indices must be a GPU tensor (no CPU fallback)")
+    if g.dtype != torch.int64:
+        raise TypeError("grain_indices must be int64, got %s" % g.dtype)
+    if codes.dim() != 3 or g.dim() != 3 or g.shape[0] != codes.shape[0] or g.numel() == 0:
+        raise ValueError("codes must be [B, H, W] and grain_indices [B, hc, wc], got %s and %s" % (tuple(codes.shape), tuple(g.shape)))
+    B, H, W = codes.shape
+    hc, wc = g.shape[1:]
+    ratio = H // hc
+    if ratio not in (2, 4) or H != hc * ratio or W != wc * ratio:
+        raise ValueError("codes %s against grain_indices %s: the code map must be 2 x (dual) or 4 x (triple) the grain map" %
+                         (tuple(codes.shape), tuple(g.shape)))
+    G = 2 if ratio == 2 else 3
+    g = g.contiguous()
+    counts = torch.empty((G, K), dtype=torch.int64, device=dev)
+    small = torch.empty((2, G), dtype=torch.int64, device=dev)
+    perp = torch.empty(G, dtype=torch.float32, device=dev)
+    with _lib.on_device(dev):
+        _lib.check(_lib_handle.dvq_code_stats_grain_f32(codes.data_ptr(), g.data_ptr(), B, H, W, hc, wc, G, K, counts.data_ptr(),
+                                                        small[0].data_ptr(), small[1].data_ptr(), perp.data_ptr(),
+                                                        _lib.stream_ptr(dev)), "dvq_code_stats_grain_f32")
+    return CodeUsage(counts, perp, small[1], small[0], None)
+
+
+class VectorQuantizer(InvalidatesPrepared, nn.Module):
+    """Reference modules/vector_quantization/quantize_vqgan.py:9-107 (the original VQ-VAE bottleneck).
+      target: dynamicvectorquantization_amd.quantize.VectorQuantizer
+
+    forward(z [B, C, H, W]) -> (z_q, loss, (perplexity, min_encodings [N, n_e], min_encoding_indices [N, 1])).  The op is the one
+    VectorQuantizer2(legacy=True) runs -- loss = mean((z_q.detach() - z)^2) + beta * mean((z_q - z.detach())^2), the same
+    autograd -- plus one `code_usage` sweep for the perplexity and the one-hot matrix, outside autograd.  The reference forms
+    z_q = min_encodings @ embedding.weight, a dense [N, n_e] x [n_e, D] product; for finite weights that product IS the gather
+    (a row of it is 1 * w[code] plus exact zeros), which is what the assign kernel writes.  (A non-finite weight row makes the
+    reference's product NaN for every token, 0 * inf; the gather confines it to the tokens that chose the row.)
+    `want_encodings = False` (the one knob the reference does not have) returns None for the one-hot and skips its N x n_e write."""
+    _prepared = ("_prep",)
+    want_encodings = True
+
+    def __init__(self, n_e, e_dim, beta):
+        super().__init__()
+        self.n_e = n_e
+        self.e_dim = e_dim
+        self.beta = beta
+        self.embedding = nn.Embedding(self.n_e, self.e_dim)
+        self.embedding.weight.data.uniform_(-1.0 / self.n_e, 1.0 / self.n_e)
+        self._prep = _CodebookPrep()
+        self.assign_mode = _lib.MODE_FILTER
+
+    def invalidate_codebook_cache(self):
+        """call after writing embedding.weight through `.data` in eval mode"""
+        self._prep.invalidate()
+
+    def forward(self, z):
+        if z.dim() != 4:
+            raise ValueError("VectorQuantizer expects z [B, C, H, W]")
+        if self.training:
+            self._prep.invalidate()                      # the optimizer may have stepped through .data
+        self._prep.track_users = self.training
+        z_q, loss, codes = _vq_straight_through(z, self.embedding.weight, None, self._prep, self.n_e,
+                                                    1.0, float(self.beta), self.assign_mode)
+        with torch.no_grad():
+            use = code_usage(codes.reshape(-1), self.n_e, want_encodings=bool(self.want_encodings))
+        return z_q, loss, (use.perplexity, use.encodings, codes.reshape(-1, 1))
+
+    def get_codebook_entry(self, indices, shape):
+        """indices [N] -> rows of the codebook (the reference's one-hot product: the gather); shape (b, h, w, c) or None.
+        On the GPU the gather kernel records no autograd: unlike the reference's `one_hot.float() @ weight` the result carries no
+        gradient to embedding.weight (as VectorQuantizer2.get_codebook_entry here; CPU indices go through nn.Embedding)."""
+        z_q = embed_gather(self.embedding.weight, indices) if indices.is_cuda else self.embedding(indices)
+        if shape is not None:
+            z_q = z_q.view(shape)
+            z_q = z_q.permute(0, 3, 1, 2).contiguous()
+        return z_q
+
+
+class EmbeddingEMA(nn.Module):
+    """Reference quantize_vqgan.py:343-370: weight, cluster_size, embed_avg as frozen Parameters (the reference's state_dict
+    keys), `update` a plain attribute.  The three update methods are the reference's torch expressions; EMAVectorQuantizer's
+    training forward runs them as one kernel instead (`dvq_ema_update_f32`)."""
+
+    def __init__(self, num_tokens, codebook_dim, decay=0.99, eps=1e-5):
+        super().__init__()
+        self.decay = decay
+        self.eps = eps
+        weight = torch.randn(num_tokens, codebook_dim)
+        self.weight = nn.Parameter(weight, requires_grad=False)
+        self.cluster_size = nn.Parameter(torch.zeros(num_tokens), requires_grad=False)
+        self.embed_avg = nn.Parameter(weight.clone(), requires_grad=False)
+        self.update = True
+
+    def forward(self, embed_id):
+        if embed_id.is_cuda:
+            return embed_gather(self.weight, embed_id)
+        return F.embedding(embed_id, self.weight)
+
+    def cluster_size_ema_update(self, new_cluster_size):
+        self.cluster_size.data.mul_(self.decay).add_(new_cluster_size, alpha=1 - self.decay)
+
+    def embed_avg_ema_update(self, new_embed_avg):
+        self.embed_avg.data.mul_(self.decay).add_(new_embed_avg, alpha=1 - self.decay)
+
+    def weight_update(self, num_tokens):
+        n = self.cluster_size.sum()
+        smoothed_cluster_size = (self.cluster_size + self.eps) / (n + num_tokens * self.eps) * n
+        self.weight.data.copy_(self.embed_avg / smoothed_cluster_size.unsqueeze(1))
+
+
+class EMAVectorQuantizer(InvalidatesPrepared, nn.Module):
+    """Reference quantize_vqgan.py:373-457 (taming's EMA codebook).
+      target: dynamicvectorquantization_amd.quantize.EMAVectorQuantizer
+
+    forward(z [B, C, H, W]) -> (z_q, loss = beta * mse(z_q.detach(), z), (perplexity, encodings [N, n_embed], encoding_indices [N])).
+    Training with `embedding.update` set, in this order: the assign on the OLD weight (z_q and the loss come from it, as in the
+    reference), the counts and sums of `dvq_ema_accumulate_nchw_f32` (the reference's encodings.sum(0) and encodings.T @ z), then
+    `dvq_ema_update_f32` without restarts into the three parameters -- its n (c + eps) / (n + K eps) is `weight_update`'s smoothed
+    cluster size in another order (1e-5) -- and the prepared codebook image is dropped.  The accumulate kernel takes every width
+    `_padded_width` serves, so no width trains differently from how it evaluates.
+    The reference's constructor crashes with remap= (it prints a `self.n_embed` that does not exist); here remap= registers `used`
+    and `remap_to_used` / `unmap_to_all` work as VectorQuantizer2's (forward does not remap, as in the reference).
+    `want_encodings = False` (not in the reference) returns None for the one-hot and skips its N x n_embed write."""
+    _prepared = ("_prep",)
+    want_encodings = True
+
+    def __init__(self, n_embed, embedding_dim, beta, decay=0.99, eps=1e-5, remap=None, unknown_index="random"):
+        super().__init__()
+        self.codebook_dim = embedding_dim
+        self.num_tokens = n_embed
+        self.beta = beta
+        self.embedding = EmbeddingEMA(self.num_tokens, self.codebook_dim, decay, eps)
+        self.remap = remap
+        if self.remap is not None:
+            import numpy as np
+            self.register_buffer("used", torch.tensor(np.load(self.remap)))
+            self.re_embed = self.used.shape[0]
+            self.unknown_index = unknown_index      # "random" or "extra" or integer
+            if self.unknown_index == "extra":
+                self.unknown_index = self.re_embed
+                self.re_embed = self.re_embed + 1
+        else:
+            self.re_embed = n_embed
+        self._prep = _CodebookPrep()
+        self.assign_mode = _lib.MODE_FILTER
+
+    @property
+    def n_e(self):
+        return self.num_tokens
+
+    remap_to_used = VectorQuantizer2.remap_to_used
+    unmap_to_all = VectorQuantizer2.unmap_to_all
+
+    def invalidate_codebook_cache(self):
+        """call after writing embedding.weight through `.data` outside the training forward"""
+        self._prep.invalidate()
+
+    @torch.no_grad()
+    def _ema_step(self, z, codes):
+        emb = self.embedding
+        K, D = self.num_tokens, self.codebook_dim
+        for name in ("weight", "cluster_size", "embed_avg"):
+            t = getattr(emb, name)
+            if not (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+                raise _lib.DvqError("EMAVectorQuantizer: embedding.%s must be a contiguous f32 GPU tensor" % name)
+        z = z.detach().contiguous()
+        B, HW = z.shape[0], z[0, 0].numel()
+        stats = torch.empty(K * D + K, dtype=torch.float32, device=z.device)
+        vsum, csize = stats[:K * D], stats[K * D:]
+        cs_new = torch.empty_like(emb.cluster_size.data)          # the update kernel's no-alias rule: every workgroup sums the OLD counts
+        with _lib.on_device(z.device):
+            st = _lib.stream_ptr(z.device)
+            _lib.check(_lib_handle.dvq_ema_accumulate_nchw_f32(z.data_ptr(), codes.data_ptr(), B, D, HW, K, csize.data_ptr(),
+                                                               vsum.data_ptr(), st), "dvq_ema_accumulate_nchw_f32")
+            _lib.check(_lib_handle.dvq_ema_update_f32(
+                vsum.data_ptr(), csize.data_ptr(), float(emb.decay), float(emb.eps), K, D, emb.cluster_size.data_ptr(),
+                cs_new.data_ptr(), emb.embed_avg.data_ptr(), emb.weight.data_ptr(), 0, 0, 0, B, HW, 0, st), "dvq_ema_update_f32")
+        emb.cluster_size.data.copy_(cs_new)
+        self._prep.invalidate()
+
+    def forward(self, z):
+        if z.dim() != 4:
+            raise ValueError("EMAVectorQuantizer expects z [B, C, H, W]")
+        if z.shape[1] != self.codebook_dim:
+            raise ValueError("channel dim %d != embedding_dim %d" % (z.shape[1], self.codebook_dim))
+        if self.training:
+            self._prep.invalidate()                      # load_state_dict / .data writers between steps
+        self._prep.track_users = self.training
+        # coefficients (1, 0): the op's loss output is 0 * m + m = m = mean((z_q.detach() - z)^2) exactly, its gradient 2 (z - e) / numel
+        z_q, mse, codes = _vq_straight_through(z, self.embedding.weight, None, self._prep, self.num_tokens, 1.0, 0.0,
+                                                   self.assign_mode)
+        flat = codes.reshape(-1)
+        with torch.no_grad():
+            use = code_usage(flat, self.num_tokens, want_encodings=bool(self.want_encodings))
+        if self.training and self.embedding.update:
+            self._ema_step(z, codes)
+        return z_q, self.beta * mse, (use.perplexity, use.encodings, flat)
+
+
+class VectorQuantizer2Seq(VectorQuantizer2):
+    """Reference modules/vqvae/quantize2.py:8-118: VectorQuantizer2 for sequences z [B, C, L].
+      target: dynamicvectorquantization_amd.quantize.VectorQuantizer2Seq
+
+    The NCHW assign kernel with HW = L reads [B, C, L] in place.  forward -> (z_q [B, C, L], loss, (None, None, indices [B * L],
+    or [B * L, 1] remapped)); get_codebook_entry(indices, shape = (batch, length, channel)) -> [batch, channel, length]."""
+
+    def __init__(self, n_e, e_dim, beta, remap=None, unknown_index="random", legacy=True):
+        super().__init__(n_e, e_dim, beta, remap=remap, unknown_index=unknown_index, sane_index_shape=False, legacy=legacy)
+
+    def forward(self, z, temp=None, rescale_logits=False, return_logits=False):
+        assert temp is None or temp == 1.0, "Only for interface compatible with Gumbel"
+        assert rescale_logits is False, "Only for interface compatible with Gumbel"
+        assert return_logits is False, "Only for interface compatible with Gumbel"
+        if z.dim() != 3:
+            raise ValueError("VectorQuantizer2Seq expects z [B, C, L]")
+        coef_z, coef_e = (1.0, float(self.beta)) if self.legacy else (float(self.beta), 1.0)
+        if self.training:
+            self._prep.invalidate()
+        self._prep.track_users = self.training
+        z_q, loss, codes = _vq_straight_through(z, self.embedding.weight, None, self._prep, self.n_e, coef_z, coef_e,
+                                                    self.assign_mode)
+        min_encoding_indices = codes.reshape(-1)
+        if self.remap is not None:
+            min_encoding_indices = self.remap_to_used(min_encoding_indices.reshape(z.shape[0], -1)).reshape(-1, 1)
+        return z_q, loss, (None, None, min_encoding_indices)
+
+    def get_codebook_entry(self, indices, shape):
+        if self.remap is not None:
+            indices = self.unmap_to_all(indices.reshape(shape[0], -1)).reshape(-1)
+        z_q = embed_gather(self.embedding.weight, indices) if indices.is_cuda else self.embedding(indices)
+        if shape is not None:
+            z_q = z_q.view(shape).permute(0, 2, 1).contiguous()
+        return z_q

@@ -30,6 +30,8 @@
  *     dvq_vq_assign_narrow_*_f32 below; every other entry point refuses them as before.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.15.0 dvq_code_stats_f32, dvq_code_stats_grain_f32 (new): code histogram, codes in use, perplexity and the optional one-hot matrix of
+ *          a batch of codes -- what VectorQuantizer / EMAVectorQuantizer return besides z_q -- and the same per grain.  Nothing else changed.
  *   0.14.0 dvq_vq_assign_narrow_workspace_bytes, dvq_vq_assign_narrow_tile_codes, dvq_vq_assign_narrow_nchw_f32,
  *          dvq_vq_assign_narrow_flat_f32 (new): the exact assign at the narrow widths D = 4, 8, 16 (3 by one zero channel).  Nothing else changed.
  *   0.13.0 dvq_gumbel_prep_bytes, dvq_gumbel_prepare_f32, dvq_vq_gumbel_assign_workspace_bytes, dvq_vq_gumbel_assign_f32 (new): GumbelQuantize's
@@ -408,6 +410,38 @@ DVQ_API int dvq_restart_pick_i64(uint64_t seed, int64_t n, int k, int64_t *out, 
 DVQ_API int dvq_ema_update_f32(const float *stats_sum, const float *stats_count, float decay, float eps, int K, int D,
                                const float *cluster_size_ema, float *cluster_size_out, float *embed_ema, float *weight,
                                int restart, const float *restart_rows, const float *z, int B, int HW, const int64_t *pick, void *stream);
+
+/*
+ * Code-usage statistics of a batch of codes, one sweep (code_stats.hip).  Replaces what VectorQuantizer / EMAVectorQuantizer build
+ * through a dense one-hot matrix (quantize_vqgan.py:58-60, 84-85 / :434-436: zeros + scatter_ or F.one_hot, mean(0), log, sum, exp) and
+ * the host-side sets of scripts/tools/codebook_usage*.py.
+ *   codes [N] int64 (may be NULL when N == 0); codes outside [0, K) are ignored (counted nowhere; their one-hot row is all zero).
+ *   counts [K] int64      exact: counts[j] = #n with codes[n] == j
+ *   n_used [1] int64      #j with counts[j] > 0
+ *   perplexity [1] f32    p_j = (float)counts[j] / (float)N (one fp32 division), t_j = p_j * logf(p_j + 1e-10f), H = sum of the t_j in
+ *                         double in one fixed order, perplexity = expf((float)(-H)): a pure function of the counts, the same bits on
+ *                         every run; within 1e-5 relative of the reference's exp(-sum(e_mean * log(e_mean + 1e-10))).  N == 0: 1.
+ *   onehot [N, K] f32     nullable; onehot[n, j] = codes[n] == j ? 1 : 0, every element written exactly once (16-byte non-temporal
+ *                         stores when K % 4 == 0 and the pointer is 16-byte aligned, 4-byte stores otherwise).
+ * All outputs are overwritten (the zeroing is part of the call); at most three kernel launches, no memset node, no host
+ * synchronisation, capturable in a HIP graph.  Integer atomics only: the counts do not depend on arrival order.
+ * DVQ_EINVAL: null counts / n_used / perplexity, null codes with N > 0, K < 1, N < 0.  DVQ_EUNSUPPORTED: K >= 2^20.
+ */
+DVQ_API int dvq_code_stats_f32(const int64_t *codes, int64_t N, int K, int64_t *counts, int64_t *n_used, float *perplexity,
+                               float *onehot, void *stream);
+
+/*
+ * The same statistics per GRAIN of a dual (G = 2) or triple (G = 3) granularity model: codes [B, H, W] int64, grain [B, hc, wc] int64 with
+ * values in [0, G), 0 = the coarsest (what the encoders return as `indices`).  H / hc == W / wc == 2^(G - 1) exactly (DVQ_EINVAL otherwise).
+ * Every region of the token stream is counted once, as the permuter emits it: with s = (H / hc) >> g for the cell's grain g, position
+ * (y, x) is counted iff y % s == 0 and x % s == 0, into row g.  Cells whose grain is outside [0, G) are ignored.
+ *   counts [G, K] int64, n_tokens [G] int64 (regions of that grain, whatever their code), n_used [G] int64, perplexity [G] f32 with
+ *   p = count / n_tokens[g]; a grain without tokens has n_used 0 and perplexity 1 (no 0 / 0).
+ * Launch properties and code range as dvq_code_stats_f32.  DVQ_EINVAL: null pointer, B / hc / wc / K < 1, G not 2 or 3, the shape rule.
+ * DVQ_EUNSUPPORTED: K >= 2^20 or B * H * W >= 2^31.
+ */
+DVQ_API int dvq_code_stats_grain_f32(const int64_t *codes, const int64_t *grain, int B, int H, int W, int hc, int wc, int G, int K,
+                                     int64_t *counts, int64_t *n_tokens, int64_t *n_used, float *perplexity, void *stream);
 
 /*
  * Fused feature-router gate (inference), the forward of DualGrainFeatureRouter
