@@ -59,6 +59,8 @@ EXPORTS = (
     "dvq_vq_assign_narrow_workspace_bytes", "dvq_vq_assign_narrow_tile_codes", "dvq_vq_assign_narrow_nchw_f32",
     "dvq_vq_assign_narrow_flat_f32",
     "dvq_code_stats_f32", "dvq_code_stats_grain_f32",
+    "dvq_vq_cdist_sample_assign_f32", "dvq_ortho_loss_workspace_bytes", "dvq_ortho_loss_forward_f32", "dvq_ortho_loss_backward_f32",
+    "dvq_lucid_update_f32",
 )
 
 
@@ -253,6 +255,16 @@ def _load():
     lib.dvq_code_stats_f32.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
     lib.dvq_code_stats_grain_f32.restype = i32
     lib.dvq_code_stats_grain_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
+    lib.dvq_vq_cdist_sample_assign_f32.restype = i32
+    lib.dvq_vq_cdist_sample_assign_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, i64, vp, vp]
+    lib.dvq_ortho_loss_workspace_bytes.restype = sz
+    lib.dvq_ortho_loss_workspace_bytes.argtypes = [i32, i32, i32]
+    lib.dvq_ortho_loss_forward_f32.restype = i32
+    lib.dvq_ortho_loss_forward_f32.argtypes = [vp, i32, i32, i32, vp, vp, vp, sz, vp]
+    lib.dvq_ortho_loss_backward_f32.restype = i32
+    lib.dvq_ortho_loss_backward_f32.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]
+    lib.dvq_lucid_update_f32.restype = i32
+    lib.dvq_lucid_update_f32.argtypes = [i32, vp, vp, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]
     return lib
 
 

@@ -7,7 +7,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 1500   // 0.15.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1600   // 0.16.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -117,6 +117,16 @@ int dvq_launch_soft_assign(const float *x, const float *prep, int D, int K, long
                            float *dist, float *sbuf, long long *codes, hipStream_t st);
 int dvq_launch_score_assign(const float *z, const float *prep, int D, int HW, int K, long N, int metric, float temp, const float *u,
                             long long *codes, hipStream_t st);
+int dvq_launch_cdist_sample_assign(const float *z, const float *prep, int D, int HW, int K, long N, float temp, const float *u,
+                                   long long *codes, hipStream_t st);
+void dvq_ortho_grid(int h, int n, unsigned *gx, unsigned *gy);
+int dvq_launch_ortho_forward(const float *t, int h, int n, int D, float *rinv, float *loss, double *partials, hipStream_t st);
+void dvq_ortho_backward_slices(int h, int n, int *S, int *tper);
+int dvq_launch_ortho_backward(const float *t, const float *rinv, const float *gout, int h, int n, int D, float *grad, float *gpart,
+                              hipStream_t st);
+int dvq_launch_lucid_update(int kind, const float *counts, const float *sums, float decay, float eps, float threshold, int K, int D,
+                            const float *cs_old, float *cs_new, const float *embed_avg, float *embed, const float *x, int HW,
+                            long long N, const long long *pick, hipStream_t st);
 int dvq_apply_codes_blocks(long N);
 int dvq_launch_apply_codes(const float *z, const float *E, const long long *codes, const float *mask, int D, int HW, int K, long N,
                            float *zq, double *partials, hipStream_t st);
@@ -1402,6 +1412,88 @@ int dvq_vq_assign_narrow_flat_f32(const float *z, const float *codebook, const f
     if (!z || !codebook || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
     if (N <= 0 || K <= 0) { dvq_set_error("%s: N=%lld K=%d must be positive", fn, (long long)N, K); return DVQ_EINVAL; }
     return narrow_common(fn, z, codebook, mask, N, D, 1, K, true, beta, zq, codes, loss, ws, ws_bytes, stream);
+}
+
+// ---- the lucidrains-style codebooks: cdist-sampled assign (vq_sample.hip), orthogonal loss (ortho_loss.hip), update (ema_update.hip) ----
+int dvq_vq_cdist_sample_assign_f32(const float *x, const void *prep, int B, int D, int HW, int K, float temp, const float *u,
+                                   int64_t u_numel, int64_t *codes, void *stream)
+{
+    const char *fn = "dvq_vq_cdist_sample_assign_f32";
+    if (!x || !prep || !codes || !u) { dvq_set_error("%s: null pointer (u is required: temp == 0 is the plain assign)", fn); return DVQ_EINVAL; }
+    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
+    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    const size_t N = (size_t)B * (size_t)HW;
+    if (N >= ((size_t)1 << 31) || N * (size_t)D >= ((size_t)1 << 40) || N * (size_t)K >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if ((((uintptr_t)x | (uintptr_t)u) & 3) != 0 || ((uintptr_t)prep & 255) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
+    if (!(temp > 0.0f) || !(temp < __builtin_inff())) { dvq_set_error("%s: temp=%g must be finite and positive", fn, (double)temp); return DVQ_EINVAL; }
+    if (u_numel < 0 || (size_t)u_numel != N * (size_t)K) { dvq_set_error("%s: u has %lld elements, expected N * K = %zu", fn, (long long)u_numel, N * (size_t)K); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_cdist_sample_assign(x, (const float *)prep, D, HW, K, (long)N, temp, u, (long long *)codes,
+                                                 (hipStream_t)stream), "vq_cdist_sample_assign");
+}
+
+static bool ortho_shape_ok(const char *fn, int h, int n, int d)
+{
+    if (h <= 0 || n <= 0) { dvq_set_error("%s: h=%d n=%d must be positive", fn, h, n); return false; }
+    return true;
+}
+
+size_t dvq_ortho_loss_workspace_bytes(int h, int n, int d)
+{
+    if (h <= 0 || n <= 0 || !dim_ok(d) || h > 65535 || n >= (1 << 24)) return 0;
+    unsigned gx, gy;
+    dvq_ortho_grid(h, n, &gx, &gy);
+    int S, tper;
+    dvq_ortho_backward_slices(h, n, &S, &tper);
+    const size_t fwd = (size_t)gx * gy * (size_t)h * sizeof(double);                 // forward: one double per workgroup
+    const size_t bwd = (size_t)S * (size_t)h * (size_t)n * (size_t)d * sizeof(float);   // backward: the column slices' partial gradients
+    return ((fwd > bwd ? fwd : bwd) + 255) / 256 * 256;
+}
+
+int dvq_ortho_loss_forward_f32(const float *t, int h, int n, int d, float *rinv, float *loss, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_ortho_loss_forward_f32";
+    if (!t || !rinv || !loss) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!ortho_shape_ok(fn, h, n, d)) return DVQ_EINVAL;
+    if (!dim_ok(d) || h > 65535 || n >= (1 << 24)) { dvq_set_error("%s: h=%d n=%d d=%d unsupported (d in 64, 128, 256; h < 2^16, n < 2^24)", fn, h, n, d); return DVQ_EUNSUPPORTED; }
+    if (((uintptr_t)t & 15) != 0 || (((uintptr_t)rinv | (uintptr_t)loss) & 3) != 0) { dvq_set_error("%s: misaligned pointer (t: 16 bytes)", fn); return DVQ_EINVAL; }
+    const size_t need = dvq_ortho_loss_workspace_bytes(h, n, d);
+    if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EWORKSPACE; }
+    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_ortho_forward(t, h, n, d, rinv, loss, (double *)ws, (hipStream_t)stream), "ortho_loss_forward");
+}
+
+int dvq_ortho_loss_backward_f32(const float *t, const float *rinv, const float *grad_out, int h, int n, int d, float *grad,
+                                void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_ortho_loss_backward_f32";
+    if (!t || !rinv || !grad_out || !grad) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!ortho_shape_ok(fn, h, n, d)) return DVQ_EINVAL;
+    if (!dim_ok(d) || h > 65535 || n >= (1 << 24)) { dvq_set_error("%s: h=%d n=%d d=%d unsupported (d in 64, 128, 256; h < 2^16, n < 2^24)", fn, h, n, d); return DVQ_EUNSUPPORTED; }
+    if ((((uintptr_t)t | (uintptr_t)grad) & 15) != 0 || (((uintptr_t)rinv | (uintptr_t)grad_out) & 3) != 0) { dvq_set_error("%s: misaligned pointer (t, grad: 16 bytes)", fn); return DVQ_EINVAL; }
+    if (t == grad) { dvq_set_error("%s: grad must not alias t", fn); return DVQ_EINVAL; }
+    const size_t need = dvq_ortho_loss_workspace_bytes(h, n, d);
+    if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EWORKSPACE; }
+    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_ortho_backward(t, rinv, grad_out, h, n, d, grad, (float *)ws, (hipStream_t)stream), "ortho_loss_backward");
+}
+
+int dvq_lucid_update_f32(int kind, const float *counts, const float *sums, float decay, float eps, float threshold, int K, int D,
+                         const float *cluster_size, float *cluster_size_out, const float *embed_avg, float *embed,
+                         const float *x, int B, int HW, const int64_t *pick, void *stream)
+{
+    const char *fn = "dvq_lucid_update_f32";
+    if (kind != 0 && kind != 1) { dvq_set_error("%s: kind must be 0 (Euclidean) or 1 (cosine), got %d", fn, kind); return DVQ_EINVAL; }
+    if (!counts || !cluster_size || !cluster_size_out || !embed) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (kind == 0 && !embed_avg) { dvq_set_error("%s: kind 0 needs embed_avg", fn); return DVQ_EINVAL; }
+    if (kind == 1 && !sums) { dvq_set_error("%s: kind 1 needs sums", fn); return DVQ_EINVAL; }
+    if (K <= 0 || D <= 0) { dvq_set_error("%s: K=%d D=%d must be positive", fn, K, D); return DVQ_EINVAL; }
+    if (cluster_size_out == cluster_size) { dvq_set_error("%s: cluster_size_out must not alias cluster_size (every workgroup reads all the OLD counts)", fn); return DVQ_EINVAL; }
+    if (embed_avg == embed) { dvq_set_error("%s: embed must not alias embed_avg", fn); return DVQ_EINVAL; }
+    if (!(decay >= 0.0f && decay <= 1.0f) || !(threshold >= 0.0f)) { dvq_set_error("%s: decay=%g must be in [0, 1], threshold=%g >= 0", fn, (double)decay, (double)threshold); return DVQ_EINVAL; }
+    if (pick && (!x || B <= 0 || HW <= 0)) { dvq_set_error("%s: expiry (pick given) needs x [B, D, HW]", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_lucid_update(kind, counts, sums, decay, eps, threshold, K, D, cluster_size, cluster_size_out, embed_avg, embed,
+                                          x, pick ? HW : 1, pick ? (long long)B * HW : 1, (const long long *)pick, (hipStream_t)stream),
+                  "lucid_update");
 }
 
 }  // extern "C"

@@ -553,3 +553,95 @@ int dvq_launch_ema_update(const float *stats_sum, const float *stats_count, floa
                        D, cs_old, cs_new, embed_ema, weight, restart, restart_rows, z, HW, pick);
     return (int)hipGetLastError();
 }
+
+// ---------------------------------------------------------------------------------------------
+// The training-mode codebook update of the lucidrains-style codebooks (quantize_lucidrains.py:131-144, :257-279), one launch, one
+// wave per code row:
+//   both kinds   cluster_size' = cluster_size * decay + (1 - decay) * counts                      (ema_inplace)
+//   kind 0       embed = embed_avg / (((cluster_size' + eps) / (sum' + K eps)) * sum'), sum' = sum over K of cluster_size' -- every
+//                workgroup sums the K new counts itself, in double, as ema_update_kernel does.  embed_avg is only read: the
+//                reference never updates it (its embed_sum einsum is dead code).
+//   kind 1       m = sums / max(counts, 1), normalised (F.normalize's 1e-12 rule); a code without tokens takes its own normalised
+//                old row instead; embed = embed * decay + (1 - decay) * that.
+//   expiry       (pick != nullptr, threshold > 0) a code with cluster_size' < threshold is replaced: the j-th such code in index order
+//                takes token pick[j] of x ([B, D, HW]; HW == 1: row-major [N, D]), L2-normalised.  Its rank j is the number of
+//                expired codes in front of it: counted by the workgroup in the same loop that sums the counts.
+// The new counts go to `cs_new` (must not alias `cs_old`: every workgroup reads all the old counts).
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void lucid_update_kernel(int kind, const float *__restrict__ counts, const float *__restrict__ sums,
+                                                           float decay, float alpha, float eps, float threshold, int K, int D,
+                                                           const float *__restrict__ cs_old, float *__restrict__ cs_new,
+                                                           const float *__restrict__ embed_avg, float *__restrict__ embed,
+                                                           const float *__restrict__ x, int HW, long long N, const long long *__restrict__ pick)
+{
+    __shared__ double red[4];
+    __shared__ int redc[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool expiry = pick != nullptr && threshold > 0.0f;
+    auto new_count = [&](int j) -> float { return __fadd_rn(__fmul_rn(cs_old[j], decay), __fmul_rn(alpha, counts[j])); };
+    const int j0 = blockIdx.x * 4;
+    double s = 0.0;
+    int before = 0;                                       // expired codes in front of this workgroup's four
+    for (int j = tid; j < K; j += 256) {
+        const float cnew = new_count(j);
+        s += (double)cnew;
+        before += (expiry && j < j0 && cnew < threshold) ? 1 : 0;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off); before += __shfl_xor(before, off); }
+    if (lane == 0) { red[wave] = s; redc[wave] = before; }
+    __syncthreads();
+    const float total = (float)((red[0] + red[1]) + (red[2] + red[3]));
+    int rank = (redc[0] + redc[1]) + (redc[2] + redc[3]);
+    const int j = j0 + wave;
+    if (j >= K) return;
+    const float cnew = new_count(j);
+    if (lane == 0) cs_new[j] = cnew;
+    float *erow = embed + (size_t)j * D;
+    if (expiry && cnew < threshold) {
+        for (int jj = j0; jj < j; ++jj) rank += (new_count(jj) < threshold) ? 1 : 0;
+        long long p = pick[rank];
+        p = p < 0 ? 0 : (p >= N ? N - 1 : p);              // (a pick outside the batch reads its nearest token, never past x)
+        const long long b = p / HW;
+        const float *rr = x + ((size_t)b * D) * HW + (size_t)(p - b * HW);
+        const size_t rstride = (size_t)HW;
+        float q = 0.0f;
+        for (int ch = lane; ch < D; ch += 64) { const float v = rr[(size_t)ch * rstride]; q += v * v; }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
+        const float nrm = fmaxf(__fsqrt_rn(q), 1e-12f);
+        for (int ch = lane; ch < D; ch += 64) erow[ch] = rr[(size_t)ch * rstride] / nrm;
+        return;
+    }
+    if (kind == 0) {
+        const float denom = __fadd_rn(total, __fmul_rn((float)K, eps));
+        const float divisor = __fmul_rn(__fadd_rn(cnew, eps) / denom, total);
+        const float *arow = embed_avg + (size_t)j * D;
+        for (int ch = lane; ch < D; ch += 64) erow[ch] = arow[ch] / divisor;
+        return;
+    }
+    const float cnt = counts[j];
+    const bool empty = cnt == 0.0f;
+    const float *srow = sums + (size_t)j * D;
+    const float bins = empty ? 1.0f : cnt;
+    float q = 0.0f;
+    for (int ch = lane; ch < D; ch += 64) { const float v = empty ? erow[ch] : srow[ch] / bins; q += v * v; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) q += __shfl_xor(q, off);
+    const float nrm = fmaxf(__fsqrt_rn(q), 1e-12f);
+    for (int ch = lane; ch < D; ch += 64) {
+        const float old = erow[ch];
+        const float v = (empty ? old : srow[ch] / bins) / nrm;
+        erow[ch] = __fadd_rn(__fmul_rn(old, decay), __fmul_rn(alpha, v));
+    }
+}
+
+int dvq_launch_lucid_update(int kind, const float *counts, const float *sums, float decay, float eps, float threshold, int K, int D,
+                            const float *cs_old, float *cs_new, const float *embed_avg, float *embed, const float *x, int HW,
+                            long long N, const long long *pick, hipStream_t st)
+{
+    const float alpha = (float)(1.0 - decay_as_written(decay));
+    hipLaunchKernelGGL(lucid_update_kernel, dim3((unsigned)((K + 3) / 4)), dim3(256), 0, st, kind, counts, sums, decay, alpha, eps,
+                       threshold, K, D, cs_old, cs_new, embed_avg, embed, x, HW, N, pick);
+    return (int)hipGetLastError();
+}

@@ -16,6 +16,8 @@
 // chain that hides them, and keeps the running argmax lane-local (the two lane halves are merged once, after the loop).
 //   score   L2:  s = -d, d = fl(fl(xn + en) - 2 dot) (ATen-order norms): the reference's expression negated, bit for bit
 //           DOT: s = dot (operands L2-normalised by the caller)
+//           CDIST: s = -sqrtf(d < 0 ? 0 : d), d as L2 (quantize_lucidrains.py:123, `-torch.cdist`): the square root does not commute
+//                  with the noise, so the sampled code of the lucidrains-style codebook needs a score of its own; a NaN d stays NaN
 //   u == nullptr: code = argmax s;  u given: code = argmax fl(fl(s / temp) + g), g = -logf(max(-logf(max(u, 1e-20f)), 1e-20f))
 //   argmax with torch's rules: the first index among equal maxima, a NaN is the maximum and the first NaN wins.
 // Nothing of size N x K is written; no workspace; no atomics.
@@ -27,6 +29,7 @@
 
 #define DVQ_METRIC_L2_ 0
 #define DVQ_METRIC_DOT_ 1
+#define DVQ_METRIC_CDIST_ 2      // s = -sqrt(max(d, 0)): torch.cdist's score (dvq_vq_cdist_sample_assign_f32 only; not a value of the ABI's `metric`)
 
 // the reference's gumbel_noise of one uniform (common_utils.py:19-29): -log(clamp(-log(clamp(u, 1e-20)), 1e-20))
 __device__ __forceinline__ float gumbel_of(float u)
@@ -74,7 +77,7 @@ __global__ __launch_bounds__(256, 2) void vq_score_assign_kernel(
 
     // ---- xn: ATen-order sum of squares of this token (vq_assign_exact.hip); the DOT metric has no norms
     float xn = 0.0f;
-    if constexpr (METRIC == DVQ_METRIC_L2_) {
+    if constexpr (METRIC != DVQ_METRIC_DOT_) {
         float p[16], o[16];
 #pragma unroll
         for (int q = 0; q < 16; ++q) {
@@ -146,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void vq_score_assign_kernel(
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             f32x4 en4 = {0.0f, 0.0f, 0.0f, 0.0f};
-            if constexpr (METRIC == DVQ_METRIC_L2_) en4 = *(const f32x4 *)(entile + 8 * g);
+            if constexpr (METRIC != DVQ_METRIC_DOT_) en4 = *(const f32x4 *)(entile + 8 * g);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int r = g * 4 + q;
@@ -155,6 +158,9 @@ __global__ __launch_bounds__(256, 2) void vq_score_assign_kernel(
                 if constexpr (METRIC == DVQ_METRIC_L2_) {
                     const float bias = __fadd_rn(xn, en4[q]);
                     s = -__builtin_fmaf(-2.0f, acc[r], bias);    // -(fl(bias - 2 dot)), 2 dot exact
+                } else if constexpr (METRIC == DVQ_METRIC_CDIST_) {
+                    const float d = __builtin_fmaf(-2.0f, acc[r], __fadd_rn(xn, en4[q]));
+                    s = -__fsqrt_rn(d < 0.0f ? 0.0f : d);        // (the conditional keeps a NaN; fmaxf would not)
                 } else {
                     s = acc[r];
                 }
@@ -200,6 +206,19 @@ int dvq_launch_score_assign(const float *z, const float *prep, int D, int HW, in
                          : launch_score<128, DVQ_METRIC_L2_>(z, prep, HW, K, N, temp, u, codes, vec, st);
     case 256: return dot ? launch_score<256, DVQ_METRIC_DOT_>(z, prep, HW, K, N, temp, u, codes, vec, st)
                          : launch_score<256, DVQ_METRIC_L2_>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    default:  return -1000;
+    }
+}
+
+// the sampled assign against -cdist (u required): the CDIST score of the same template
+int dvq_launch_cdist_sample_assign(const float *z, const float *prep, int D, int HW, int K, long N, float temp, const float *u,
+                                   long long *codes, hipStream_t st)
+{
+    const int vec = (K % 4 == 0) && ((uintptr_t)u & 15) == 0;
+    switch (D) {
+    case 64:  return launch_score<64, DVQ_METRIC_CDIST_>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 128: return launch_score<128, DVQ_METRIC_CDIST_>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 256: return launch_score<256, DVQ_METRIC_CDIST_>(z, prep, HW, K, N, temp, u, codes, vec, st);
     default:  return -1000;
     }
 }

@@ -1285,6 +1285,39 @@ def _noop(*args, **kwargs):
     pass
 
 
+def _kmeans_lloyd(flat, means, iters, all_reduce_fn=_noop, cosine=False):
+    """The Lloyd loop of common_utils.kmeans:128-154 on the kernels: flat [N, D] f32 GPU tokens, means [1, K, D] the initial rows
+    -> (means [1, K, D], bins [1, K] int64 of the last iteration).  Per iteration the exact-mode assign, codes only (cosine: the
+    scored assign on the dot product, `samples @ means^T`; the caller passes normalised tokens) and the counts / sums kernel of the
+    EMA update (`dvq_ema_accumulate_nchw_f32`); empty clusters keep their mean; cosine: the new means are L2-normalised."""
+    N, D = flat.shape
+    K = means.shape[1]
+    dev = flat.device
+    prep = _CodebookPrep()
+    stats = torch.empty(K * D + K, dtype=torch.float32, device=dev)
+    sums, counts = stats[:K * D].view(K, D), stats[K * D:]
+    bins = torch.zeros(1, K, dtype=torch.int64, device=dev)
+    for _ in range(iters):
+        cb = means[0].contiguous()
+        if cosine:
+            buckets = score_assign(flat, cb, prep, _lib.METRIC_DOT)
+        else:
+            _, buckets, _ = vq_assign(flat, cb, prep, want_zq=False, want_loss=False, mode=_lib.MODE_EXACT)
+        with _lib.on_device(dev):
+            _lib.check(_lib_handle.dvq_ema_accumulate_nchw_f32(
+                flat.data_ptr(), buckets.data_ptr(), N, D, 1, K, counts.data_ptr(), sums.data_ptr(),
+                _lib.stream_ptr(dev)), "dvq_ema_accumulate_nchw_f32")
+        bins = counts.round().to(torch.int64).unsqueeze(0)        # [1, K]
+        all_reduce_fn(bins)
+        zero_mask = bins == 0
+        new_means = sums.unsqueeze(0) / bins.masked_fill(zero_mask, 1).unsqueeze(-1)
+        all_reduce_fn(new_means)
+        if cosine:
+            new_means = F.normalize(new_means, p=2, dim=-1)
+        means = torch.where(zero_mask.unsqueeze(-1), means, new_means)
+    return means, bins
+
+
 class _LearnableCodebookQuantizer(InvalidatesPrepared, nn.Module):
     """What MaskVectorQuantize and VectorQuantize share -- in the reference the two classes are one text with and without the
     codebook mask (modules/vector_quantization/quantize_codebook_mask.py, quantize.py): a codebook trained by back-propagation
@@ -1349,27 +1382,8 @@ class _LearnableCodebookQuantizer(InvalidatesPrepared, nn.Module):
             return
         K, D = self.codebook_size, self.codebook_dim
         flat = _lib.require_cuda_f32(data.detach().reshape(-1, D), "x")
-        samples = flat.unsqueeze(0)                                   # [1, N, D], the reference's 'h n d'
-        means = self.sample_fn(samples, K)                            # [1, K, D]
-        N = flat.shape[0]
-        dev = flat.device
-        prep = _CodebookPrep()
-        stats = torch.empty(K * D + K, dtype=torch.float32, device=dev)
-        sums, counts = stats[:K * D].view(K, D), stats[K * D:]
-        bins = torch.zeros(1, K, dtype=torch.int64, device=dev)
-        for _ in range(self.kmeans_iters):
-            cb = means[0].contiguous()
-            _, buckets, _ = vq_assign(flat, cb, prep, want_zq=False, want_loss=False, mode=_lib.MODE_EXACT)
-            with _lib.on_device(dev):
-                _lib.check(_lib_handle.dvq_ema_accumulate_nchw_f32(
-                    flat.data_ptr(), buckets.data_ptr(), N, D, 1, K, counts.data_ptr(), sums.data_ptr(),
-                    _lib.stream_ptr(dev)), "dvq_ema_accumulate_nchw_f32")
-            bins = counts.round().to(torch.int64).unsqueeze(0)        # [1, K]
-            self.all_reduce_fn(bins)
-            zero_mask = bins == 0
-            new_means = sums.unsqueeze(0) / bins.masked_fill(zero_mask, 1).unsqueeze(-1)
-            self.all_reduce_fn(new_means)
-            means = torch.where(zero_mask.unsqueeze(-1), means, new_means)
+        means = self.sample_fn(flat.unsqueeze(0), K)                  # [1, K, D] rows of the reference's 'h n d' samples
+        means, bins = _kmeans_lloyd(flat, means, self.kmeans_iters, self.all_reduce_fn)
         self.embedding.weight.data.copy_(means.squeeze(0))
         self.cluster_size.data.copy_(bins)
         self.initted.data.copy_(torch.Tensor([True]))

@@ -30,6 +30,9 @@
  *     dvq_vq_assign_narrow_*_f32 below; every other entry point refuses them as before.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.16.0 dvq_vq_cdist_sample_assign_f32, dvq_ortho_loss_workspace_bytes, dvq_ortho_loss_forward_f32, dvq_ortho_loss_backward_f32,
+ *          dvq_lucid_update_f32 (new): the lucidrains-style codebooks (quantize_lucidrains.py) -- the sampled assign against -cdist, the
+ *          orthogonal regulariser with its gradient, and the per-step codebook update with code expiry.  Nothing else changed.
  *   0.15.0 dvq_code_stats_f32, dvq_code_stats_grain_f32 (new): code histogram, codes in use, perplexity and the optional one-hot matrix of
  *          a batch of codes -- what VectorQuantizer / EMAVectorQuantizer return besides z_q -- and the same per grain.  Nothing else changed.
  *   0.14.0 dvq_vq_assign_narrow_workspace_bytes, dvq_vq_assign_narrow_tile_codes, dvq_vq_assign_narrow_nchw_f32,
@@ -878,6 +881,60 @@ DVQ_API int dvq_exchange_pack(const int64_t *codes, const int64_t *grain, const 
 DVQ_API int dvq_exchange_unpack(const void *gathered, int world, int global_batch, int64_t codes_per_image,
                         int64_t grain_per_image, int num_codes, int64_t *codes, int64_t *grain, float *mean,
                         void *stream);
+
+/*
+ * Temperature-sampled code assignment against -cdist: EuclideanCodebook with sample_codebook_temp > 0
+ * (quantize_lucidrains.py:123-125: `dist = -torch.cdist(flatten, embed)`, gumbel_sample(dist, temperature = temp)).
+ * dvq_vq_score_assign_f32 with a third score: s = -sqrtf(d < 0 ? 0 : d), d = the assign's distance bit for bit (a NaN d stays a
+ * NaN score: the maximum); the square root does not commute with the noise, so DVQ_METRIC_L2 cannot serve this codebook.
+ *   codes [N] int64 = argmax_j fl(fl(s[n, j] / temp) + g[n, j]), g and the argmax rules as dvq_vq_score_assign_f32
+ * x, prep, B, D, HW, K, u, u_numel as there; u is REQUIRED (temp == 0 is the plain assign) and temp finite, > 0.
+ * DVQ_EINVAL: null x / prep / u / codes, sizes, temp, u_numel != N * K, misaligned pointers.  DVQ_EUNSUPPORTED: D outside {64, 128, 256},
+ * tensor too large.  One launch, no N x K store, no workspace, no atomics, no host synchronisation.  Vector stores only.
+ */
+DVQ_API int dvq_vq_cdist_sample_assign_f32(const float *x, const void *prep, int B, int D, int HW, int K, float temp,
+                                           const float *u, int64_t u_numel, int64_t *codes, void *stream);
+
+/*
+ * Orthogonal regulariser of a codebook, eq. (2) of arXiv 2112.00384 (quantize_lucidrains.py:18-24, orthogonal_loss_fn; the same
+ * expression sits in quantize_codebook_mask.py:124-132 and quantize.py), and its gradient (ortho_loss.hip).
+ *   t [h, n, d] f32, 16-byte aligned; c^_i = t_i / max(|t_i|, 1e-12) (F.normalize); C = c^ c^T per head
+ *   forward:  rinv [h, n] = 1 / max(|t_i|, 1e-12) (written; keep it for backward), loss [1] = sum (C - I)^2 / (h n^2)
+ *             ws >= dvq_ortho_loss_workspace_bytes(h, n, d), 256-byte aligned (forward: one double per workgroup; backward: the
+ *             partial gradients of the up to 8 column slices its sweep is split into, at most 8 h n d floats)
+ *   backward: grad [h, n, d] = grad_out[0] * dloss/dt (grad_out: a DEVICE scalar), every element written once; must not alias t;
+ *             ws as for forward (its contents need not survive from forward)
+ * The Gram matrix is tiled over its upper triangle on the fp32 MFMA chains of the assign; nothing of size n x n reaches memory, no
+ * float atomics; partial sums in double, finalised in one fixed order: loss and grad are the same bits on every run.  Within 1e-5
+ * relative of the float64 value.  No host synchronisation; capturable in a HIP graph.
+ * d in {64, 128, 256}, h < 2^16, n < 2^24: DVQ_EUNSUPPORTED otherwise (dvq_ortho_loss_workspace_bytes: 0).  DVQ_EINVAL: null pointer,
+ * h or n < 1, misaligned pointer, grad == t.  DVQ_EWORKSPACE: ws too small.
+ */
+DVQ_API size_t dvq_ortho_loss_workspace_bytes(int h, int n, int d);
+DVQ_API int dvq_ortho_loss_forward_f32(const float *t, int h, int n, int d, float *rinv, float *loss, void *ws, size_t ws_bytes,
+                                       void *stream);
+DVQ_API int dvq_ortho_loss_backward_f32(const float *t, const float *rinv, const float *grad_out, int h, int n, int d, float *grad,
+                                        void *ws, size_t ws_bytes, void *stream);
+
+/*
+ * The training-mode codebook update of EuclideanCodebook (kind 0, quantize_lucidrains.py:131-144) and CosineSimCodebook (kind 1,
+ * :257-279) as ONE launch, code expiry included (:85-105):
+ *   both    cluster_size_out = cluster_size * decay + (1 - decay) * counts       (counts [K] f32: this step's tokens per code)
+ *   kind 0  embed = embed_avg / (((cluster_size_out + eps) / (S + K eps)) * S), S = sum of cluster_size_out (in double).  embed_avg
+ *           [K, D] is only read: the reference never updates it.  sums is ignored (may be NULL).
+ *   kind 1  sums [K, D] = per-code sums of the L2-normalised tokens (dvq_ema_accumulate_nchw_f32 on the normalised rows):
+ *           m = normalize(sums / max(counts, 1)), a code without tokens takes normalize(embed) instead;
+ *           embed = embed * decay + (1 - decay) * m.  embed_avg is ignored (may be NULL).
+ *   expiry  pick != NULL and threshold > 0: the j-th code (in index order) with cluster_size_out < threshold takes token pick[j] of x
+ *           -- [B, D, HW] (NCHW), HW == 1: row-major [N, D] with B = N -- L2-normalised (in BOTH kinds, as the reference does).
+ *           pick [K] int64 in [0, B * HW) (dvq_restart_pick_i64: distinct, no host read; values outside are clamped).
+ * cluster_size_out must not alias cluster_size; embed [K, D] is updated in place (a row has one owner).  `1 - decay` as
+ * dvq_ema_update_f32: the Python double, rounded to fp32.  Within rounding (1e-5) of the reference.  No atomics, no host
+ * synchronisation.  DVQ_EINVAL: kind not 0 / 1, null pointer, K or D < 1, aliasing, decay outside [0, 1], threshold < 0, pick without x.
+ */
+DVQ_API int dvq_lucid_update_f32(int kind, const float *counts, const float *sums, float decay, float eps, float threshold,
+                                 int K, int D, const float *cluster_size, float *cluster_size_out, const float *embed_avg,
+                                 float *embed, const float *x, int B, int HW, const int64_t *pick, void *stream);
 
 #ifdef __cplusplus
 }
