@@ -4,10 +4,19 @@ modules of this package and the HIP kernels.
 There is NO fallback: if the shared library is missing or an entry point is absent the import
 of this module raises.  torch is imported first so that libdvq.so binds to the HIP runtime torch
 already loaded (same libamdhip64.so.7 SONAME) and can use torch's streams and device pointers.
+
+The binding is derived from the header: at import `_parse_header` reads every `DVQ_API <ret> dvq_name(<args>);` declaration of
+include/dvq.h and maps its C types to ctypes (`_CTYPES`; any pointer is c_void_p, `const char *` returned is c_char_p).  A type
+outside that table, or a DVQ_API declaration that does not parse, raises: nothing defaults to int.  A new entry point needs its
+declaration in the header and its definition in csrc/dvq_abi.hip, nothing here.  Two namespaces carry the same prototypes:
+`lib.dvq_x(...)` returns the status code (tests, tools, bench), `checked.dvq_x(...)` raises DvqError on a non-zero one (the
+package's own call sites).  The constants below restate the header's #defines; tests/test_abi_and_host.py pins them to it.
 """
 import ctypes
 import os
+import re
 import subprocess
+import types
 
 import torch
 
@@ -35,37 +44,54 @@ TRANSFER_SAMPLED, TRANSFER_REMAIN = 0, 1
 TRANSFER_SOS_NONE, TRANSFER_SOS_CONST, TRANSFER_SOS_COPY = 0, 1, 2
 METRIC_L2, METRIC_DOT = 0, 1   # dvq_vq_score_assign_f32: s = -distance / s = dot product
 
-EXPORTS = (
-    "dvq_version", "dvq_last_error_string", "dvq_codebook_prep_bytes", "dvq_codebook_prepare_f32",
-    "dvq_vq_assign_workspace_bytes", "dvq_vq_assign_nchw_f32", "dvq_vq_assign_flat_f32", "dvq_vq_assign_fallback_count_offset",
-    "dvq_embed_gather_f32",
-    "dvq_vq_assign_routed_workspace_bytes", "dvq_vq_assign_routed_dual_f32", "dvq_vq_assign_routed_triple_f32",
-    "dvq_vq_assign_routed_fallback_count_offset",
-    "dvq_exchange_bytes", "dvq_exchange_pack", "dvq_exchange_unpack", "dvq_debug_filter_scores_f32",
-    "dvq_qconv_prep_bytes", "dvq_qconv_prepare_f32", "dvq_qconv_f32", "dvq_qconv_select_f32",
-    "dvq_vq_backward_nchw_f32", "dvq_vq_backward_codebook_nchw_f32", "dvq_vq_assign_qconv_f32", "dvq_vq_assign_routed_qconv_dual_f32", "dvq_vq_assign_routed_qconv_triple_f32",
-    "dvq_fold_prep_bytes", "dvq_fold_prepare_f32", "dvq_vq_assign_fold_f32", "dvq_vq_assign_routed_fold_dual_f32",
-    "dvq_vq_assign_routed_fold_triple_f32", "dvq_debug_fold_scores_f32",
-    "dvq_entropy_gate_f32", "dvq_route_select_dual_f32", "dvq_route_select_dual_entropy_f32", "dvq_route_select_triple_f32",
-    "dvq_entropy_map_f32", "dvq_ema_accumulate_nchw_f32", "dvq_restart_pick_i64", "dvq_ema_update_f32", "dvq_router_gate_workspace_bytes", "dvq_router_gate_prep_bytes", "dvq_router_gate_prepare_f32", "dvq_router_gate_prepare_norm_f32", "dvq_router_gate_f32", "dvq_permute_dual_count_i64", "dvq_permute_dual_forward_i64", "dvq_permute_dual_backward_i64",
-    "dvq_route_train_workspace_bytes", "dvq_route_train_forward_f32", "dvq_route_train_backward_f32",
-    "dvq_rq_workspace_bytes", "dvq_rq_residual_offset", "dvq_rq_step_f32", "dvq_rq_loss_f32", "dvq_rq_backward_f32",
-    "dvq_rq_embed_code_f32",
-    "dvq_sample_head_f32", "dvq_sample_transfer_count_i64", "dvq_sample_transfer_fill_i64",
-    "dvq_decode_table_bytes", "dvq_decode_table_prepare_f32", "dvq_decode_head_f32",
-    "dvq_vq_soft_assign_workspace_bytes", "dvq_vq_soft_assign_flat_f32",
-    "dvq_vq_score_assign_f32", "dvq_vq_apply_codes_nchw_f32", "dvq_vq_apply_codes_flat_f32",
-    "dvq_gumbel_prep_bytes", "dvq_gumbel_prepare_f32", "dvq_vq_gumbel_assign_workspace_bytes", "dvq_vq_gumbel_assign_f32",
-    "dvq_vq_assign_narrow_workspace_bytes", "dvq_vq_assign_narrow_tile_codes", "dvq_vq_assign_narrow_nchw_f32",
-    "dvq_vq_assign_narrow_flat_f32",
-    "dvq_code_stats_f32", "dvq_code_stats_grain_f32",
-    "dvq_vq_cdist_sample_assign_f32", "dvq_ortho_loss_workspace_bytes", "dvq_ortho_loss_forward_f32", "dvq_ortho_loss_backward_f32",
-    "dvq_lucid_update_f32",
-)
-
 
 class DvqError(RuntimeError):
     pass
+
+
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "dvq.h")       # as csrc/Makefile finds it: ../../include/dvq.h
+_CTYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
+           "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
+_DECL = re.compile(r"\s+([^();]+?)\s*\b(dvq_\w+)\s*\(([^()]*)\)\s*;")
+
+
+def _ctype(text, name, is_param):
+    """the ctypes type of one C parameter (`const float *z`, `int64_t N`) or return type; an unknown type raises -- no default"""
+    if "*" in text:
+        return ctypes.c_char_p if not is_param and text.split() == ["const", "char", "*"] else ctypes.c_void_p
+    words = [w for w in text.split() if w != "const"]
+    if is_param and len(words) > 1:
+        words.pop()                                                      # the parameter's name
+    if " ".join(words) not in _CTYPES:
+        raise DvqError("include/dvq.h: %s: no ctypes type for `%s`" % (name, " ".join(text.split())))
+    return _CTYPES[" ".join(words)]
+
+
+def _parse_header(text):
+    """{name: (restype, [argtypes])} of every `DVQ_API <ret> dvq_name(<args>);` declaration of the header text, in its order.
+    Every use of DVQ_API other than its own #define has to parse as such a declaration."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#[ \t]*define[ \t]+DVQ_API\b.*$", "", text, flags=re.M)
+    protos = {}
+    for chunk in re.split(r"\bDVQ_API\b", text)[1:]:
+        m = _DECL.match(chunk)
+        if m is None:
+            raise DvqError("include/dvq.h: cannot parse the declaration `DVQ_API %s`" % " ".join(chunk.split(";")[0].split())[:160])
+        ret, name, args = m.groups()
+        args = [] if args.strip() in ("", "void") else args.split(",")
+        protos[name] = (_ctype(ret, name, False), [_ctype(a, name, True) for a in args])
+    return protos
+
+
+def _read_header():
+    if not os.path.exists(HEADER):
+        raise DvqError("include/dvq.h not found at %s: the binding of libdvq.so is derived from it" % HEADER)
+    with open(HEADER) as f:
+        return _parse_header(f.read())
+
+
+_PROTOTYPES = _read_header()
+EXPORTS = tuple(_PROTOTYPES)
 
 
 def build(force=False):
@@ -77,6 +103,16 @@ def build(force=False):
     return LIB_PATH
 
 
+_INT_QUERIES = ("dvq_version", "dvq_vq_assign_narrow_tile_codes")     # return an int that is a value, not a status
+
+
+def _raise_on_error(rc, func, args):
+    """errcheck of the checked entry points: what check(rc, name) raises"""
+    if rc != DVQ_OK:
+        raise DvqError("%s failed (rc=%d): %s" % (func.__name__, rc, lib.dvq_last_error_string().decode("utf-8", "replace")))
+    return rc
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise DvqError(
@@ -86,189 +122,22 @@ def _load():
     for name in EXPORTS:
         if not hasattr(lib, name):
             raise DvqError("libdvq.so does not export %s (stale build?)" % name)
-    vp, i32, i64, f32, sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
-    lib.dvq_version.restype = i32
-    lib.dvq_last_error_string.restype = ctypes.c_char_p
-    lib.dvq_codebook_prep_bytes.restype = sz
-    lib.dvq_codebook_prep_bytes.argtypes = [i32, i32]
-    lib.dvq_codebook_prepare_f32.restype = i32
-    lib.dvq_codebook_prepare_f32.argtypes = [vp, i32, i32, vp, sz, vp]
-    lib.dvq_vq_assign_workspace_bytes.restype = sz
-    lib.dvq_vq_assign_workspace_bytes.argtypes = [i32, i32, i32, i32, i32]
-    lib.dvq_vq_assign_fallback_count_offset.restype = sz
-    lib.dvq_vq_assign_fallback_count_offset.argtypes = [i32, i32, i32, i32]
-    lib.dvq_vq_assign_nchw_f32.restype = i32
-    lib.dvq_vq_assign_nchw_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, i32, vp]
-    lib.dvq_vq_assign_flat_f32.restype = i32
-    lib.dvq_vq_assign_flat_f32.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp, sz, i32, vp]
-    lib.dvq_vq_assign_routed_workspace_bytes.restype = sz
-    lib.dvq_vq_assign_routed_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32]
-    lib.dvq_vq_assign_routed_fallback_count_offset.restype = sz
-    lib.dvq_vq_assign_routed_fallback_count_offset.argtypes = [i32, i32, i32, i32, i32, i32]
-    lib.dvq_vq_assign_routed_dual_f32.restype = i32
-    lib.dvq_vq_assign_routed_dual_f32.argtypes = [vp, i32, f32, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
-                                                  vp, vp, vp, vp, vp, vp, vp, sz, i32, vp]
-    lib.dvq_vq_assign_routed_triple_f32.restype = i32
-    lib.dvq_vq_assign_routed_triple_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
-                                                    vp, vp, vp, vp, vp, vp, sz, i32, vp]
-    lib.dvq_vq_backward_nchw_f32.restype = i32
-    lib.dvq_vq_backward_nchw_f32.argtypes = [vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp]
-    lib.dvq_vq_backward_codebook_nchw_f32.restype = i32
-    lib.dvq_vq_backward_codebook_nchw_f32.argtypes = [vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, vp, vp]
-    lib.dvq_vq_assign_qconv_f32.restype = i32
-    lib.dvq_vq_assign_qconv_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, i32, vp, sz, i32, vp]
-    lib.dvq_vq_assign_routed_qconv_dual_f32.restype = i32
-    lib.dvq_vq_assign_routed_qconv_dual_f32.argtypes = [vp, i32, f32, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
-                                                        vp, vp, vp, vp, vp, vp, vp, i32, vp, sz, i32, vp]
-    lib.dvq_vq_assign_routed_qconv_triple_f32.restype = i32
-    lib.dvq_vq_assign_routed_qconv_triple_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32,
-                                                          vp, vp, vp, vp, vp, vp, i32, vp, sz, i32, vp]
-    lib.dvq_fold_prep_bytes.restype = sz
-    lib.dvq_fold_prep_bytes.argtypes = [i32, i32]
-    lib.dvq_fold_prepare_f32.restype = i32
-    lib.dvq_fold_prepare_f32.argtypes = [vp, i32, i32, vp, vp, vp, vp, sz, vp]
-    lib.dvq_vq_assign_fold_f32.restype = i32
-    lib.dvq_vq_assign_fold_f32.argtypes = [vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, sz, i32, vp]
-    lib.dvq_vq_assign_routed_fold_dual_f32.restype = i32
-    lib.dvq_vq_assign_routed_fold_dual_f32.argtypes = [vp, i32, f32, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
-                                                       vp, vp, vp, vp, vp, vp, sz, i32, vp]
-    lib.dvq_vq_assign_routed_fold_triple_f32.restype = i32
-    lib.dvq_vq_assign_routed_fold_triple_f32.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, i32,
-                                                         vp, vp, vp, vp, vp, sz, i32, vp]
-    lib.dvq_debug_fold_scores_f32.restype = i32
-    lib.dvq_debug_fold_scores_f32.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
-    lib.dvq_qconv_prep_bytes.restype = sz
-    lib.dvq_qconv_prep_bytes.argtypes = [i32]
-    lib.dvq_qconv_prepare_f32.restype = i32
-    lib.dvq_qconv_prepare_f32.argtypes = [vp, vp, i32, vp, sz, vp]
-    lib.dvq_qconv_f32.restype = i32
-    lib.dvq_qconv_f32.argtypes = [vp, vp, i32, i32, i32, vp, vp]
-    lib.dvq_qconv_select_f32.restype = i32
-    lib.dvq_qconv_select_f32.argtypes = [i32, vp, i32, f32, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    if hasattr(lib, "dvq_tuning_buffers"):                 # tuning build only
-        lib.dvq_tuning_buffers.restype = i32
-        lib.dvq_tuning_buffers.argtypes = [vp, vp]
-    lib.dvq_debug_filter_scores_f32.restype = i32
-    lib.dvq_debug_filter_scores_f32.argtypes = [vp, i32, vp, i32, i32, vp, vp, vp, vp, vp]
-    lib.dvq_exchange_bytes.restype = sz
-    lib.dvq_exchange_bytes.argtypes = [i64, i64, i32, i32]
-    lib.dvq_exchange_pack.restype = i32
-    lib.dvq_exchange_pack.argtypes = [vp, vp, vp, ctypes.c_double, i32, i32, i64, i64, i32, vp, vp]
-    lib.dvq_exchange_unpack.restype = i32
-    lib.dvq_exchange_unpack.argtypes = [vp, i32, i32, i64, i64, i32, vp, vp, vp, vp]
-    lib.dvq_embed_gather_f32.restype = i32
-    lib.dvq_embed_gather_f32.argtypes = [vp, i32, i32, vp, i64, vp, vp]
-    lib.dvq_entropy_gate_f32.restype = i32
-    lib.dvq_entropy_gate_f32.argtypes = [vp, i64, f32, vp, vp]
-    lib.dvq_route_select_dual_f32.restype = i32
-    lib.dvq_route_select_dual_f32.argtypes = [vp, i32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    lib.dvq_route_select_dual_entropy_f32.restype = i32
-    lib.dvq_route_select_dual_entropy_f32.argtypes = [vp, f32, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.dvq_route_select_triple_f32.restype = i32
-    lib.dvq_route_select_triple_f32.argtypes = [vp, i32, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]
-    lib.dvq_ema_accumulate_nchw_f32.restype = i32
-    lib.dvq_ema_accumulate_nchw_f32.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, vp]
-    lib.dvq_ema_update_f32.restype = i32
-    lib.dvq_ema_update_f32.argtypes = [vp, vp, f32, f32, i32, i32, vp, vp, vp, vp, i32, vp, vp, i32, i32, vp, vp]
-    lib.dvq_restart_pick_i64.restype = i32
-    lib.dvq_restart_pick_i64.argtypes = [ctypes.c_uint64, i64, i32, vp, vp]
-    lib.dvq_router_gate_workspace_bytes.restype = sz
-    lib.dvq_router_gate_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32]
-    lib.dvq_router_gate_prep_bytes.restype = sz
-    lib.dvq_router_gate_prep_bytes.argtypes = [i32, i32, i32]
-    lib.dvq_router_gate_prepare_f32.restype = i32
-    lib.dvq_router_gate_prepare_f32.argtypes = [vp, i32, i32, i32, vp, sz, vp]
-    lib.dvq_router_gate_prepare_norm_f32.restype = i32
-    lib.dvq_router_gate_prepare_norm_f32.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp]
-    lib.dvq_router_gate_f32.restype = i32
-    lib.dvq_router_gate_f32.argtypes = [i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp,
-                                        vp, vp, vp, vp, i32, i32, vp, vp, vp, sz, vp]
-    lib.dvq_route_train_workspace_bytes.restype = sz
-    lib.dvq_route_train_workspace_bytes.argtypes = [i32, i32, i32, i32, i32, i32, i32]
-    _rt_in = [i32, vp, vp, vp, i32, i32, i32, i32, i32, f32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, f32]
-    lib.dvq_route_train_forward_f32.restype = i32
-    lib.dvq_route_train_forward_f32.argtypes = _rt_in + [vp, vp, vp, vp, vp, sz, vp]
-    lib.dvq_route_train_backward_f32.restype = i32
-    lib.dvq_route_train_backward_f32.argtypes = _rt_in + [vp, vp, vp, sz] + [vp] * 3 + [vp] * 6 + [vp] * 4 + [vp]
-    lib.dvq_rq_workspace_bytes.restype = sz
-    lib.dvq_rq_workspace_bytes.argtypes = [i64, i32, i32, i32]
-    lib.dvq_rq_residual_offset.restype = sz
-    lib.dvq_rq_residual_offset.argtypes = [i64, i32, i32, i32]
-    lib.dvq_rq_step_f32.restype = i32
-    lib.dvq_rq_step_f32.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, sz, vp]
-    lib.dvq_rq_loss_f32.restype = i32
-    lib.dvq_rq_loss_f32.argtypes = [i64, i32, i32, vp, sz, vp, vp]
-    lib.dvq_rq_backward_f32.restype = i32
-    lib.dvq_rq_backward_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, sz, vp, vp]
-    lib.dvq_rq_embed_code_f32.restype = i32
-    lib.dvq_rq_embed_code_f32.argtypes = [ctypes.POINTER(vp), ctypes.POINTER(i32), i32, vp, i32, i32, i32, i32, i32, i32, i32,
-                                          i32, i32, vp, vp]
-    lib.dvq_entropy_map_f32.restype = i32
-    lib.dvq_entropy_map_f32.argtypes = [vp, i32, i32, i32, i32, vp, vp]
-    lib.dvq_permute_dual_count_i64.restype = i32
-    lib.dvq_permute_dual_count_i64.argtypes = [vp, i32, i32, i32, vp, vp, vp]
-    lib.dvq_permute_dual_forward_i64.restype = i32
-    lib.dvq_permute_dual_forward_i64.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, ctypes.POINTER(i64),
-                                                 vp, vp, vp, vp, vp, vp, vp]
-    lib.dvq_permute_dual_backward_i64.restype = i32
-    lib.dvq_permute_dual_backward_i64.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, i32, i64, i64, vp, vp]
-    lib.dvq_sample_head_f32.restype = i32
-    lib.dvq_sample_head_f32.argtypes = [vp, i64, i32, i32, f32, ctypes.POINTER(i64), vp, i64, i32, vp, i32, f32, i32, vp,
-                                        vp, i64, vp, vp, vp]
-    lib.dvq_sample_transfer_count_i64.restype = i32
-    lib.dvq_sample_transfer_count_i64.argtypes = [vp, i64, i32, i32, i32, i64, i32, vp, vp, vp]
-    lib.dvq_sample_transfer_fill_i64.restype = i32
-    lib.dvq_sample_transfer_fill_i64.argtypes = [vp, i64, i32, i32, i32, i64, i32, i32, i32, i64, i64, i64, i32, vp, vp]
-    lib.dvq_decode_table_bytes.restype = sz
-    lib.dvq_decode_table_bytes.argtypes = [i32, i32]
-    lib.dvq_decode_table_prepare_f32.restype = i32
-    lib.dvq_decode_table_prepare_f32.argtypes = [vp, i32, i32, vp, vp, i32, vp, sz, vp]
-    lib.dvq_decode_head_f32.restype = i32
-    lib.dvq_decode_head_f32.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, vp]
-    lib.dvq_vq_soft_assign_workspace_bytes.restype = sz
-    lib.dvq_vq_soft_assign_workspace_bytes.argtypes = [i64, i32, i32]
-    lib.dvq_vq_soft_assign_flat_f32.restype = i32
-    lib.dvq_vq_soft_assign_flat_f32.argtypes = [vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp, vp, sz, vp]
-    lib.dvq_vq_score_assign_f32.restype = i32
-    lib.dvq_vq_score_assign_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, f32, vp, i64, vp, vp]
-    lib.dvq_vq_apply_codes_nchw_f32.restype = i32
-    lib.dvq_vq_apply_codes_nchw_f32.argtypes = [vp, vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, sz, vp]
-    lib.dvq_vq_apply_codes_flat_f32.restype = i32
-    lib.dvq_vq_apply_codes_flat_f32.argtypes = [vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, sz, vp]
-    lib.dvq_gumbel_prep_bytes.restype = sz
-    lib.dvq_gumbel_prep_bytes.argtypes = [i32, i32]
-    lib.dvq_gumbel_prepare_f32.restype = i32
-    lib.dvq_gumbel_prepare_f32.argtypes = [vp, vp, i32, i32, vp, sz, vp]
-    lib.dvq_vq_gumbel_assign_workspace_bytes.restype = sz
-    lib.dvq_vq_gumbel_assign_workspace_bytes.argtypes = [i32, i32]
-    lib.dvq_vq_gumbel_assign_f32.restype = i32
-    lib.dvq_vq_gumbel_assign_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, sz, vp]
-    lib.dvq_vq_assign_narrow_workspace_bytes.restype = sz
-    lib.dvq_vq_assign_narrow_workspace_bytes.argtypes = [i64]
-    lib.dvq_vq_assign_narrow_tile_codes.restype = i32
-    lib.dvq_vq_assign_narrow_tile_codes.argtypes = [i32]
-    lib.dvq_vq_assign_narrow_nchw_f32.restype = i32
-    lib.dvq_vq_assign_narrow_nchw_f32.argtypes = [vp, vp, vp, i32, i32, i32, i32, f32, vp, vp, vp, vp, sz, vp]
-    lib.dvq_vq_assign_narrow_flat_f32.restype = i32
-    lib.dvq_vq_assign_narrow_flat_f32.argtypes = [vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp, sz, vp]
-    lib.dvq_code_stats_f32.restype = i32
-    lib.dvq_code_stats_f32.argtypes = [vp, i64, i32, vp, vp, vp, vp, vp]
-    lib.dvq_code_stats_grain_f32.restype = i32
-    lib.dvq_code_stats_grain_f32.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, i32, vp, vp, vp, vp, vp]
-    lib.dvq_vq_cdist_sample_assign_f32.restype = i32
-    lib.dvq_vq_cdist_sample_assign_f32.argtypes = [vp, vp, i32, i32, i32, i32, f32, vp, i64, vp, vp]
-    lib.dvq_ortho_loss_workspace_bytes.restype = sz
-    lib.dvq_ortho_loss_workspace_bytes.argtypes = [i32, i32, i32]
-    lib.dvq_ortho_loss_forward_f32.restype = i32
-    lib.dvq_ortho_loss_forward_f32.argtypes = [vp, i32, i32, i32, vp, vp, vp, sz, vp]
-    lib.dvq_ortho_loss_backward_f32.restype = i32
-    lib.dvq_ortho_loss_backward_f32.argtypes = [vp, vp, vp, i32, i32, i32, vp, vp, sz, vp]
-    lib.dvq_lucid_update_f32.restype = i32
-    lib.dvq_lucid_update_f32.argtypes = [i32, vp, vp, f32, f32, f32, i32, i32, vp, vp, vp, vp, vp, i32, i32, vp, vp]
-    return lib
+    protos = dict(_PROTOTYPES)
+    if hasattr(lib, "dvq_tuning_buffers"):                 # tuning build only; not in the header
+        protos["dvq_tuning_buffers"] = (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p])
+    checked = types.SimpleNamespace()
+    for name, (restype, argtypes) in protos.items():
+        raw, fn = getattr(lib, name), lib[name]            # lib[name] is a function object of its own, lib.name the cached one
+        raw.restype, raw.argtypes = restype, argtypes
+        fn.restype, fn.argtypes = restype, argtypes
+        if restype is ctypes.c_int and name not in _INT_QUERIES:
+            fn.errcheck = _raise_on_error
+        setattr(checked, name, fn)
+    return lib, checked
 
 
-lib = _load()
+# lib.dvq_x(...) returns the status code; checked.dvq_x(...) raises DvqError on a non-zero one (size queries: no difference)
+lib, checked = _load()
 # DVQ_MODE_WS_CLEAN exists since ABI 0.5.0 (an older build loaded through DVQ_LIBRARY for an A/B rejects the flag)
 HAS_WS_CLEAN = lib.dvq_version() >= 500
 

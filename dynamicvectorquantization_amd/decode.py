@@ -20,7 +20,7 @@ from torch import nn
 from . import _lib
 from ._prepared import PreparedImage
 
-_L = _lib.lib
+checked = _lib.checked
 
 # Decoder.forward's dispatch on position_type (DecoderPositional.py:110-118), restated with its quirks: "learned" and
 # "learned-relative" construct a position_bias that forward never applies
@@ -112,9 +112,9 @@ class DecodeHead:
             cb = None if conv.bias is None else _lib.require_cuda_f32(conv.bias.detach(), "post_quant_conv.bias")
             if cw.device != w.device:
                 raise _lib.DvqError("post_quant_conv is on %s, the codebook on %s" % (cw.device, w.device))
-            nbytes = _L.dvq_decode_table_bytes(rows, C)
-            buf = self._table.rebuild(key, w.device, nbytes, lambda p, size, stream: _lib.check(_L.dvq_decode_table_prepare_f32(
-                e.data_ptr(), rows, D, cw.data_ptr(), _lib.ptr(cb), C, p, size, stream), "dvq_decode_table_prepare_f32"))
+            nbytes = checked.dvq_decode_table_bytes(rows, C)
+            buf = self._table.rebuild(key, w.device, nbytes, lambda p, size, stream: checked.dvq_decode_table_prepare_f32(
+                e.data_ptr(), rows, D, cw.data_ptr(), _lib.ptr(cb), C, p, size, stream))
         return buf[:rows * C * 4].view(torch.float32).view(rows, C)
 
     def position_tables(self, H, W, device):
@@ -166,8 +166,8 @@ class DecodeHead:
             first, second = self.position_tables(H, W, dev)
             h_in = torch.empty((B, C, H, W), dtype=torch.float32, device=dev)
             if B * H * W:
-                _lib.check(_L.dvq_decode_head_f32(codes.data_ptr(), B, H * W, T.data_ptr(), rows, C, _lib.ptr(first),
-                                                  _lib.ptr(second), h_in.data_ptr(), _lib.stream_ptr(dev)), "dvq_decode_head_f32")
+                checked.dvq_decode_head_f32(codes.data_ptr(), B, H * W, T.data_ptr(), rows, C, _lib.ptr(first),
+                                            _lib.ptr(second), h_in.data_ptr(), _lib.stream_ptr(dev))
         return h_in
 
     def from_tokens(self, permuter, coarse_content, fine_content, coarse_position, fine_position):

@@ -352,7 +352,7 @@ class CodeExchange:
         self._pending = None
         self._result = None
         if self.on_gpu:
-            self.nbytes = _lib.lib.dvq_exchange_bytes(self.cpi, self.gpi, self.b_max, num_codes)
+            self.nbytes = _lib.checked.dvq_exchange_bytes(self.cpi, self.gpi, self.b_max, num_codes)
             self.local = torch.empty(self.nbytes, dtype=torch.uint8, device=self.dev)
             self.gathered = torch.empty(self.world * self.nbytes, dtype=torch.uint8, device=self.dev)
             self.g_codes = torch.empty((global_batch,) + self.cshape, dtype=torch.int64, device=self.dev)
@@ -371,10 +371,9 @@ class CodeExchange:
             return
         assert codes.is_contiguous() and codes.dtype == torch.int64 and codes.shape[0] == self.b_local
         with _lib.on_device(self.dev):
-            _lib.check(_lib.lib.dvq_exchange_pack(
+            _lib.checked.dvq_exchange_pack(
                 codes.data_ptr(), _lib.ptr(grain) if self.gpi else 0, _lib.ptr(loss), numel, self.b_local, self.b_max,
-                self.cpi, self.gpi, self.num_codes, self.local.data_ptr(), _lib.stream_ptr(self.dev)),
-                "dvq_exchange_pack")
+                self.cpi, self.gpi, self.num_codes, self.local.data_ptr(), _lib.stream_ptr(self.dev))
         self._pending = dist.all_gather_into_tensor(self.gathered, self.local, group=self.group, async_op=True)
 
     def finish(self):
@@ -387,10 +386,9 @@ class CodeExchange:
         self._pending.wait()                       # the current stream waits for the collective
         self._pending = None
         with _lib.on_device(self.dev):
-            _lib.check(_lib.lib.dvq_exchange_unpack(
+            _lib.checked.dvq_exchange_unpack(
                 self.gathered.data_ptr(), self.world, self.global_batch, self.cpi, self.gpi, self.num_codes,
-                self.g_codes.data_ptr(), _lib.ptr(self.g_grain), self.g_mean.data_ptr(), _lib.stream_ptr(self.dev)),
-                "dvq_exchange_unpack")
+                self.g_codes.data_ptr(), _lib.ptr(self.g_grain), self.g_mean.data_ptr(), _lib.stream_ptr(self.dev))
         self._result = (self.g_codes, self.g_grain, self.g_mean[0])
         return self._result
 

@@ -37,8 +37,7 @@ class Entropy(nn.Sequential):
         if B == 0:
             return out
         with _lib.on_device(x.device):
-            _lib.check(_lib.lib.dvq_entropy_map_f32(x.data_ptr(), B, H, W, 16, out.data_ptr(),
-                                                    _lib.stream_ptr(x.device)), "dvq_entropy_map_f32")
+            _lib.checked.dvq_entropy_map_f32(x.data_ptr(), B, H, W, 16, out.data_ptr(), _lib.stream_ptr(x.device))
         return out
 
 

@@ -35,7 +35,7 @@ from ._prepared import InvalidatesPrepared
 from .quantize import (KERNEL_WIDTHS, _CodebookPrep, _kmeans_lloyd, _batched_sample_vectors, _pad_channels, _restart_pick,
                        _vq_given_codes, _wide_width, embed_gather, score_assign, vq_assign)
 
-_lib_handle = _lib.lib
+checked = _lib.checked
 
 __all__ = ["orthogonal_loss_fn", "EuclideanCodebook", "CosineSimCodebook", "VectorQuantize", "cdist_sample_assign"]
 
@@ -62,11 +62,10 @@ class _OrthogonalLoss(torch.autograd.Function):
         tc = t.detach().contiguous()
         rinv = torch.empty((h, n), dtype=torch.float32, device=dev)
         loss = torch.empty((), dtype=torch.float32, device=dev)
-        ws = torch.empty(max(_lib_handle.dvq_ortho_loss_workspace_bytes(h, n, d), 256), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(checked.dvq_ortho_loss_workspace_bytes(h, n, d), 256), dtype=torch.uint8, device=dev)
         with _lib.on_device(dev):
-            _lib.check(_lib_handle.dvq_ortho_loss_forward_f32(tc.data_ptr(), h, n, d, rinv.data_ptr(), loss.data_ptr(),
-                                                              ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
-                       "dvq_ortho_loss_forward_f32")
+            checked.dvq_ortho_loss_forward_f32(tc.data_ptr(), h, n, d, rinv.data_ptr(), loss.data_ptr(),
+                                               ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
         ctx.save_for_backward(tc, rinv)
         return loss
 
@@ -77,11 +76,10 @@ class _OrthogonalLoss(torch.autograd.Function):
         dev = tc.device
         g = g.reshape(1).to(torch.float32).contiguous()
         grad = torch.empty_like(tc)
-        ws = torch.empty(max(_lib_handle.dvq_ortho_loss_workspace_bytes(h, n, d), 256), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(checked.dvq_ortho_loss_workspace_bytes(h, n, d), 256), dtype=torch.uint8, device=dev)
         with _lib.on_device(dev):
-            _lib.check(_lib_handle.dvq_ortho_loss_backward_f32(tc.data_ptr(), rinv.data_ptr(), g.data_ptr(), h, n, d,
-                                                               grad.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev)),
-                       "dvq_ortho_loss_backward_f32")
+            checked.dvq_ortho_loss_backward_f32(tc.data_ptr(), rinv.data_ptr(), g.data_ptr(), h, n, d,
+                                                grad.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(dev))
         return grad
 
 
@@ -95,7 +93,7 @@ def orthogonal_loss_fn(t):
         raise ValueError("t must be [h, n, d] or [n, d], got %s" % (tuple(t.shape),))
     h, n, d = t.shape
     if (t.is_cuda and t.dtype == torch.float32 and d in KERNEL_WIDTHS and h >= 1 and n >= 1
-            and _lib_handle.dvq_ortho_loss_workspace_bytes(h, n, d) != 0):
+            and checked.dvq_ortho_loss_workspace_bytes(h, n, d) != 0):
         return _OrthogonalLoss.apply(t)
     return _orthogonal_loss_torch(t)
 
@@ -127,9 +125,9 @@ def cdist_sample_assign(x, codebook, prep, temp, u):
         x, codebook = _pad_channels(x, Dp), prep.padded_codebook(codebook, Dp)
     with _lib.on_device(dev):
         pbuf = prep.get(codebook)
-        _lib.check(_lib_handle.dvq_vq_cdist_sample_assign_f32(
+        checked.dvq_vq_cdist_sample_assign_f32(
             x.data_ptr(), pbuf.data_ptr(), B, Dp, HW, K, temp, u.data_ptr(), u.numel(), codes.data_ptr(),
-            _lib.stream_ptr(dev)), "dvq_vq_cdist_sample_assign_f32")
+            _lib.stream_ptr(dev))
     return codes
 
 
@@ -252,16 +250,15 @@ class _Codebook(InvalidatesPrepared, nn.Module):
             small = torch.empty(2, dtype=torch.int64, device=dev)
             perp = torch.empty((), dtype=torch.float32, device=dev)
             with _lib.on_device(dev):
-                _lib.check(_lib_handle.dvq_code_stats_f32(codes.data_ptr(), N, K, cnt64.data_ptr(), small.data_ptr(), perp.data_ptr(),
-                                                          0, _lib.stream_ptr(dev)), "dvq_code_stats_f32")
+                checked.dvq_code_stats_f32(codes.data_ptr(), N, K, cnt64.data_ptr(), small.data_ptr(), perp.data_ptr(),
+                                           0, _lib.stream_ptr(dev))
             flat = counts = cnt64.to(torch.float32)
         else:
             flat = torch.empty(K * D + K, dtype=torch.float32, device=dev)
             sums, counts = flat[:K * D].view(K, D), flat[K * D:]
             with _lib.on_device(dev):
-                _lib.check(_lib_handle.dvq_ema_accumulate_nchw_f32(toks.data_ptr(), codes.data_ptr(), N, D, 1, K, counts.data_ptr(),
-                                                                   sums.data_ptr(), _lib.stream_ptr(dev)),
-                           "dvq_ema_accumulate_nchw_f32")
+                checked.dvq_ema_accumulate_nchw_f32(toks.data_ptr(), codes.data_ptr(), N, D, 1, K, counts.data_ptr(),
+                                                    sums.data_ptr(), _lib.stream_ptr(dev))
         if _ddp():
             dist.all_reduce(flat, op=dist.ReduceOp.SUM)            # the step's statistics: one collective
         thr = float(self.threshold_ema_dead_code)
@@ -275,10 +272,10 @@ class _Codebook(InvalidatesPrepared, nn.Module):
         def launch(pick_t, threshold):
             B, HW = (z.shape[0], z[0, 0].numel()) if channel_major else (N, 1)
             with _lib.on_device(dev):
-                _lib.check(_lib_handle.dvq_lucid_update_f32(
+                checked.dvq_lucid_update_f32(
                     self._kind, counts.data_ptr(), _lib.ptr(sums), float(self.decay), float(self.eps), threshold, K, D,
                     self.cluster_size.data_ptr(), cs_new.data_ptr(), 0 if self._kind else self.embed_avg.data_ptr(), embed.data_ptr(),
-                    z.data_ptr(), B, HW, _lib.ptr(pick_t), _lib.stream_ptr(dev)), "dvq_lucid_update_f32")
+                    z.data_ptr(), B, HW, _lib.ptr(pick_t), _lib.stream_ptr(dev))
 
         if thr > 0 and pick is None:
             # fewer tokens than codes: the reference's own calls, host read included (quantize_lucidrains.py:92, common_utils.py:43-50)

@@ -14,7 +14,7 @@ from torch import nn
 
 from . import _lib
 
-_L = _lib.lib
+checked = _lib.checked
 
 
 def _i64_cuda(t, name):
@@ -86,8 +86,7 @@ class DualGrainSeperatePermuter(nn.Module):
             else:
                 counts = torch.empty((B, 2), dtype=torch.int32, device=dev)
                 maxes = torch.empty(2, dtype=torch.int32, device=dev)
-                _lib.check(_L.dvq_permute_dual_count_i64(grain.data_ptr(), B, hc, hc, counts.data_ptr(), maxes.data_ptr(), st),
-                           "dvq_permute_dual_count_i64")
+                checked.dvq_permute_dual_count_i64(grain.data_ptr(), B, hc, hc, counts.data_ptr(), maxes.data_ptr(), st)
                 mc, mf = maxes.tolist()                               # the sync pad_sequence implies
                 Lc, Lf = mc + 1, 4 * mf + 1
             if out is not None:
@@ -99,9 +98,8 @@ class DualGrainSeperatePermuter(nn.Module):
                 outs = [torch.empty((B, Lc), dtype=torch.int64, device=dev) for _ in range(3)] + \
                        [torch.empty((B, Lf), dtype=torch.int64, device=dev) for _ in range(3)]
             order = 0 if self.fine_position_order == "region-first" else 1
-            _lib.check(_L.dvq_permute_dual_forward_i64(indices.data_ptr(), grain.data_ptr(), B, hc, hc, order, Lc, Lf,
-                                                       self._special, *[o.data_ptr() for o in outs], st),
-                       "dvq_permute_dual_forward_i64")
+            checked.dvq_permute_dual_forward_i64(indices.data_ptr(), grain.data_ptr(), B, hc, hc, order, Lc, Lf,
+                                                 self._special, *[o.data_ptr() for o in outs], st)
         return {"coarse_content": outs[0], "fine_content": outs[3], "coarse_position": outs[1],
                 "fine_position": outs[4], "coarse_segment": outs[2], "fine_segment": outs[5]}
 
@@ -114,9 +112,8 @@ class DualGrainSeperatePermuter(nn.Module):
             raise ValueError("content / position shapes differ")
         target = torch.empty((B, self.fine_hw, self.fine_hw), dtype=torch.int64, device=cc.device)
         with _lib.on_device(cc.device):
-            _lib.check(_L.dvq_permute_dual_backward_i64(cc.data_ptr(), fc.data_ptr(), cp.data_ptr(), fp.data_ptr(),
-                                                        B, Lc, Lf, self.hw1, self.hw1,
-                                                        self.coarse_position_eos_code, self.fine_position_eos_code,
-                                                        target.data_ptr(), _lib.stream_ptr(cc.device)),
-                       "dvq_permute_dual_backward_i64")
+            checked.dvq_permute_dual_backward_i64(cc.data_ptr(), fc.data_ptr(), cp.data_ptr(), fp.data_ptr(),
+                                                  B, Lc, Lf, self.hw1, self.hw1,
+                                                  self.coarse_position_eos_code, self.fine_position_eos_code,
+                                                  target.data_ptr(), _lib.stream_ptr(cc.device))
         return target

@@ -18,7 +18,7 @@ from torch import nn
 from . import _lib
 from ._prepared import PreparedImage
 
-_lib_handle = _lib.lib
+checked = _lib.checked
 
 
 class _ConvPrep(PreparedImage):
@@ -33,13 +33,13 @@ class _ConvPrep(PreparedImage):
             return self.buf
         buf = self.lookup(key, w.device)
         if buf is None:
-            nbytes = _lib_handle.dvq_qconv_prep_bytes(D)
+            nbytes = checked.dvq_qconv_prep_bytes(D)
             if nbytes == 0:
                 raise _lib.DvqError("quant_conv: unsupported channel count %d" % D)
             w2 = _lib.require_cuda_f32(w.detach().reshape(D, D), "quant_conv.weight")
             b2 = None if bias is None else _lib.require_cuda_f32(bias.detach(), "quant_conv.bias")
-            buf = self.rebuild(key, w.device, nbytes, lambda buf, size, stream: _lib.check(_lib_handle.dvq_qconv_prepare_f32(
-                w2.data_ptr(), _lib.ptr(b2), D, buf, size, stream), "dvq_qconv_prepare_f32"))
+            buf = self.rebuild(key, w.device, nbytes, lambda buf, size, stream: checked.dvq_qconv_prepare_f32(
+                w2.data_ptr(), _lib.ptr(b2), D, buf, size, stream))
         return buf
 
 
@@ -87,8 +87,8 @@ def quant_conv(conv, x):
         return h
     with _lib.on_device(x.device):
         pbuf = _prep_of(conv).get(conv)
-        _lib.check(_lib_handle.dvq_qconv_f32(x.data_ptr(), pbuf.data_ptr(), B, D, HW, h.data_ptr(),
-                                             _lib.stream_ptr(x.device)), "dvq_qconv_f32")
+        checked.dvq_qconv_f32(x.data_ptr(), pbuf.data_ptr(), B, D, HW, h.data_ptr(),
+                              _lib.stream_ptr(x.device))
     return h
 
 
@@ -138,8 +138,8 @@ def quant_conv_select(conv, h_coarse, h_fine, h_median=None, gate=None, entropy=
     if h.numel() > 0:
         with _lib.on_device(dev):
             pbuf = _prep_of(conv).get(conv)
-            _lib.check(_lib_handle.dvq_qconv_select_f32(
+            checked.dvq_qconv_select_f32(
                 nb, g.data_ptr(), kind, thr, h_coarse.data_ptr(), _lib.ptr(h_median), h_fine.data_ptr(), pbuf.data_ptr(),
                 B, D, hc, wc, h.data_ptr(), indices.data_ptr(), cmask.data_ptr(), _lib.ptr(gate_out),
-                _lib.stream_ptr(dev)), "dvq_qconv_select_f32")
+                _lib.stream_ptr(dev))
     return {"h": h, "indices": indices, "codebook_mask": cmask, "gate": gate_out if entropy is not None else gate}

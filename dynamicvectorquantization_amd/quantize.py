@@ -23,7 +23,7 @@ from torch.nn import functional as F
 from . import _lib
 from ._prepared import InvalidatesPrepared, PreparedImage
 
-_lib_handle = _lib.lib
+checked = _lib.checked
 
 
 class _Workspace:
@@ -48,12 +48,8 @@ class _Workspace:
         return self.t.data_ptr(), self.t.numel(), mode | flag
 
     def end(self, mode):
+        """checked.fn(..., *ws.begin(mode), ...); ws.end(mode) -- a call that raises skips `end`: the workspace stays dirty"""
         self.clean = mode in (_lib.MODE_FILTER, _lib.MODE_FILTER_WIDE)
-
-    def check(self, mode, rc, what):
-        """ws.check(mode, lib.fn(..., *ws.begin(mode), ...), "fn"): raises on failure (the workspace then stays dirty)"""
-        _lib.check(rc, what)
-        self.end(mode)
 
     def __getitem__(self, sl):                      # (fallback_count reads two counters)
         return self.t[sl]
@@ -95,7 +91,7 @@ class _CodebookPrep(PreparedImage):
         buf = self.lookup(key, dev)
         if buf is not None:
             return buf
-        nbytes = _lib_handle.dvq_codebook_prep_bytes(K, D)
+        nbytes = checked.dvq_codebook_prep_bytes(K, D)
         if nbytes == 0:
             raise _lib.DvqError("unsupported codebook shape K=%d D=%d" % (K, D))
         cur = torch.cuda.current_stream(dev)
@@ -105,8 +101,8 @@ class _CodebookPrep(PreparedImage):
         self._users.clear()
         self._drop_folds()                           # the fold images derive from this one: retired with it
         # outside training (load_state_dict, invalidate, .to()) no use events exist: the new image goes to a fresh buffer
-        return self.rebuild(key, dev, nbytes, lambda buf, size, stream: _lib.check(_lib_handle.dvq_codebook_prepare_f32(
-            codebook.data_ptr(), K, D, buf, size, stream), "dvq_codebook_prepare_f32"), in_place=self.track_users)
+        return self.rebuild(key, dev, nbytes, lambda buf, size, stream: checked.dvq_codebook_prepare_f32(
+            codebook.data_ptr(), K, D, buf, size, stream), in_place=self.track_users)
 
     def _drop_folds(self):
         """forget the fold images; their buffers, and the ones they had retired themselves, stay alive in this image's list"""
@@ -130,14 +126,13 @@ class _CodebookPrep(PreparedImage):
             img.invalidate()                             # optimizers may write through .data
         fbuf = img.buf if (key == img.key and img._built is None) else img.lookup(key, codebook.device)
         if fbuf is None:
-            nbytes = _lib_handle.dvq_fold_prep_bytes(K, D)
+            nbytes = checked.dvq_fold_prep_bytes(K, D)
             if nbytes == 0:
                 raise _lib.DvqError("fold: unsupported codebook shape K=%d D=%d" % (K, D))
             w2 = _lib.require_cuda_f32(w.detach().reshape(D, D), "quant_conv.weight")
             b2 = None if bias is None else _lib.require_cuda_f32(bias.detach(), "quant_conv.bias")
-            fbuf = img.rebuild(key, codebook.device, nbytes, lambda buf, size, stream: _lib.check(
-                _lib_handle.dvq_fold_prepare_f32(codebook.data_ptr(), K, D, pbuf.data_ptr(), w2.data_ptr(), _lib.ptr(b2),
-                                                 buf, size, stream), "dvq_fold_prepare_f32"))
+            fbuf = img.rebuild(key, codebook.device, nbytes, lambda buf, size, stream: checked.dvq_fold_prepare_f32(
+                codebook.data_ptr(), K, D, pbuf.data_ptr(), w2.data_ptr(), _lib.ptr(b2), buf, size, stream))
         return pbuf, fbuf
 
     def padded_codebook(self, codebook, Dp):
@@ -169,11 +164,11 @@ class _CodebookPrep(PreparedImage):
         ws = self._ws.get(key)
         if ws is None:
             if nbytes is None and isinstance(HW, tuple):        # routed workspace: ("routed2" | "routed3", hc, wc)
-                nbytes = _lib_handle.dvq_vq_assign_routed_workspace_bytes(int(HW[0][-1]), B, D, HW[1], HW[2], K, mode)
+                nbytes = checked.dvq_vq_assign_routed_workspace_bytes(int(HW[0][-1]), B, D, HW[1], HW[2], K, mode)
                 if nbytes == 0:
                     raise _lib.DvqError("routed assign: unsupported shape B=%d D=%d hc=%d wc=%d K=%d" % (B, D, HW[1], HW[2], K))
             if nbytes is None:
-                nbytes = _lib_handle.dvq_vq_assign_workspace_bytes(B, D, HW, K, mode)
+                nbytes = checked.dvq_vq_assign_workspace_bytes(B, D, HW, K, mode)
             if len(self._ws) >= 8:                   # shapes rarely change: keep the table small
                 self._ws.clear()
             ws = _Workspace(nbytes, device)
@@ -190,9 +185,9 @@ class _CodebookPrep(PreparedImage):
         if mode not in _lib.FILTER_MODES:
             return (0, 0)
         if isinstance(HW, tuple):                   # routed workspace: ("routed2" | "routed3", hc, wc)
-            off = _lib_handle.dvq_vq_assign_routed_fallback_count_offset(int(HW[0][-1]), B, D, HW[1], HW[2], K)
+            off = checked.dvq_vq_assign_routed_fallback_count_offset(int(HW[0][-1]), B, D, HW[1], HW[2], K)
         else:
-            off = _lib_handle.dvq_vq_assign_fallback_count_offset(B, D, HW, K)
+            off = checked.dvq_vq_assign_fallback_count_offset(B, D, HW, K)
         c = ws[off:off + 8].view(torch.int32).tolist()
         return (int(c[0]), int(c[1]))
 
@@ -250,7 +245,7 @@ def _restart_pick(n, k, device):
     seed = int(torch.empty((), dtype=torch.int64).random_(generator=_RESTART_GEN[1]).item()) & 0x7FFFFFFFFFFFFFFF
     out = torch.empty(k, dtype=torch.int64, device=device)
     with _lib.on_device(device):
-        _lib.check(_lib_handle.dvq_restart_pick_i64(seed, n, k, out.data_ptr(), _lib.stream_ptr(device)), "dvq_restart_pick_i64")
+        checked.dvq_restart_pick_i64(seed, n, k, out.data_ptr(), _lib.stream_ptr(device))
     return out
 
 
@@ -355,50 +350,54 @@ def vq_assign(z, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=T
         # the exact narrow kernel: no prepared image, no modes (`mode` is accepted and ignored); row-major [N, D] by the flat form
         ws_ptr, ws_bytes = 0, 0
         if loss is not None:
-            ws = prep.workspace(B, D, HW, K, "narrow", z.device, nbytes=_lib_handle.dvq_vq_assign_narrow_workspace_bytes(B * HW))
+            ws = prep.workspace(B, D, HW, K, "narrow", z.device, nbytes=checked.dvq_vq_assign_narrow_workspace_bytes(B * HW))
             ws_ptr, ws_bytes = ws.t.data_ptr(), ws.t.numel()
         with _lib.on_device(z.device):
             if HW == 1:
-                _lib.check(_lib_handle.dvq_vq_assign_narrow_flat_f32(
+                checked.dvq_vq_assign_narrow_flat_f32(
                     z.data_ptr(), codebook.data_ptr(), _lib.ptr(mask), B, D, K, float(beta), _lib.ptr(zq), codes.data_ptr(),
-                    _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(z.device)), "dvq_vq_assign_narrow_flat_f32")
+                    _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(z.device))
             else:
-                _lib.check(_lib_handle.dvq_vq_assign_narrow_nchw_f32(
+                checked.dvq_vq_assign_narrow_nchw_f32(
                     z.data_ptr(), codebook.data_ptr(), _lib.ptr(mask), B, D, HW, K, float(beta), _lib.ptr(zq), codes.data_ptr(),
-                    _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(z.device)), "dvq_vq_assign_narrow_nchw_f32")
+                    _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(z.device))
         return zq, codes, loss
     ws = prep.workspace(B, D, HW, K, mode, z.device)
     if fold:
         with _lib.on_device(z.device):
             qbuf, pbuf, fbuf = _fold_args(conv, prep, codebook, loss is not None, mode)
-            ws.check(mode, _lib_handle.dvq_vq_assign_fold_f32(
+            checked.dvq_vq_assign_fold_f32(
                 z.data_ptr(), qbuf.data_ptr(), fbuf.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(), B, D, HW, K,
-                _lib.ptr(zq), codes.data_ptr(), *ws.begin(mode), _lib.stream_ptr(z.device)), "dvq_vq_assign_fold_f32")
+                _lib.ptr(zq), codes.data_ptr(), *ws.begin(mode), _lib.stream_ptr(z.device))
+            ws.end(mode)
         return zq, codes, loss
     if conv is not None:
         with _lib.on_device(z.device):
             qbuf, hb, h_all = _conv_args(conv, prep, z.shape, z.device, h_buf)
             pbuf = prep.get(codebook)
-            ws.check(mode, _lib_handle.dvq_vq_assign_qconv_f32(
+            checked.dvq_vq_assign_qconv_f32(
                 z.data_ptr(), qbuf.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(), _lib.ptr(mask), B, D, HW, K, float(beta),
                 _lib.ptr(zq), codes.data_ptr(), _lib.ptr(loss), _lib.ptr(hb), int(h_all), *ws.begin(mode),
-                _lib.stream_ptr(z.device)), "dvq_vq_assign_qconv_f32")
+                _lib.stream_ptr(z.device))
+            ws.end(mode)
         return zq, codes, loss
     if HW == 1:
         # row-major [N, D] (channel_last inputs, VectorQuantize2List's concatenated rows, VQEmbedding.forward): the entry point
         # whose pass 1 reads / writes a token's row with 16-byte accesses
         with _lib.on_device(z.device):
             pbuf = prep.get(codebook)
-            ws.check(mode, _lib_handle.dvq_vq_assign_flat_f32(
+            checked.dvq_vq_assign_flat_f32(
                 z.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(), _lib.ptr(mask), B, D, K, float(beta),
-                _lib.ptr(zq), codes.data_ptr(), _lib.ptr(loss), *ws.begin(mode), _lib.stream_ptr(z.device)), "dvq_vq_assign_flat_f32")
+                _lib.ptr(zq), codes.data_ptr(), _lib.ptr(loss), *ws.begin(mode), _lib.stream_ptr(z.device))
+            ws.end(mode)
         return zq, codes, loss
     with _lib.on_device(z.device):
         pbuf = prep.get(codebook)
-        ws.check(mode, _lib_handle.dvq_vq_assign_nchw_f32(
+        checked.dvq_vq_assign_nchw_f32(
             z.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(), _lib.ptr(mask), B, D, HW, K, float(beta),
             _lib.ptr(zq), codes.data_ptr(), _lib.ptr(loss), *ws.begin(mode),
-            _lib.stream_ptr(z.device)), "dvq_vq_assign_nchw_f32")
+            _lib.stream_ptr(z.device))
+        ws.end(mode)
     return zq, codes, loss
 
 
@@ -442,11 +441,11 @@ def soft_assign(x, codebook, prep, temp=1.0, q=None, want_soft=True, want_dist=F
         pbuf = prep.get(codebook)
         ws_ptr, ws_bytes = 0, 0
         if soft is None and q is not None:
-            ws = prep.workspace(N, Dp, 1, K, "soft", dev, nbytes=_lib_handle.dvq_vq_soft_assign_workspace_bytes(N, Dp, K))
+            ws = prep.workspace(N, Dp, 1, K, "soft", dev, nbytes=checked.dvq_vq_soft_assign_workspace_bytes(N, Dp, K))
             ws_ptr, ws_bytes = ws.t.data_ptr(), ws.t.numel()
-        _lib.check(_lib_handle.dvq_vq_soft_assign_flat_f32(
+        checked.dvq_vq_soft_assign_flat_f32(
             flat.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(), N, Dp, K, temp, _lib.ptr(q), _lib.ptr(soft), _lib.ptr(dist),
-            codes.data_ptr(), ws_ptr, ws_bytes, _lib.stream_ptr(dev)), "dvq_vq_soft_assign_flat_f32")
+            codes.data_ptr(), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
     return soft, codes, dist
 
 
@@ -494,9 +493,9 @@ def score_assign(x, codebook, prep, metric=_lib.METRIC_L2, temp=0.0, u=None):
         x, codebook = _pad_channels(x, Dp), prep.padded_codebook(codebook, Dp)
     with _lib.on_device(dev):
         pbuf = prep.get(codebook)
-        _lib.check(_lib_handle.dvq_vq_score_assign_f32(
+        checked.dvq_vq_score_assign_f32(
             x.data_ptr(), pbuf.data_ptr(), B, Dp, HW, K, int(metric), temp, _lib.ptr(u), u_numel, codes.data_ptr(),
-            _lib.stream_ptr(dev)), "dvq_vq_score_assign_f32")
+            _lib.stream_ptr(dev))
     return codes
 
 
@@ -536,13 +535,13 @@ def apply_codes(z, codes, codebook, prep, mask=None, beta=0.25, want_zq=True, wa
         ws_ptr, ws_bytes = ws.t.data_ptr(), ws.t.numel()
     with _lib.on_device(dev):
         if HW == 1:
-            _lib.check(_lib_handle.dvq_vq_apply_codes_flat_f32(
+            checked.dvq_vq_apply_codes_flat_f32(
                 z.data_ptr(), codes.data_ptr(), codebook.data_ptr(), _lib.ptr(mask), B, D, K, float(beta), _lib.ptr(zq),
-                _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(dev)), "dvq_vq_apply_codes_flat_f32")
+                _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
         else:
-            _lib.check(_lib_handle.dvq_vq_apply_codes_nchw_f32(
+            checked.dvq_vq_apply_codes_nchw_f32(
                 z.data_ptr(), codes.data_ptr(), codebook.data_ptr(), _lib.ptr(mask), B, D, HW, K, float(beta), _lib.ptr(zq),
-                _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(dev)), "dvq_vq_apply_codes_nchw_f32")
+                _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(dev))
     return zq, loss
 
 
@@ -619,46 +618,48 @@ def _vq_assign_routed(nb, h_coarse, h_median, h_fine, codebook, prep, gate, entr
         if fold:                                 # the conv folded into the codebook (see vq_assign): codes [+ z_q], no loss
             qbuf, pbuf, fbuf = _fold_args(conv, prep, codebook, loss is not None, mode)
             if dual:
-                ws.check(mode, _lib_handle.dvq_vq_assign_routed_fold_dual_f32(
+                checked.dvq_vq_assign_routed_fold_dual_f32(
                     g.data_ptr(), kind, thr, h_coarse.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(), fbuf.data_ptr(),
                     codebook.data_ptr(), pbuf.data_ptr(), B, D, hc, wc, K, zq_p, codes.data_ptr(), indices.data_ptr(),
-                    cmask.data_ptr(), _lib.ptr(gate_out), *ws.begin(mode), _lib.stream_ptr(dev)),
-                    "dvq_vq_assign_routed_fold_dual_f32")
+                    cmask.data_ptr(), _lib.ptr(gate_out), *ws.begin(mode), _lib.stream_ptr(dev))
+                ws.end(mode)
             else:
-                ws.check(mode, _lib_handle.dvq_vq_assign_routed_fold_triple_f32(
+                checked.dvq_vq_assign_routed_fold_triple_f32(
                     g.data_ptr(), kind, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(),
                     fbuf.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(), B, D, hc, wc, K, zq_p, codes.data_ptr(),
-                    indices.data_ptr(), cmask.data_ptr(), *ws.begin(mode), _lib.stream_ptr(dev)),
-                    "dvq_vq_assign_routed_fold_triple_f32")
+                    indices.data_ptr(), cmask.data_ptr(), *ws.begin(mode), _lib.stream_ptr(dev))
+                ws.end(mode)
         elif conv is not None:
             qbuf, hb, h_all = _conv_args(conv, prep, h_fine.shape, dev, h_buf)
             pbuf = prep.get(codebook)
             if dual:
-                ws.check(mode, _lib_handle.dvq_vq_assign_routed_qconv_dual_f32(
+                checked.dvq_vq_assign_routed_qconv_dual_f32(
                     g.data_ptr(), kind, thr, h_coarse.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(), codebook.data_ptr(),
                     pbuf.data_ptr(), B, D, hc, wc, K, float(beta), zq_p, codes.data_ptr(), loss_p,
                     indices.data_ptr(), cmask.data_ptr(), _lib.ptr(gate_out), _lib.ptr(hb), int(h_all), *ws.begin(mode),
-                    _lib.stream_ptr(dev)), "dvq_vq_assign_routed_qconv_dual_f32")
+                    _lib.stream_ptr(dev))
+                ws.end(mode)
             else:
-                ws.check(mode, _lib_handle.dvq_vq_assign_routed_qconv_triple_f32(
+                checked.dvq_vq_assign_routed_qconv_triple_f32(
                     g.data_ptr(), kind, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), qbuf.data_ptr(),
                     codebook.data_ptr(), pbuf.data_ptr(), B, D, hc, wc, K, float(beta), zq_p, codes.data_ptr(),
                     loss_p, indices.data_ptr(), cmask.data_ptr(), _lib.ptr(hb), int(h_all), *ws.begin(mode),
-                    _lib.stream_ptr(dev)), "dvq_vq_assign_routed_qconv_triple_f32")
+                    _lib.stream_ptr(dev))
+                ws.end(mode)
         else:
             pbuf = prep.get(codebook)
             if dual:
-                ws.check(mode, _lib_handle.dvq_vq_assign_routed_dual_f32(
+                checked.dvq_vq_assign_routed_dual_f32(
                     g.data_ptr(), kind, thr, h_coarse.data_ptr(), h_fine.data_ptr(), codebook.data_ptr(), pbuf.data_ptr(),
                     B, D, hc, wc, K, float(beta), zq_p, codes.data_ptr(), loss_p, indices.data_ptr(),
-                    cmask.data_ptr(), _lib.ptr(gate_out), *ws.begin(mode), _lib.stream_ptr(dev)),
-                    "dvq_vq_assign_routed_dual_f32")
+                    cmask.data_ptr(), _lib.ptr(gate_out), *ws.begin(mode), _lib.stream_ptr(dev))
+                ws.end(mode)
             else:
-                ws.check(mode, _lib_handle.dvq_vq_assign_routed_triple_f32(
+                checked.dvq_vq_assign_routed_triple_f32(
                     g.data_ptr(), kind, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), codebook.data_ptr(),
                     pbuf.data_ptr(), B, D, hc, wc, K, float(beta), zq_p, codes.data_ptr(), loss_p,
-                    indices.data_ptr(), cmask.data_ptr(), *ws.begin(mode), _lib.stream_ptr(dev)),
-                    "dvq_vq_assign_routed_triple_f32")
+                    indices.data_ptr(), cmask.data_ptr(), *ws.begin(mode), _lib.stream_ptr(dev))
+                ws.end(mode)
     return res
 
 
@@ -698,9 +699,8 @@ def embed_gather(codebook, idx):
         return codebook[idx]
     out = torch.empty(tuple(idx.shape) + (D,), dtype=torch.float32, device=codebook.device)
     with _lib.on_device(codebook.device):
-        _lib.check(_lib_handle.dvq_embed_gather_f32(codebook.data_ptr(), K, D, idx.data_ptr(), idx.numel(),
-                                                    out.data_ptr(), _lib.stream_ptr(codebook.device)),
-                   "dvq_embed_gather_f32")
+        checked.dvq_embed_gather_f32(codebook.data_ptr(), K, D, idx.data_ptr(), idx.numel(),
+                                     out.data_ptr(), _lib.stream_ptr(codebook.device))
     return out
 
 
@@ -756,19 +756,18 @@ class _VQStraightThrough(torch.autograd.Function):
             m = None if mask is None else _lib.require_cuda_f32(mask, "codebook_mask")
             gz = torch.empty_like(z)
             with _lib.on_device(z.device):
-                _lib.check(_lib_handle.dvq_vq_backward_nchw_f32(
+                checked.dvq_vq_backward_nchw_f32(
                     z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), _lib.ptr(gq), gl.data_ptr(),
-                    float(ctx.coef_z * scale), B, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device)),
-                    "dvq_vq_backward_nchw_f32")
+                    float(ctx.coef_z * scale), B, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device))
         if need_w and g_loss is not None and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and snap.shape[0] <= 8192:
             HW = z[0, 0].numel()
             gw = torch.zeros(ctx.wshape, dtype=z.dtype, device=z.device)
             gl = g_loss.reshape(1).to(torch.float32).contiguous()
             m = None if mask is None else _lib.require_cuda_f32(mask, "codebook_mask")
             with _lib.on_device(z.device):
-                _lib.check(_lib_handle.dvq_vq_backward_codebook_nchw_f32(
+                checked.dvq_vq_backward_codebook_nchw_f32(
                     z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), gl.data_ptr(), float(ctx.coef_e * scale),
-                    B, D, HW, snap.shape[0], gw.data_ptr(), _lib.stream_ptr(z.device)), "dvq_vq_backward_codebook_nchw_f32")
+                    B, D, HW, snap.shape[0], gw.data_ptr(), _lib.stream_ptr(z.device))
             need_w = False                                # done
         diff = None
         if (need_z and gz is None) or (need_w and g_loss is not None):
@@ -903,9 +902,9 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
             B, HW = z.shape[0], z[0, 0].numel()
             codes = idxs.reshape(B, HW).contiguous()
             with _lib.on_device(z.device):
-                _lib.check(_lib_handle.dvq_ema_accumulate_nchw_f32(
+                checked.dvq_ema_accumulate_nchw_f32(
                     z.data_ptr(), codes.data_ptr(), B, embed_dim, HW, n_embed, cluster_size.data_ptr(),
-                    vsum.data_ptr(), _lib.stream_ptr(z.device)), "dvq_ema_accumulate_nchw_f32")
+                    vsum.data_ptr(), _lib.stream_ptr(z.device))
         else:
             cluster_size.copy_(torch.bincount(idxs, minlength=n_embed))
             vsum.zero_().index_add_(0, idxs, vectors.to(torch.float32))
@@ -962,10 +961,10 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
                 restart = 1
         cs_new = torch.empty_like(self.cluster_size_ema)
         with _lib.on_device(z.device):
-            _lib.check(_lib_handle.dvq_ema_update_f32(
+            checked.dvq_ema_update_f32(
                 vectors_sum.data_ptr(), cluster_size.data_ptr(), float(self.decay), float(self.eps), n_embed, embed_dim,
                 self.cluster_size_ema.data_ptr(), cs_new.data_ptr(), self.embed_ema.data_ptr(), self.weight.data_ptr(),
-                restart, _lib.ptr(rows), z.data_ptr(), B, HW, _lib.ptr(pick), _lib.stream_ptr(z.device)), "dvq_ema_update_f32")
+                restart, _lib.ptr(rows), z.data_ptr(), B, HW, _lib.ptr(pick), _lib.stream_ptr(z.device))
         self.cluster_size_ema.copy_(cs_new)
         self._prep.invalidate()
 
@@ -1304,9 +1303,9 @@ def _kmeans_lloyd(flat, means, iters, all_reduce_fn=_noop, cosine=False):
         else:
             _, buckets, _ = vq_assign(flat, cb, prep, want_zq=False, want_loss=False, mode=_lib.MODE_EXACT)
         with _lib.on_device(dev):
-            _lib.check(_lib_handle.dvq_ema_accumulate_nchw_f32(
+            checked.dvq_ema_accumulate_nchw_f32(
                 flat.data_ptr(), buckets.data_ptr(), N, D, 1, K, counts.data_ptr(), sums.data_ptr(),
-                _lib.stream_ptr(dev)), "dvq_ema_accumulate_nchw_f32")
+                _lib.stream_ptr(dev))
         bins = counts.round().to(torch.int64).unsqueeze(0)        # [1, K]
         all_reduce_fn(bins)
         zero_mask = bins == 0
@@ -1559,17 +1558,17 @@ def gumbel_assign(z, prep_buf, embed, tau=1.0, q=None, kl_K=None, want_zq=True, 
         zq = torch.empty((B, d) + spatial, dtype=torch.float32, device=dev) if want_zq else None
         codes = torch.empty((B,) + spatial, dtype=torch.int64, device=dev)
         kl = torch.empty(1, dtype=torch.float32, device=dev) if want_kl else None
-        ws = torch.empty(_lib_handle.dvq_vq_gumbel_assign_workspace_bytes(B, max(HW, 1)), dtype=torch.uint8,
+        ws = torch.empty(checked.dvq_vq_gumbel_assign_workspace_bytes(B, max(HW, 1)), dtype=torch.uint8,
                          device=dev) if want_kl else None
     else:
         zq, codes, kl, ws = out
     if B * HW == 0:
         return zq, codes, kl
     with _lib.on_device(dev):
-        _lib.check(_lib_handle.dvq_vq_gumbel_assign_f32(
+        checked.dvq_vq_gumbel_assign_f32(
             z.data_ptr(), prep_buf.data_ptr(), embed.data_ptr(), B, C, HW, K, d, tau, float(K if kl_K is None else kl_K),
             _lib.ptr(q), _lib.ptr(zq), codes.data_ptr(), _lib.ptr(kl), _lib.ptr(ws), 0 if ws is None else ws.numel(),
-            _lib.stream_ptr(dev)), "dvq_vq_gumbel_assign_f32")
+            _lib.stream_ptr(dev))
     return zq, codes, kl
 
 
@@ -1655,13 +1654,13 @@ class GumbelQuantize(InvalidatesPrepared, nn.Module):
         buf = img.lookup(key, dev)
         if buf is not None:
             return buf
-        nbytes = _lib_handle.dvq_gumbel_prep_bytes(K, C)
+        nbytes = checked.dvq_gumbel_prep_bytes(K, C)
         if nbytes == 0:
             raise _lib.DvqError("unsupported projection shape K=%d C=%d" % (K, C))
         w2 = _lib.require_cuda_f32(w.detach().reshape(K, C), "proj.weight")
         b2 = None if bias is None else _lib.require_cuda_f32(bias.detach(), "proj.bias")
-        return img.rebuild(key, dev, nbytes, lambda pbuf, size, stream: _lib.check(_lib_handle.dvq_gumbel_prepare_f32(
-            w2.data_ptr(), _lib.ptr(b2), K, C, pbuf, size, stream), "dvq_gumbel_prepare_f32"))
+        return img.rebuild(key, dev, nbytes, lambda pbuf, size, stream: checked.dvq_gumbel_prepare_f32(
+            w2.data_ptr(), _lib.ptr(b2), K, C, pbuf, size, stream))
 
     def _fusable(self, z, hard, return_logits):
         if not hard or self.remap is not None or return_logits or z.dtype != torch.float32 or z.dim() != 4:
@@ -1774,8 +1773,8 @@ def code_usage(codes, K, grain_indices=None, want_encodings=False):
         perp = torch.empty((), dtype=torch.float32, device=dev)
         onehot = torch.empty((N, K), dtype=torch.float32, device=dev) if want_encodings else None
         with _lib.on_device(dev):
-            _lib.check(_lib_handle.dvq_code_stats_f32(codes.data_ptr(), N, K, counts.data_ptr(), n_used.data_ptr(), perp.data_ptr(),
-                                                      _lib.ptr(onehot), _lib.stream_ptr(dev)), "dvq_code_stats_f32")
+            checked.dvq_code_stats_f32(codes.data_ptr(), N, K, counts.data_ptr(), n_used.data_ptr(), perp.data_ptr(),
+                                       _lib.ptr(onehot), _lib.stream_ptr(dev))
         return CodeUsage(counts, perp, n_used, torch.full((), N, dtype=torch.int64, device=dev), onehot)
     if want_encodings:
         raise ValueError("want_encodings is not available with grain_indices (the one-hot matrix is per token, not per region)")
@@ -1798,9 +1797,9 @@ def code_usage(codes, K, grain_indices=None, want_encodings=False):
     small = torch.empty((2, G), dtype=torch.int64, device=dev)
     perp = torch.empty(G, dtype=torch.float32, device=dev)
     with _lib.on_device(dev):
-        _lib.check(_lib_handle.dvq_code_stats_grain_f32(codes.data_ptr(), g.data_ptr(), B, H, W, hc, wc, G, K, counts.data_ptr(),
-                                                        small[0].data_ptr(), small[1].data_ptr(), perp.data_ptr(),
-                                                        _lib.stream_ptr(dev)), "dvq_code_stats_grain_f32")
+        checked.dvq_code_stats_grain_f32(codes.data_ptr(), g.data_ptr(), B, H, W, hc, wc, G, K, counts.data_ptr(),
+                                         small[0].data_ptr(), small[1].data_ptr(), perp.data_ptr(),
+                                         _lib.stream_ptr(dev))
     return CodeUsage(counts, perp, small[1], small[0], None)
 
 
@@ -1949,11 +1948,11 @@ class EMAVectorQuantizer(InvalidatesPrepared, nn.Module):
         cs_new = torch.empty_like(emb.cluster_size.data)          # the update kernel's no-alias rule: every workgroup sums the OLD counts
         with _lib.on_device(z.device):
             st = _lib.stream_ptr(z.device)
-            _lib.check(_lib_handle.dvq_ema_accumulate_nchw_f32(z.data_ptr(), codes.data_ptr(), B, D, HW, K, csize.data_ptr(),
-                                                               vsum.data_ptr(), st), "dvq_ema_accumulate_nchw_f32")
-            _lib.check(_lib_handle.dvq_ema_update_f32(
+            checked.dvq_ema_accumulate_nchw_f32(z.data_ptr(), codes.data_ptr(), B, D, HW, K, csize.data_ptr(),
+                                                vsum.data_ptr(), st)
+            checked.dvq_ema_update_f32(
                 vsum.data_ptr(), csize.data_ptr(), float(emb.decay), float(emb.eps), K, D, emb.cluster_size.data_ptr(),
-                cs_new.data_ptr(), emb.embed_avg.data_ptr(), emb.weight.data_ptr(), 0, 0, 0, B, HW, 0, st), "dvq_ema_update_f32")
+                cs_new.data_ptr(), emb.embed_avg.data_ptr(), emb.weight.data_ptr(), 0, 0, 0, B, HW, 0, st)
         emb.cluster_size.data.copy_(cs_new)
         self._prep.invalidate()
 

@@ -23,7 +23,7 @@ import torch.nn as nn
 from . import _lib
 from ._prepared import InvalidatesPrepared, PreparedImage
 
-_lib_handle = _lib.lib
+checked = _lib.checked
 
 
 def entropy_gate(entropy, threshold):
@@ -33,9 +33,8 @@ def entropy_gate(entropy, threshold):
     if entropy.numel() == 0:
         return gate
     with _lib.on_device(entropy.device):
-        _lib.check(_lib_handle.dvq_entropy_gate_f32(entropy.data_ptr(), entropy.numel(), float(threshold),
-                                                    gate.data_ptr(), _lib.stream_ptr(entropy.device)),
-                   "dvq_entropy_gate_f32")
+        checked.dvq_entropy_gate_f32(entropy.data_ptr(), entropy.numel(), float(threshold),
+                                     gate.data_ptr(), _lib.stream_ptr(entropy.device))
     return gate
 
 
@@ -73,10 +72,9 @@ def _route_select_dual_raw(gate, h_coarse, h_fine, out=None):
     if h_dual.numel() == 0:
         return {"h_dual": h_dual, "indices": indices, "codebook_mask": cmask, "gate": gate.permute(0, 3, 1, 2)}
     with _lib.on_device(h_fine.device):
-        _lib.check(_lib_handle.dvq_route_select_dual_f32(
+        checked.dvq_route_select_dual_f32(
             g.data_ptr(), gdt, h_coarse.data_ptr(), h_fine.data_ptr(), B, C, hc, wc,
-            h_dual.data_ptr(), indices.data_ptr(), cmask.data_ptr(), _lib.stream_ptr(h_fine.device)),
-            "dvq_route_select_dual_f32")
+            h_dual.data_ptr(), indices.data_ptr(), cmask.data_ptr(), _lib.stream_ptr(h_fine.device))
     return {"h_dual": h_dual, "indices": indices, "codebook_mask": cmask, "gate": gate.permute(0, 3, 1, 2)}
 
 
@@ -101,10 +99,10 @@ def _route_select_dual_entropy_raw(entropy, threshold, h_coarse, h_fine, out=Non
         gate = torch.empty((B, hc, wc, 2), dtype=torch.int64, device=h_fine.device)
     if h_dual.numel() > 0:
         with _lib.on_device(h_fine.device):
-            _lib.check(_lib_handle.dvq_route_select_dual_entropy_f32(
+            checked.dvq_route_select_dual_entropy_f32(
                 entropy.data_ptr(), float(threshold), h_coarse.data_ptr(), h_fine.data_ptr(), B, C, hc, wc,
                 h_dual.data_ptr(), indices.data_ptr(), cmask.data_ptr(), gate.data_ptr(),
-                _lib.stream_ptr(h_fine.device)), "dvq_route_select_dual_entropy_f32")
+                _lib.stream_ptr(h_fine.device))
     return {"h_dual": h_dual, "indices": indices, "codebook_mask": cmask, "gate": gate.permute(0, 3, 1, 2)}
 
 
@@ -130,10 +128,9 @@ def _route_select_triple_raw(gate, h_coarse, h_median, h_fine, out=None):
     if h_triple.numel() == 0:
         return {"h_triple": h_triple, "indices": indices, "codebook_mask": cmask, "gate": gate.permute(0, 3, 1, 2)}
     with _lib.on_device(h_fine.device):
-        _lib.check(_lib_handle.dvq_route_select_triple_f32(
+        checked.dvq_route_select_triple_f32(
             g.data_ptr(), gdt, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), B, C, hc, wc,
-            h_triple.data_ptr(), indices.data_ptr(), cmask.data_ptr(), _lib.stream_ptr(h_fine.device)),
-            "dvq_route_select_triple_f32")
+            h_triple.data_ptr(), indices.data_ptr(), cmask.data_ptr(), _lib.stream_ptr(h_fine.device))
     return {"h_triple": h_triple, "indices": indices, "codebook_mask": cmask, "gate": gate.permute(0, 3, 1, 2)}
 
 
@@ -255,19 +252,18 @@ class _GateWeightPrep(PreparedImage):
             return self.buf
         buf = self.lookup(key, w1.device)
         if buf is None:
-            nbytes = _lib_handle.dvq_router_gate_prep_bytes(nb, C, hidden)
+            nbytes = checked.dvq_router_gate_prep_bytes(nb, C, hidden)
             if nbytes == 0:
                 raise _lib.DvqError("unsupported gate shape nb=%d C=%d hidden=%d" % (nb, C, hidden))
 
             def prepare(buf, size, stream):
-                _lib.check(_lib_handle.dvq_router_gate_prepare_f32(w1.data_ptr(), nb, C, hidden, buf, size, stream),
-                           "dvq_router_gate_prepare_f32")
+                checked.dvq_router_gate_prepare_f32(w1.data_ptr(), nb, C, hidden, buf, size, stream)
                 if gn is not None:
                     gw, gb = gn
                     p = lambda t: t.data_ptr()
-                    _lib.check(_lib_handle.dvq_router_gate_prepare_norm_f32(
+                    checked.dvq_router_gate_prepare_norm_f32(
                         nb, C, hidden, p(gw[0]), p(gb[0]), p(gw[1]) if nb == 3 else None, p(gb[1]) if nb == 3 else None,
-                        p(gw[-1]), p(gb[-1]), buf, size, stream), "dvq_router_gate_prepare_norm_f32")
+                        p(gw[-1]), p(gb[-1]), buf, size, stream)
             buf = self.rebuild(key, w1.device, nbytes, prepare)
         return buf
 
@@ -300,7 +296,7 @@ def fused_router_gate(gate, gate_type, norms, branches, weight_prep=None):
                                                else t.detach().float().contiguous()) for t in (w1, b1, w2, b2)]
     dev = hs[0].device
     out = torch.empty((B, hc, wc, nb), dtype=torch.float32, device=dev)
-    ws_bytes = _lib_handle.dvq_router_gate_workspace_bytes(nb, B, C, hc, wc, groups, hidden)
+    ws_bytes = checked.dvq_router_gate_workspace_bytes(nb, B, C, hc, wc, groups, hidden)
     if ws_bytes == 0:
         raise _lib.DvqError("unsupported router shape")
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
@@ -312,11 +308,11 @@ def fused_router_gate(gate, gate_type, norms, branches, weight_prep=None):
     prep = (weight_prep.get(w1, nb, C, gn=(gw, gb) if groups > 0 else None, owners=owners)
             if (weight_prep is not None and w1 is not None) else None)
     with _lib.on_device(dev):
-        _lib.check(_lib_handle.dvq_router_gate_f32(
+        checked.dvq_router_gate_f32(
             nb, hs[0].data_ptr(), ptr(med), hs[-1].data_ptr(), B, C, hc, wc, groups, float(eps),
             ptr(gw[0]), ptr(gb[0]), ptr(gw[1]) if nb == 3 else None, ptr(gb[1]) if nb == 3 else None,
             ptr(gw[-1]), ptr(gb[-1]), ptr(w1), ptr(b1), ptr(w2), ptr(b2), hidden, act, ptr(prep),
-            out.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)), "dvq_router_gate_f32")
+            out.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
     return out
 
 
@@ -453,7 +449,7 @@ class _RouteTrainFn(torch.autograd.Function):
         B, C, hc, wc = h_coarse.shape
         S = 2 if nb == 2 else 4
         dev = h_coarse.device
-        ws_bytes = _lib_handle.dvq_route_train_workspace_bytes(nb, B, C, hc, wc, groups, hidden)
+        ws_bytes = checked.dvq_route_train_workspace_bytes(nb, B, C, hc, wc, groups, hidden)
         if ws_bytes == 0:
             raise _lib.DvqError("unsupported router shape: num_branches=%d C=%d hidden=%d (C %% 8 == 0, num_branches*C <= 1280)"
                                 % (nb, C, hidden))
@@ -466,9 +462,9 @@ class _RouteTrainFn(torch.autograd.Function):
         args = ([nb] + [ptr(t) for t in hs] + [B, C, hc, wc, groups, eps] + [ptr(t) for t in params]
                 + [hidden, act, ptr(gumbels), tau])
         with _lib.on_device(dev):
-            _lib.check(_lib_handle.dvq_route_train_forward_f32(
+            checked.dvq_route_train_forward_f32(
                 *args, h_out.data_ptr(), indices.data_ptr(), cmask.data_ptr(), gate.data_ptr(), ws.data_ptr(), ws_bytes,
-                _lib.stream_ptr(dev)), "dvq_route_train_forward_f32")
+                _lib.stream_ptr(dev))
         ctx.meta, ctx.args, ctx.ws, ctx.hs, ctx.params = meta, args, ws, hs, params
         ctx.mark_non_differentiable(indices, cmask)
         return h_out, indices, cmask, gate
@@ -483,9 +479,9 @@ class _RouteTrainFn(torch.autograd.Function):
         dp = [None if t is None else torch.empty_like(t) for t in ctx.params]
         ptr = _lib.ptr
         with _lib.on_device(dev):
-            _lib.check(_lib_handle.dvq_route_train_backward_f32(
+            checked.dvq_route_train_backward_f32(
                 *ctx.args, ptr(g_out), ptr(g_gate), ctx.ws.data_ptr(), ctx.ws.numel(), *[ptr(t) for t in dh],
-                *[ptr(t) for t in dp], _lib.stream_ptr(dev)), "dvq_route_train_backward_f32")
+                *[ptr(t) for t in dp], _lib.stream_ptr(dev))
         return (None, None) + tuple(dh) + tuple(dp)
 
 

@@ -28,7 +28,7 @@ try:
 except ImportError:                                   # pragma: no cover
     from typing import Iterable
 
-_lib_handle = _lib.lib
+checked = _lib.checked
 
 
 class _RQGeom:
@@ -73,7 +73,7 @@ def _rq_forward(mod, x, want_grad, want_loss, training, assign=None):
         if loss is not None:
             loss.fill_(float("nan"))
         return out, loss, codes, None
-    nbytes = _lib_handle.dvq_rq_workspace_bytes(N, D, depth, int(want_grad))
+    nbytes = checked.dvq_rq_workspace_bytes(N, D, depth, int(want_grad))
     if nbytes == 0:
         raise _lib.DvqError("RQBottleneck: unsupported shape N=%d D=%d depth=%d" % (N, D, depth))
     if want_grad:
@@ -107,19 +107,18 @@ def _rq_forward(mod, x, want_grad, want_loss, training, assign=None):
                 c = assign(i, cb, r)
             if training:
                 cb._prep.used(dev)
-            _lib.check(_lib_handle.dvq_rq_step_f32(
+            checked.dvq_rq_step_f32(
                 x.data_ptr(), r.data_ptr(), weight.data_ptr(), cb.n_embed, c.data_ptr(), *g.args(), i, depth, int(want_grad),
-                codes.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream), "dvq_rq_step_f32")
+                codes.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
             if training and cb.ema:
                 with torch.no_grad():
                     cb._update_buffers(r, c)
                     cb._update_embedding()
             if i + 1 < depth:
-                off = _lib_handle.dvq_rq_residual_offset(N, D, depth, i + 1)
+                off = checked.dvq_rq_residual_offset(N, D, depth, i + 1)
                 r = ws[off:off + N * D * 4].view(torch.float32).view(N, D)
         if loss is not None:
-            _lib.check(_lib_handle.dvq_rq_loss_f32(N, D, depth, ws.data_ptr(), ws.numel(), loss.data_ptr(), stream),
-                       "dvq_rq_loss_f32")
+            checked.dvq_rq_loss_f32(N, D, depth, ws.data_ptr(), ws.numel(), loss.data_ptr(), stream)
     return out, loss, codes, ws
 
 
@@ -143,9 +142,9 @@ class _RQFunction(torch.autograd.Function):
         go = None if g_out is None else _lib.require_cuda_f32(g_out, "grad of out")
         gl = None if g_loss is None else g_loss.reshape(1).to(torch.float32).contiguous()
         with _lib.on_device(gx.device):
-            _lib.check(_lib_handle.dvq_rq_backward_f32(
+            checked.dvq_rq_backward_f32(
                 _lib.ptr(go), _lib.ptr(gl), *g.args(), g.depth, ws.data_ptr(), ws.numel(), gx.data_ptr(),
-                _lib.stream_ptr(gx.device)), "dvq_rq_backward_f32")
+                _lib.stream_ptr(gx.device))
         ctx.ws = None
         return gx, None, None
 
@@ -247,8 +246,8 @@ class RQBottleneck(nn.Module):
         ptrs = (ctypes.c_void_p * depth)(*[wt.data_ptr() for wt in ws])
         ks = (ctypes.c_int * depth)(*[wt.shape[0] for wt in ws])
         with _lib.on_device(code.device):
-            _lib.check(_lib_handle.dvq_rq_embed_code_f32(ptrs, ks, depth, code.data_ptr(), B, h, w, rH, rW, Dl, D, mode, j,
-                                                         out.data_ptr(), _lib.stream_ptr(code.device)), "dvq_rq_embed_code_f32")
+            checked.dvq_rq_embed_code_f32(ptrs, ks, depth, code.data_ptr(), B, h, w, rH, rW, Dl, D, mode, j,
+                                          out.data_ptr(), _lib.stream_ptr(code.device))
         return out
 
     @torch.no_grad()

@@ -18,7 +18,7 @@ import torch
 
 from . import _lib
 
-_L = _lib.lib
+checked = _lib.checked
 
 VARIANTS = ("class", "class2_entropy", "uncond")
 KINDS = ("coarse_position", "fine_position", "content")
@@ -164,11 +164,10 @@ def sample_step(logits, kind, rules, history=None, flag=None, temperature=1.0, t
         if t is not None and (tuple(t.shape) != (B, V) or t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev):
             raise ValueError("%s must be a contiguous float32 [B, V] tensor on %s" % (name, dev))
     with _lib.on_device(dev):
-        _lib.check(_L.dvq_sample_head_f32(last.data_ptr(), last.stride(0), B, V, float(temperature), rules._c[kind],
-                                          hptr, hstride, hlen, flag.data_ptr(), int(top_k or 0), float(top_p or 0.0),
-                                          1 if sample else 0, _lib.ptr(q) if sample else 0, ix.data_ptr(), ix.stride(0),
-                                          _lib.ptr(out_logits), _lib.ptr(out_probs), _lib.stream_ptr(dev)),
-                   "dvq_sample_head_f32")
+        checked.dvq_sample_head_f32(last.data_ptr(), last.stride(0), B, V, float(temperature), rules._c[kind],
+                                    hptr, hstride, hlen, flag.data_ptr(), int(top_k or 0), float(top_p or 0.0),
+                                    1 if sample else 0, _lib.ptr(q) if sample else 0, ix.data_ptr(), ix.stride(0),
+                                    _lib.ptr(out_logits), _lib.ptr(out_probs), _lib.stream_ptr(dev))
     return ix
 
 
@@ -187,9 +186,8 @@ def _transfer(model_or_rules, coarse_position, variant, max_len):
         if max_len is None:
             counts = torch.empty(B, dtype=torch.int32, device=dev)
             mx = torch.empty(1, dtype=torch.int32, device=dev)
-            _lib.check(_L.dvq_sample_transfer_count_i64(cp.data_ptr(), cp.stride(0), B, Lc, r.hw1, r.coarse_position_eos_code,
-                                                        variant, counts.data_ptr(), mx.data_ptr(), st),
-                       "dvq_sample_transfer_count_i64")
+            checked.dvq_sample_transfer_count_i64(cp.data_ptr(), cp.stride(0), B, Lc, r.hw1, r.coarse_position_eos_code,
+                                                  variant, counts.data_ptr(), mx.data_ptr(), st)
             L = (sos_mode != _lib.TRANSFER_SOS_NONE) + 4 * int(mx.item()) + 1      # the sync pad_sequence implies
         else:
             L = int(max_len)
@@ -197,10 +195,9 @@ def _transfer(model_or_rules, coarse_position, variant, max_len):
                 raise ValueError("max_len must be >= 1, got %r" % (max_len,))
         out = torch.empty((B, L), dtype=torch.int64, device=dev)
         order = 0 if r.fine_position_order == "region-first" else 1
-        _lib.check(_L.dvq_sample_transfer_fill_i64(cp.data_ptr(), cp.stride(0), B, Lc, r.hw1, r.coarse_position_eos_code,
-                                                   variant, order, sos_mode, int(r.fine_position_sos_code or 0),
-                                                   r.fine_position_eos_code, r.fine_position_pad_code, L, out.data_ptr(), st),
-                   "dvq_sample_transfer_fill_i64")
+        checked.dvq_sample_transfer_fill_i64(cp.data_ptr(), cp.stride(0), B, Lc, r.hw1, r.coarse_position_eos_code,
+                                             variant, order, sos_mode, int(r.fine_position_sos_code or 0),
+                                             r.fine_position_eos_code, r.fine_position_pad_code, L, out.data_ptr(), st)
     return out
 
 

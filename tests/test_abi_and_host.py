@@ -148,6 +148,95 @@ def test_size_queries_and_validation_without_gpu():
     assert L.dvq_vq_backward_codebook_nchw_f32(1, 1, 1, 0, 1, 1.0, 1, 256, 1, 10000, 1, 0) == -2                    # K > 8192
 
 
+def test_prototypes_are_derived_from_the_header():
+    """spot checks of the binding _lib derives from include/dvq.h, on the raw and on the checked function: every C type of the
+    mapping occurs (char pointer return, double, uint64_t, int64_t among ints, size_t as argument and as return, float) and the
+    host arrays `const float *const *` / `const int *` are plain pointers"""
+    from dynamicvectorquantization_amd import _lib
+    vp, i32, i64, u64, f32, f64, sz = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float,
+                                       ctypes.c_double, ctypes.c_size_t)
+    want = {
+        "dvq_last_error_string": (ctypes.c_char_p, []),
+        "dvq_exchange_pack": (i32, [vp, vp, vp, f64, i32, i32, i64, i64, i32, vp, vp]),
+        "dvq_restart_pick_i64": (i32, [u64, i64, i32, vp, vp]),
+        "dvq_vq_assign_flat_f32": (i32, [vp, vp, vp, vp, i64, i32, i32, f32, vp, vp, vp, vp, sz, i32, vp]),
+        "dvq_exchange_bytes": (sz, [i64, i64, i32, i32]),
+        "dvq_rq_embed_code_f32": (i32, [vp, vp, i32, vp, i32, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp]),
+    }
+    for name, (restype, argtypes) in want.items():
+        for fn in (getattr(_lib.lib, name), getattr(_lib.checked, name)):
+            assert fn.restype is restype, (name, fn.restype)
+            assert list(fn.argtypes or []) == argtypes, (name, fn.argtypes)
+    assert len(_lib.EXPORTS) == len(set(_lib.EXPORTS)) and all(hasattr(_lib.checked, n) for n in _lib.EXPORTS)
+
+
+def test_header_parser_fails_loudly():
+    """a parameter type outside the mapping and a DVQ_API declaration the parser cannot match raise, naming the declaration:
+    nothing is skipped and nothing defaults to int"""
+    from dynamicvectorquantization_amd import _lib
+    ok = "#define DVQ_API __attribute__((visibility(\"default\")))\n/* DVQ_API in a comment */\nDVQ_API int dvq_a(void);\n"
+    assert _lib._parse_header(ok + "DVQ_API size_t dvq_b(const float *z,\n   int64_t n); // DVQ_API too\n") == {
+        "dvq_a": (ctypes.c_int, []), "dvq_b": (ctypes.c_size_t, [ctypes.c_void_p, ctypes.c_int64])}
+    with pytest.raises(_lib.DvqError, match=r"dvq_bad.*long double x"):
+        _lib._parse_header(ok + "DVQ_API int dvq_bad(int n, long double x);\n")
+    with pytest.raises(_lib.DvqError, match="dvq_ret"):
+        _lib._parse_header(ok + "DVQ_API unsigned dvq_ret(int n);\n")
+    with pytest.raises(_lib.DvqError, match="dvq_callback"):
+        _lib._parse_header(ok + "DVQ_API int dvq_callback(void (*fn)(int), int n);\n")
+    with pytest.raises(_lib.DvqError, match="dvq_unfinished"):
+        _lib._parse_header(ok + "DVQ_API int dvq_unfinished(int n)\n")
+
+
+def test_checked_calls_raise_on_their_own():
+    from dynamicvectorquantization_amd import _lib
+    L, C = _lib.lib, _lib.checked
+    with pytest.raises(_lib.DvqError) as e:
+        C.dvq_vq_assign_nchw_f32(0, 0, 0, 0, 1, 256, 1, 1, 0.25, 0, 0, 0, 0, 0, 0, 0)
+    assert "dvq_vq_assign_nchw_f32 failed (rc=-1)" in str(e.value) and "null" in str(e.value)
+    assert L.dvq_vq_assign_nchw_f32(0, 0, 0, 0, 1, 256, 1, 1, 0.25, 0, 0, 0, 0, 0, 0, 0) == -1     # the raw one still returns
+    assert C.dvq_embed_gather_f32(1, 4, 8, 1, 0, 1, 0) == 0                                          # n = 0: no launch
+    assert C.dvq_codebook_prep_bytes(1024, 256) == L.dvq_codebook_prep_bytes(1024, 256)
+    assert C.dvq_vq_assign_narrow_tile_codes(4) == L.dvq_vq_assign_narrow_tile_codes(4) > 0          # an int that is no status
+    assert C.dvq_version() == L.dvq_version()
+    for name in _lib.EXPORTS:
+        assert getattr(C, name) is not getattr(L, name), name
+        assert getattr(L, name).errcheck is not _lib._raise_on_error, name
+
+
+def test_workspace_stays_dirty_when_the_call_raises():
+    """checked.fn(..., *ws.begin(mode), ...); ws.end(mode): a call that raises skips `end` (the success half, clean after `end`,
+    is tests/test_workspace_selfclean.py's, on the GPU)"""
+    from dynamicvectorquantization_amd import _lib
+    from dynamicvectorquantization_amd.quantize import _Workspace
+    ws = _Workspace(1024, torch.device("cpu"))
+    ws.clean = True
+    with pytest.raises(_lib.DvqError, match="null"):
+        _lib.checked.dvq_vq_assign_nchw_f32(0, 0, 0, 0, 1, 256, 1, 1, 0.25, 0, 0, 0, *ws.begin(_lib.MODE_FILTER), 0)
+        ws.end(_lib.MODE_FILTER)
+    assert ws.clean is False
+
+
+def test_constants_match_the_header():
+    """every `#define DVQ_<NAME> <integer>` of include/dvq.h that _lib restates (as <NAME>, or DVQ_<NAME> for DVQ_OK) has the
+    header's value"""
+    from dynamicvectorquantization_amd import _lib
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dvq.h")).read(), flags=re.S)
+    defines = {n: int(v, 0) for n, v in re.findall(r"^[ \t]*#[ \t]*define[ \t]+DVQ_(\w+)[ \t]+\(?(-?(?:0x[0-9A-Fa-f]+|\d+))\)?[ \t]*$", src, flags=re.M)}
+    assert len(defines) == 28 and defines["EINVAL"] == -1 and defines["MODE_WS_CLEAN"] == 0x100
+    hit = []
+    for name, value in defines.items():
+        for attr in (name, "DVQ_" + name):
+            if hasattr(_lib, attr):
+                assert getattr(_lib, attr) == value, (attr, getattr(_lib, attr), value)
+                hit.append(attr)
+    assert len(hit) >= 23, hit
+    for attr in ("DVQ_OK", "MODE_EXACT", "MODE_FILTER", "MODE_FILTER_PASS1", "MODE_FILTER_WIDE", "MODE_WS_CLEAN", "GATE_F32", "GATE_I64",
+                 "GATE_ENTROPY", "ACT_NONE", "ACT_SILU", "ACT_RELU", "RQ_MAX_DEPTH", "RQ_EMBED_SUM", "RQ_EMBED_SELECT", "RQ_EMBED_EACH",
+                 "TRANSFER_SAMPLED", "TRANSFER_REMAIN", "TRANSFER_SOS_NONE", "TRANSFER_SOS_CONST", "TRANSFER_SOS_COPY", "METRIC_L2",
+                 "METRIC_DOT"):
+        assert attr in hit, attr
+
+
 def test_cpu_tensors_fail_loudly():
     """the product path has no CPU fallback: CPU tensors raise instead of silently computing"""
     from dynamicvectorquantization_amd import _lib
