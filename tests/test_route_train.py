@@ -17,82 +17,17 @@ from dynamicvectorquantization_amd import _lib
 from dynamicvectorquantization_amd.router import (DualGrainFeatureRouter, DualGrainFixedEntropyRouter,
                                                   TripleGrainFeatureRouter, route_select_dual_entropy, route_train_dual,
                                                   route_train_triple)
+from tests._route_train_ref import branches as _branches
+from tests._route_train_ref import check_gate as _check_gate
+from tests._route_train_ref import check_h as _check_h
+from tests._route_train_ref import make_router as _make_router
+from tests._route_train_ref import margin as _margin
+from tests._route_train_ref import nudge as _nudge
+from tests._route_train_ref import torch_tail as _torch_tail
 
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def _torch_tail(router, branches, gumbels, nb, update_router=True, tau=1.0):
-    """the reference's training tail (EncoderDual.py:131-156 / EncoderTriple.py:145-183) as torch ops, F.gumbel_softmax's
-    arithmetic with explicit noise"""
-    if nb == 2:
-        h_coarse, h_fine = branches
-        gate = router(h_fine=h_fine, h_coarse=h_coarse)
-    else:
-        h_coarse, h_median, h_fine = branches
-        gate = router(h_fine=h_fine, h_median=h_median, h_coarse=h_coarse)
-    scaled = update_router
-    if update_router:
-        y_soft = ((gate + gumbels) / tau).softmax(-1)
-        index = y_soft.max(-1, keepdim=True)[1]
-        y_hard = torch.zeros_like(gate).scatter_(-1, index, 1.0)
-        gate = y_hard - y_soft.detach() + y_soft
-    gate = gate.permute(0, 3, 1, 2)
-    indices = gate.argmax(dim=1)
-    S = 2 if nb == 2 else 4
-    rep = lambda t, s: t.repeat_interleave(s, dim=-1).repeat_interleave(s, dim=-2)
-    ir = rep(indices, S).unsqueeze(1)
-    if nb == 2:
-        h = torch.where(ir == 0, rep(h_coarse, 2), h_fine)
-        masks = (0.25, 1.0)
-    else:
-        hm = rep(h_median, 2)
-        h = torch.where(ir == 0, rep(h_coarse, 4), hm)
-        h = torch.where(ir == 1, hm, h)
-        h = torch.where(ir == 2, h_fine, h)
-        masks = (0.0625, 0.25, 1.0)
-    if scaled:
-        h = h * rep(gate.max(dim=1, keepdim=True)[0], S)
-    cmask = torch.full_like(ir, masks[-1], dtype=torch.float32)
-    for i, m in enumerate(masks[:-1]):
-        cmask = torch.where(ir == i, torch.full_like(cmask, m), cmask)
-    return {"h": h, "indices": indices, "codebook_mask": cmask, "gate": gate}
-
-
-def _branches(nb, B, C, hc, wc, dev, seed):
-    g = torch.Generator(device="cpu").manual_seed(seed)
-    out = []
-    for i in range(nb):
-        s = (1 << i) if nb == 3 else 1 + i
-        out.append((torch.randn((B, C, hc * s, wc * s), generator=g) * (0.5 + i) + 0.1 * i).to(dev).requires_grad_(True))
-    return out
-
-
-def _make_router(nb, C, norm, gate_type, dev, seed):
-    torch.manual_seed(seed)
-    cls = DualGrainFeatureRouter if nb == 2 else TripleGrainFeatureRouter
-    r = cls(C, normalization_type=norm, gate_type=gate_type).to(dev)
-    with torch.no_grad():
-        for n, p in r.named_parameters():
-            if "feature_norm" in n:           # non-trivial GroupNorm affines
-                p.add_(0.2 * torch.randn_like(p))
-    return r
-
-
-def _margin(z):
-    top = z.topk(2, dim=-1).values
-    return top[..., 0] - top[..., 1]
-
-
-def _nudge(logits, gumbels, thr=1e-3):
-    """raise the winner's noise where the perturbed top-2 margin is below thr (decisions then identical at fp32 noise)"""
-    z = logits + gumbels
-    small = _margin(z) < thr
-    bump = torch.zeros_like(gumbels).scatter_(-1, z.argmax(-1, keepdim=True), 2 * thr)
-    g = torch.where(small.unsqueeze(-1), gumbels + bump, gumbels)
-    assert float(_margin(logits + g).min()) >= thr
-    return g
 
 
 def _close_grad(a, b, what):
@@ -100,22 +35,6 @@ def _close_grad(a, b, what):
     tol = 1e-4 * float(ref.abs().max()) + 1e-30
     err = float((a.detach().double() - ref).abs().max())
     assert err <= tol, "%s: max err %g > %g" % (what, err, tol)
-
-
-def _check_gate(gate, ref_gate, hard):
-    if hard:
-        off = ref_gate == 0
-        assert torch.equal(gate == 0, off), "gate zero pattern"
-        on = ~off
-        a, b = gate[on], ref_gate[on]
-        ulp = torch.abs(torch.nextafter(b, torch.full_like(b, 2.0)) - b)
-        assert bool(((a - b).abs() <= 2 * ulp).all()), "gate on the hard index beyond 2 ulp"
-    else:
-        assert bool(((gate - ref_gate).abs() <= 1e-5 * ref_gate.abs().max()).all()), "logits"
-
-
-def _check_h(h, ref):
-    assert bool(((h - ref).abs() <= 1e-6 * ref.abs() + 1e-30).all()), "h_out beyond 1e-6 relative"
 
 
 def _run_pair(nb, norm, gate_type, B=30, C=256, hc=None, update_router=True, seed=0):
