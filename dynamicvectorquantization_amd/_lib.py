@@ -43,6 +43,8 @@ SAMPLE_MAX_V = 8192     # the sampling head's vocabulary limit (include/dvq.h: d
 TRANSFER_SAMPLED, TRANSFER_REMAIN = 0, 1
 TRANSFER_SOS_NONE, TRANSFER_SOS_CONST, TRANSFER_SOS_COPY = 0, 1, 2
 METRIC_L2, METRIC_DOT = 0, 1   # dvq_vq_score_assign_f32: s = -distance / s = dot product
+DTYPE_F16, DTYPE_BF16 = 1, 2   # DVQ_DTYPE_*: the 16-bit latents of the *_x16 entry points
+X16 = {torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
 
 
 class DvqError(RuntimeError):
@@ -185,6 +187,22 @@ def require_cuda_f32(t, name):
     if t.dtype != torch.float32:
         raise TypeError("%s must be float32, got %s" % (name, t.dtype))
     return t if t.is_contiguous() else t.contiguous()
+
+
+def require_cuda_latents(t, name):
+    """require_cuda_f32 for LATENTS: float32, or float16 / bfloat16 (the *_x16 entry points of the dense assign, its backward
+    and the EMA statistics); everything that is not a latent-shaped tensor stays with require_cuda_f32"""
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in X16:
+        return t if t.is_contiguous() else t.contiguous()
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype != torch.float32:
+        raise TypeError("%s must be float32, float16 or bfloat16, got %s" % (name, t.dtype))
+    return require_cuda_f32(t, name)
+
+
+def refuse_x16(t, name):
+    """the ops that stay float32-only raise for 16-bit latents exactly what require_cuda_f32 raises (vq_assign itself takes them)"""
+    if isinstance(t, torch.Tensor) and t.dtype in X16:
+        raise TypeError("%s must be float32, got %s" % (name, t.dtype))
 
 
 def ptr(t):

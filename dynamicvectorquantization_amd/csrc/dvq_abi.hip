@@ -7,7 +7,7 @@
 #include "../../include/dvq.h"
 #include "dvq_filter.h"
 
-#define DVQ_VERSION 1600   // 0.16.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1700   // 0.17.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -25,11 +25,11 @@ int dvq_launch_prep_f32(const float *E, int K, int D, void *prep, hipStream_t st
 int dvq_launch_prep_f16(const float *E, int K, int D, void *prep, hipStream_t st);
 int dvq_launch_exact(const float *z, const float *prep, const float *E, const float *mask,
                      int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
-                     const DvqRouted *rv, hipStream_t st);
+                     const DvqRouted *rv, hipStream_t st, int xt = 0);
 int dvq_launch_filter(const float *z, const void *prep, const float *E, const float *mask,
                       int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
                       void *ws_extra, bool pass1_only, bool force_wide, float *loss, float beta,
-                      const DvqRouted *rv, hipStream_t st, const DvqConv *cv, const DvqFold *fd, bool ws_clean);
+                      const DvqRouted *rv, hipStream_t st, const DvqConv *cv, const DvqFold *fd, bool ws_clean, int xt = 0);
 int dvq_launch_routed(int G, int gate_mode, const void *gate, float thr, const float *h_coarse,
                       const float *h_median, const float *h_fine, const void *prep, const float *E,
                       int B, int D, int hc, int wc, int K, float beta, float *zq, long long *codes,
@@ -50,6 +50,10 @@ int dvq_launch_route_select(int G, int gate_mode, const void *gate, const float 
 int dvq_launch_entropy_gate(const float *ent, long n, float thr, long long *gate, hipStream_t st);
 int dvq_launch_vq_backward_z(const float *z, const float *E, const long long *codes, const float *mask, const float *g_zq,
                              const float *g_loss, float coef_scale, int D, int HW, int K, long N, float *gz, hipStream_t st);
+int dvq_launch_vq_backward_z_x16(const void *z, int xt, const float *E, const long long *codes, const float *mask, const void *g_zq,
+                                 const float *g_loss, float coef_scale, int D, int HW, int K, long N, void *gz, hipStream_t st);
+int dvq_launch_ema_accumulate_x16(const void *z, int xt, const long long *codes, int D, int HW, long N, int K,
+                                  float *cluster_size, float *vectors_sum, hipStream_t st);
 int dvq_launch_codebook_grad(const float *z, const float *E, const long long *codes, const float *mask, const float *g_loss,
                              float coef_scale, int D, int HW, long N, int K, float *gw, hipStream_t st);
 int dvq_launch_embed_gather(const float *E, int K, int D, const long long *idx, long n, float *out,
@@ -253,6 +257,47 @@ int dvq_vq_assign_nchw_f32(const float *z, const float *codebook, const void *pr
     }
     if (loss) {
         rc = dvq_launch_loss_finalize(partials, nparts, 1.0 / ((double)N * D), beta, loss, st);
+        if (rc) return hip_rc(rc, "vq_loss_finalize");
+    }
+    return DVQ_OK;
+}
+
+// 16-bit latents (dtype: DVQ_DTYPE_F16 / DVQ_DTYPE_BF16): the same chain of kernels, z read and zq written as that type
+int dvq_vq_assign_nchw_x16(const void *z, int dtype, const float *codebook, const void *prep, const float *mask,
+                           int B, int D, int HW, int K, float beta, void *zq, int64_t *codes, float *loss,
+                           void *ws, size_t ws_bytes, int mode, void *stream)
+{
+    const char *fn = "dvq_vq_assign_nchw_x16";
+    if (dtype != DVQ_DTYPE_F16 && dtype != DVQ_DTYPE_BF16) { dvq_set_error("%s: dtype %d (DVQ_DTYPE_F16 = 1, DVQ_DTYPE_BF16 = 2)", fn, dtype); return DVQ_EINVAL; }
+    if (!z || !codebook || !prep || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if ((((uintptr_t)z | (uintptr_t)zq) & 1) != 0) { dvq_set_error("%s: z and zq must be 2-byte aligned", fn); return DVQ_EINVAL; }
+    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
+    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; the narrow widths 3, 4, 8, 16 take float32 latents only: dvq_vq_assign_narrow_*_f32)", fn, D); return DVQ_EUNSUPPORTED; }
+    const bool ws_clean = (mode & DVQ_MODE_WS_CLEAN) != 0;
+    mode &= ~DVQ_MODE_WS_CLEAN;
+    if (mode == DVQ_MODE_FILTER_PASS1 || mode == DVQ_MODE_FILTER_WIDE) { dvq_set_error("%s: mode %d (pass 1 alone / the wide form) exists for float32 latents only", fn, mode); return DVQ_EUNSUPPORTED; }
+    if (mode != DVQ_MODE_EXACT && mode != DVQ_MODE_FILTER) { dvq_set_error("%s: unknown mode %d", fn, mode); return DVQ_EINVAL; }
+    if ((size_t)B * HW * D >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    const long N = (long)B * HW;
+    if (loss && !ws) { dvq_set_error("%s: loss requested without workspace", fn); return DVQ_EINVAL; }
+    if ((loss || mode == DVQ_MODE_FILTER) && (!ws || ws_bytes < dvq_vq_assign_workspace_bytes(B, D, HW, K, mode))) {
+        dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, dvq_vq_assign_workspace_bytes(B, D, HW, K, mode));
+        return DVQ_EWORKSPACE;
+    }
+    if (ws && ((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    hipStream_t st = (hipStream_t)stream;
+    double *partials = loss ? (double *)ws : nullptr;
+    if (mode == DVQ_MODE_FILTER && dvq_filter_supported(D, HW, K, N)) {
+        const int rc = dvq_launch_filter((const float *)z, prep, codebook, mask, D, HW, K, N, (float *)zq, (long long *)codes, partials,
+                                         (char *)ws + partials_bytes_for(N), false, false, loss, beta, nullptr, st, nullptr, nullptr,
+                                         ws_clean, dtype);
+        return hip_rc(rc, "vq_assign_filter_x16");
+    }
+    int rc = dvq_launch_exact((const float *)z, (const float *)prep, codebook, mask, D, HW, K, N, (float *)zq, (long long *)codes, partials,
+                              nullptr, st, dtype);
+    if (rc) return hip_rc(rc, "vq_assign_exact_x16");
+    if (loss) {
+        rc = dvq_launch_loss_finalize(partials, (int)((N + 127) / 128), 1.0 / ((double)N * D), beta, loss, st);
         if (rc) return hip_rc(rc, "vq_loss_finalize");
     }
     return DVQ_OK;
@@ -545,6 +590,22 @@ int dvq_vq_backward_nchw_f32(const float *z, const float *codebook, const int64_
                                            (long)B * HW, g_z, (hipStream_t)stream), fn);
 }
 
+int dvq_vq_backward_nchw_x16(const void *z, int dtype, const float *codebook, const int64_t *codes, const float *mask,
+                             const void *g_zq, const float *g_loss, float coef_scale, int B, int D, int HW, int K,
+                             void *g_z, void *stream)
+{
+    const char *fn = "dvq_vq_backward_nchw_x16";
+    if (dtype != DVQ_DTYPE_F16 && dtype != DVQ_DTYPE_BF16) { dvq_set_error("%s: dtype %d (DVQ_DTYPE_F16 = 1, DVQ_DTYPE_BF16 = 2)", fn, dtype); return DVQ_EINVAL; }
+    if (!z || !codebook || !codes || !g_z) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!g_zq && !g_loss) { dvq_set_error("%s: neither g_zq nor g_loss given", fn); return DVQ_EINVAL; }
+    if (B <= 0 || HW <= 0 || K <= 0 || D <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
+    if (D % 16 != 0) { dvq_set_error("%s: D=%d must be a multiple of 16", fn, D); return DVQ_EUNSUPPORTED; }
+    if ((((uintptr_t)codebook) & 15) != 0) { dvq_set_error("%s: codebook must be 16-byte aligned", fn); return DVQ_EINVAL; }
+    if ((((uintptr_t)z | (uintptr_t)g_zq | (uintptr_t)g_z) & 1) != 0) { dvq_set_error("%s: z, g_zq and g_z must be 2-byte aligned", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_vq_backward_z_x16(z, dtype, codebook, (const long long *)codes, mask, g_zq, g_loss, coef_scale, D, HW, K,
+                                               (long)B * HW, g_z, (hipStream_t)stream), fn);
+}
+
 int dvq_vq_backward_codebook_nchw_f32(const float *z, const float *codebook, const int64_t *codes, const float *mask,
                                       const float *g_loss, float coef_scale, int B, int D, int HW, int K,
                                       float *g_weight, void *stream)
@@ -624,6 +685,18 @@ int dvq_ema_accumulate_nchw_f32(const float *z, const int64_t *codes, int B, int
     if (B <= 0 || D <= 0 || HW <= 0 || K <= 0) { dvq_set_error("dvq_ema_accumulate_nchw_f32: sizes must be positive"); return DVQ_EINVAL; }
     return hip_rc(dvq_launch_ema_accumulate(z, (const long long *)codes, D, HW, (long)B * HW, K, cluster_size, vectors_sum,
                                             (hipStream_t)stream), "ema_accumulate");
+}
+
+int dvq_ema_accumulate_nchw_x16(const void *z, int dtype, const int64_t *codes, int B, int D, int HW, int K,
+                                float *cluster_size, float *vectors_sum, void *stream)
+{
+    const char *fn = "dvq_ema_accumulate_nchw_x16";
+    if (dtype != DVQ_DTYPE_F16 && dtype != DVQ_DTYPE_BF16) { dvq_set_error("%s: dtype %d (DVQ_DTYPE_F16 = 1, DVQ_DTYPE_BF16 = 2)", fn, dtype); return DVQ_EINVAL; }
+    if (!z || !codes || !cluster_size || !vectors_sum) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (((uintptr_t)z & 1) != 0) { dvq_set_error("%s: z must be 2-byte aligned", fn); return DVQ_EINVAL; }
+    if (B <= 0 || D <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_ema_accumulate_x16(z, dtype, (const long long *)codes, D, HW, (long)B * HW, K, cluster_size, vectors_sum,
+                                                (hipStream_t)stream), fn);
 }
 
 int dvq_code_stats_f32(const int64_t *codes, int64_t N, int K, int64_t *counts, int64_t *n_used, float *perplexity, float *onehot,

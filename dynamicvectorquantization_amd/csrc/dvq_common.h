@@ -13,6 +13,29 @@ typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 #define DVQ_CODE_TILE 32  // codes per MFMA tile (rows of a 32x32 MFMA)
 
 // ---------------------------------------------------------------------------------------------
+// 16-bit latents (the *_x16 entry points of dvq.h; XT = DVQ_DTYPE_F16 / DVQ_DTYPE_BF16, 0 = float32).  Only the storage type of
+// latent-shaped tensors (z, z_q, g_zq, g_z) changes: a value is widened to fp32 where it enters registers (exact: f16 -> f32 is
+// the hardware convert, subnormals included; bf16 -> f32 a 16-bit shift) and narrowed once, round-to-nearest-even, where it
+// leaves them (f32 -> f16: v_cvt_f16_f32, overflow -> inf; f32 -> bf16: gfx950's v_cvt_pk_bf16_f32; NaN stays NaN) -- the
+// bits of torch's `.float()` and `.to(dtype)`.  All arithmetic in between is the fp32 op's.
+// ---------------------------------------------------------------------------------------------
+template <int XT> struct DvqLat { typedef float T; };
+template <> struct DvqLat<1> { typedef _Float16 T; };
+template <> struct DvqLat<2> { typedef __bf16 T; };
+template <int XT> __device__ __forceinline__ float dvq_widen(typename DvqLat<XT>::T v) { return (float)v; }
+template <int XT> __device__ __forceinline__ typename DvqLat<XT>::T dvq_narrow(float v) { return (typename DvqLat<XT>::T)v; }
+// the same on the raw 16 bits a buffer instruction moves (zero-extended in / low half out)
+template <int XT> __device__ __forceinline__ float dvq_widen_bits(unsigned short u)
+{
+    if constexpr (XT == 2) return __builtin_bit_cast(float, (unsigned)u << 16);
+    else return (float)__builtin_bit_cast(_Float16, u);
+}
+template <int XT> __device__ __forceinline__ unsigned short dvq_narrow_bits(float v)
+{
+    return __builtin_bit_cast(unsigned short, dvq_narrow<XT>(v));
+}
+
+// ---------------------------------------------------------------------------------------------
 // Prep buffer (built once per codebook by dvq_codebook_prepare_f32), all offsets in bytes,
 // T = ceil(K/32) code tiles:
 //   [f32 tile images]  T x (32*D + 64) floats.  Image of tile t:

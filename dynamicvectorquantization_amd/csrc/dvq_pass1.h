@@ -14,6 +14,10 @@
 // the same through buffer instructions (resource = wave-uniform base, vector byte offset, scalar byte offset; aux 2 = nt)
 #define DVQ_BUF_LOAD(rsrc, voff, soff, AUX) __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32((rsrc), (voff), (soff), (AUX)))
 #define DVQ_BUF_STORE(v, rsrc, voff, soff) __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)(v)), (rsrc), (voff), (soff), 2)
+// 16-bit latents (XT = DVQ_DTYPE_F16 / DVQ_DTYPE_BF16, dvq_common.h): 2-byte buffer accesses, widened behind the load and narrowed
+// (round-to-nearest-even) in front of the store -- the registers in between are the fp32 kernel's
+#define DVQ_BUF_LOAD16(XT, rsrc, voff, soff, AUX) dvq_widen_bits<XT>(__builtin_amdgcn_raw_buffer_load_b16((rsrc), (voff), (soff), (AUX)))
+#define DVQ_BUF_STORE16(XT, v, rsrc, voff, soff) __builtin_amdgcn_raw_buffer_store_b16(dvq_narrow_bits<XT>(v), (rsrc), (voff), (soff), 2)
 // the per-lane select prologue (SEL = 1) reads lines of the coarser branches that neighbouring waves read again:
 // plain loads keep them in L2
 #define DVQ_LOAD_SEL(p) (*(p))
@@ -99,7 +103,10 @@ static inline int dvq_tuning_set_unit(void *stamps, void *tokdbg)
 #define DVQ_SEED_TABLE_TILES 32   // code tiles whose seeds fit the seeds area as one table ([32 tiles][32] floats = its 4 KiB)
 constexpr size_t dvq_pass1_lds_bytes(int D) { return 4 * (size_t)(D / 16) * 1024 + 4 * 4 * 64 * sizeof(float) + 4 * 2048; }
 
-template <int D, int SEL, bool CONV, bool FOLD, bool NT, bool RES, bool FLAT = false, bool SPLIT = false>
+// XT != 0: z and zq hold 16-bit latents (passed through the float pointers; only their bytes are addressed).  The dense lane-per-token
+// form alone has it (any HW; HW == 1 is the row-major tensor): the latents are widened where the loads land and z_q is narrowed
+// at the stores, everything between -- fragments, bound, records, loss term -- is the fp32 kernel's on the widened values.
+template <int D, int SEL, bool CONV, bool FOLD, bool NT, bool RES, bool FLAT = false, bool SPLIT = false, int XT = 0>
 __device__ __forceinline__ void pass1_body(
     const float *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
     const float *__restrict__ E, const float *__restrict__ mask,
@@ -113,6 +120,8 @@ __device__ __forceinline__ void pass1_body(
     static_assert(!CONV || (D == 256 && SEL != 2), "the conv prologue exists for D = 256, dense or per-lane select");
     static_assert(!(CONV && FOLD), "the conv is either computed (CONV) or folded into the code image (FOLD)");
     static_assert(!FLAT || (SEL == 0 && !CONV), "the row-major form is a dense op");
+    static_assert(XT == 0 || (SEL == 0 && !CONV && !FOLD && !FLAT && !SPLIT), "16-bit latents: the dense lane-per-token form only");
+    constexpr int ZB = XT ? 2 : 4;                           // bytes per latent in memory
     constexpr int NW = 4;
     constexpr int S16 = D / 16;
     constexpr int S32 = S16 / 2;
@@ -212,13 +221,14 @@ __device__ __forceinline__ void pass1_body(
         const size_t tb = token_base(hw, hh);
         const size_t tb0 = ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tb >> 32)) << 32) |
                            (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tb & 0xFFFFFFFFu));
-        return __builtin_amdgcn_make_buffer_rsrc((void *)(p0 + tb0), 0, -1, 0x00020000);
+        if constexpr (XT != 0) return __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p0 + tb0 * ZB), 0, -1, 0x00020000);
+        else return __builtin_amdgcn_make_buffer_rsrc((void *)(p0 + tb0), 0, -1, 0x00020000);
     };
     auto lane_off = [&](int hw, int hh) -> unsigned {        // byte offset of this lane's token_base() from lane 0's
         const size_t tb = token_base(hw, hh);
         const size_t tb0 = ((size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tb >> 32)) << 32) |
                            (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(tb & 0xFFFFFFFFu));
-        return (unsigned)(tb - tb0) * 4u;
+        return (unsigned)(tb - tb0) * (XT ? 2u : 4u);
     };
     float zf[S16][8];
     float sel_mask = 1.0f;                                   // SEL: the codebook_mask value of this lane's cell (1 / rep^2), NEGATED for
@@ -512,7 +522,10 @@ __device__ __forceinline__ void pass1_body(
 #pragma unroll
         for (int s = 0; s < S16; ++s)
 #pragma unroll
-            for (int j = 0; j < 8; ++j) zf[s][j] = DVQ_BUF_LOAD(zr, zo, (16 * s + j) * HW * 4, NT ? 2 : 0);
+            for (int j = 0; j < 8; ++j) {
+                if constexpr (XT != 0) zf[s][j] = DVQ_BUF_LOAD16(XT, zr, zo, (16 * s + j) * HW * 2, NT ? 2 : 0);
+                else zf[s][j] = DVQ_BUF_LOAD(zr, zo, (16 * s + j) * HW * 4, NT ? 2 : 0);
+            }
         __builtin_amdgcn_s_setprio(0);
     }
     f16x8 zb[2][S32];                                        // B operands of the 16x16x32 loop, [token half][k-step of 32]
@@ -821,7 +834,7 @@ __device__ __forceinline__ void pass1_body(
                 asm volatile("" : "+s"(hw_e));               // by HW, once) instead of keeping the prologue's reciprocal of HW in a
                 const __amdgpu_buffer_rsrc_t qr = wave_base(STORE ? zq : (float *)E, hw_e, h_e);       // VGPR through the code loop
                 const unsigned qo = lane_off(hw_e, h_e);
-                int hw4 = HW * 4;                            // opaque: the 128 scalar offsets are recomputed here (two scalar
+                int hw4 = HW * (XT ? 2 : 4);                 // opaque: the 128 scalar offsets are recomputed here (two scalar
                 asm volatile("" : "+s"(hw4));                // instructions each) instead of living in spilled SGPRs since the prologue
 #pragma unroll
                 for (int s0 = 0; s0 < S16; s0 += SB) {
@@ -841,6 +854,9 @@ __device__ __forceinline__ void pass1_body(
                                 if (STORE) DVQ_BUF_STORE(e, qr, qo, (16 * s + j) * hw4);   // fl(h + fl(e - h))), no loss term
                             } else {
                             float diff = __fsub_rn(e, zf[s][j]);
+                            if constexpr (XT != 0) {
+                                if (STORE) DVQ_BUF_STORE16(XT, __fadd_rn(zf[s][j], diff), qr, qo, (16 * s + j) * hw4);
+                            } else
                             if (STORE) DVQ_BUF_STORE(__fadd_rn(zf[s][j], diff), qr, qo, (16 * s + j) * hw4);
                             lsum = __builtin_fmaf(diff, diff, lsum);   // the token's loss weight is applied once, below
                             }
@@ -1012,6 +1028,20 @@ __global__ __launch_bounds__(256, 2) void vq_assign_filter_cached_kernel(
     pass1_body<D, SEL, false, FOLD, false, RES>(z, img, meta, E, mask, HW, K, N, zq, codes, partials, counters, exact_list, records, rec_cap, rv, cv);
 }
 
+// 16-bit latents (XT: dvq_common.h), dense, any HW: the plain form's kernel on 2-byte loads and stores
+template <int D, bool RES, int XT>
+__global__ __launch_bounds__(256, 2) void vq_assign_filter_x16_kernel(
+    const void *__restrict__ z, const char *__restrict__ img, const DvqF16Meta *__restrict__ meta,
+    const float *__restrict__ E, const float *__restrict__ mask,
+    int HW, int K, long N, void *__restrict__ zq, long long *__restrict__ codes,
+    double *__restrict__ partials, int *__restrict__ counters, int *__restrict__ exact_list,
+    char *__restrict__ records, int rec_cap)
+{
+    static_assert(XT == 1 || XT == 2, "f16 or bf16");
+    pass1_body<D, 0, false, false, true, RES, false, false, XT>((const float *)z, img, meta, E, mask, HW, K, N, (float *)zq, codes, partials,
+                                                                counters, exact_list, records, rec_cap, DvqRouted{}, DvqConv{});
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side: the workspace carve, the plan and the arguments of one launch (made by vq_assign_filter.hip)
 // ---------------------------------------------------------------------------------------------
@@ -1023,12 +1053,13 @@ struct FilterWs {
 };
 
 // The forms of pass 1 (one kernel family each) and the plan of one launch
-enum class P1Form { plain, cached, flat, split, wide };
+enum class P1Form { plain, cached, flat, split, wide, x16 };
 struct P1Plan {
     P1Form form;
     int sel;                                                 // pass1_body's SEL
     bool conv, fold, flat;                                   // ... CONV, FOLD and FLAT
     int ks;                                                  // the split form's workgroups per token block
+    int xt;                                                  // form x16: the latents' type (DVQ_DTYPE_F16 / DVQ_DTYPE_BF16); else 0
 };
 
 // two row-major forms at D = 256 keep the per-tile seed piece at every K: with the table their register allocation spills
@@ -1082,6 +1113,7 @@ static int launch_pass1_form(const P1Plan &p, const P1Args &a)
                                                                                          DVQ_P1_ARGS, a.rv, a.cv, a.w.split, p.ks);
         break;
     case P1Form::wide:
+    case P1Form::x16:                                        // launch_pass1_x16, below
         break;
     }
 #undef DVQ_P1_ARGS
@@ -1106,6 +1138,24 @@ static int launch_pass1_res(const P1Plan &p, const P1Args &a)
     }
 }
 
+// the 16-bit form: one unit per (D, RES) as well (vq_pass1_x16_d<D>[_res].hip), both types in it
+template <int D, bool RES>
+static int launch_pass1_x16(const P1Plan &p, const P1Args &a)
+{
+    const unsigned nb = (unsigned)((a.N + 127) / 128);
+    const size_t lds = dvq_pass1_lds_bytes(D);
+    if (p.form != P1Form::x16) return -1000;
+    if (p.xt == 1)
+        return dvq_launch_lds<vq_assign_filter_x16_kernel<D, RES, 1>>(dim3(nb), dim3(256), lds, a.st, (const void *)a.z, a.img16, a.meta, a.E,
+                                                                      a.mask, a.HW, a.K, a.N, (void *)a.zq, a.codes, a.partials,
+                                                                      a.w.counters, a.w.exact_list, a.w.records, a.w.cap / DVQ_QSHARDS);
+    if (p.xt == 2)
+        return dvq_launch_lds<vq_assign_filter_x16_kernel<D, RES, 2>>(dim3(nb), dim3(256), lds, a.st, (const void *)a.z, a.img16, a.meta, a.E,
+                                                                      a.mask, a.HW, a.K, a.N, (void *)a.zq, a.codes, a.partials,
+                                                                      a.w.counters, a.w.exact_list, a.w.records, a.w.cap / DVQ_QSHARDS);
+    return -1000;
+}
+
 // the six pass-1 units (vq_pass1_d<D>[_res].hip), the wide form (vq_pass1_wide.hip; D = 256) and the resolver (vq_resolve.hip)
 int dvq_launch_pass1_d64(const P1Plan &p, const P1Args &a);
 int dvq_launch_pass1_d64_res(const P1Plan &p, const P1Args &a);
@@ -1114,11 +1164,18 @@ int dvq_launch_pass1_d128_res(const P1Plan &p, const P1Args &a);
 int dvq_launch_pass1_d256(const P1Plan &p, const P1Args &a);
 int dvq_launch_pass1_d256_res(const P1Plan &p, const P1Args &a);
 int dvq_launch_pass1_wide(const P1Args &a);
+int dvq_launch_pass1_x16_d64(const P1Plan &p, const P1Args &a);
+int dvq_launch_pass1_x16_d64_res(const P1Plan &p, const P1Args &a);
+int dvq_launch_pass1_x16_d128(const P1Plan &p, const P1Args &a);
+int dvq_launch_pass1_x16_d128_res(const P1Plan &p, const P1Args &a);
+int dvq_launch_pass1_x16_d256(const P1Plan &p, const P1Args &a);
+int dvq_launch_pass1_x16_d256_res(const P1Plan &p, const P1Args &a);
 int dvq_resolver_slices(int K);
+// xt != 0: zq holds 16-bit latents of that type (dense op only)
 int dvq_launch_resolver(int D, const char *img, const DvqF16Meta *meta, const float *en_all, const float *E,
                         int HWout, int K, float *zq, long long *codes, double *partials,
                         const FilterWs &w, int Wout, float *h_spill, const DvqFold *fd, hipStream_t st,
-                        const double *p1_partials, int np1);
+                        const double *p1_partials, int np1, int xt = 0);
 #ifdef DVQ_TUNING
 int dvq_tuning_set_pass1_d64(void *stamps, void *tokdbg);
 int dvq_tuning_set_pass1_d64_res(void *stamps, void *tokdbg);

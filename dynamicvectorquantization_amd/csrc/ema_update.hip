@@ -22,8 +22,11 @@
 // rule, not the exception: the 2 x 2 / 4 x 4 copies of a coarse cell carry one code, and a trained codebook's usage is
 // skewed -- atomics on one address serialise in L2 (10 % of the tokens on one code: 1314 us without, profiles/
 // r02_ema_lds_table_negative_result.txt).  Needs a [K] int table in LDS: K <= 8192 (larger codebooks: plain form).
-template <bool COMBINE>
-__global__ __launch_bounds__(256) void ema_accumulate_kernel(const float *__restrict__ z,
+// XT != 0 (dvq_ema_accumulate_nchw_x16): the latents are fp16 / bf16 (dvq_common.h), widened (exactly) where the tile is loaded;
+// the sums and the counts stay fp32, accumulated as for fp32 latents.  This kernel's loads are per element, so any 2-byte
+// aligned tensor and any HW will do (the sorted-tile kernel below reads 16-byte pieces and stays fp32-only).
+template <bool COMBINE, int XT = 0>
+__global__ __launch_bounds__(256) void ema_accumulate_kernel(const typename DvqLat<XT>::T *__restrict__ z,
                                                              const long long *__restrict__ codes, int D, int HW,
                                                              long N, int K, float *__restrict__ cluster_size,
                                                              float *__restrict__ vectors_sum)
@@ -69,13 +72,13 @@ __global__ __launch_bounds__(256) void ema_accumulate_kernel(const float *__rest
     const long nn = (n < N) ? n : N - 1;
     const long b = nn / HW;
     const int hw = (int)(nn - b * HW);
-    const float *zp = z + (size_t)b * D * HW + hw;
+    const typename DvqLat<XT>::T *zp = z + (size_t)b * D * HW + hw;
     for (int c0 = 0; c0 < D; c0 += 64) {
         __syncthreads();
 #pragma unroll
         for (int i = 0; i < 16; ++i) {             // wave w loads channels c0 + 16w + i: 64 tokens, coalesced
             const int ch = 16 * wave + i;
-            tile[ch][lane] = (c0 + ch < D) ? zp[(size_t)(c0 + ch) * HW] : 0.0f;
+            tile[ch][lane] = (c0 + ch < D) ? dvq_widen<XT>(zp[(size_t)(c0 + ch) * HW]) : 0.0f;
         }
         __syncthreads();
 #pragma unroll 4
@@ -390,6 +393,31 @@ int dvq_launch_ema_accumulate(const float *z, const long long *codes, int D, int
     else
         hipLaunchKernelGGL(ema_accumulate_kernel<false>, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, st, z, codes, D, HW, N, K,
                            cluster_size, vectors_sum);
+    return (int)hipGetLastError();
+}
+
+// 16-bit latents (xt = DVQ_DTYPE_F16 / DVQ_DTYPE_BF16): the tile-transpose kernel, equal codes combined up to K = 8192
+int dvq_launch_ema_accumulate_x16(const void *z, int xt, const long long *codes, int D, int HW, long N, int K,
+                                  float *cluster_size, float *vectors_sum, hipStream_t st)
+{
+    if (xt != 1 && xt != 2) return -1000;
+    {
+        size_t n = (size_t)K * D;
+        int blocks = (int)((n / 4 + 255) / 256);
+        if (blocks > 2048) blocks = 2048;
+        if (blocks < 1) blocks = 1;
+        hipLaunchKernelGGL(ema_zero_kernel, dim3(blocks), dim3(256), 0, st, cluster_size, (size_t)K, vectors_sum, n);
+    }
+    const dim3 grid((unsigned)((N + 63) / 64));
+    const bool combine = K <= 8192;
+    const size_t shm = combine ? (size_t)K * sizeof(int) : 0;
+    if (xt == 1) {
+        auto kernel = combine ? ema_accumulate_kernel<true, 1> : ema_accumulate_kernel<false, 1>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), shm, st, (const _Float16 *)z, codes, D, HW, N, K, cluster_size, vectors_sum);
+    } else {
+        auto kernel = combine ? ema_accumulate_kernel<true, 2> : ema_accumulate_kernel<false, 2>;
+        hipLaunchKernelGGL(kernel, grid, dim3(256), shm, st, (const __bf16 *)z, codes, D, HW, N, K, cluster_size, vectors_sum);
+    }
     return (int)hipGetLastError();
 }
 

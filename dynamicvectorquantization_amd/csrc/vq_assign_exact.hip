@@ -30,7 +30,9 @@
 // from the L2-resident images; bit-identical to dvq_qconv_f32 and to the resolver's h) and moves the accumulators into the
 // (even / odd channel per lane half) layout of zr by one cross-half exchange per register pair.  A rare path: one workgroup
 // per CU (512 registers), no attempt at overlap.
-template <int D, bool LIST, bool ROUTED, bool FOLDCONV = false>
+// XT != 0 (dense op on 16-bit latents, dvq_common.h): z and zq hold that type (behind the float pointers); z is widened where it is
+// read, z_q narrowed at the store, the loss term taken before.
+template <int D, bool LIST, bool ROUTED, bool FOLDCONV = false, int XT = 0>
 __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
     const float *__restrict__ z, const float *__restrict__ tiles, const float *__restrict__ E,
     const float *__restrict__ mask, int HW, int K, long N,
@@ -38,6 +40,8 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
     const int *__restrict__ list, const int *__restrict__ list_count,
     DvqLossTail tail, const DvqRouted rv, const DvqConv cv)
 {
+    static_assert(XT == 0 || (!ROUTED && !FOLDCONV), "16-bit latents: the dense op");
+    typedef typename DvqLat<XT>::T ZT;
     constexpr int S = D / 2;                         // MFMA steps (2 k each)
     constexpr int TILE_FLOATS = 32 * D + 64;
     constexpr int CHUNKS_PER_WAVE = (32 * D * 4 / 1024) / 4;   // 1-KiB DMA pieces per wave per tile
@@ -165,6 +169,10 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
 #pragma unroll
             for (int s = 0; s < S; ++s) hp[(size_t)2 * s * HWo] = zr[s];
         }
+    } else if constexpr (XT != 0) {
+        const ZT *zp16 = (const ZT *)z + zqbase;              // dense: the token's input and output offsets are the same
+#pragma unroll
+        for (int s = 0; s < S; ++s) zr[s] = dvq_widen<XT>(zp16[(size_t)2 * s * HW]);
     } else {
 #pragma unroll
     for (int s = 0; s < S; ++s) zr[s] = zp[(size_t)2 * s * stride];
@@ -277,13 +285,17 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
         // per-lane pointer, it turned every store into its own exec-masked branch)
         auto finish = [&](auto store_tag) {
             constexpr bool STORE = decltype(store_tag)::value;
-            float *zqp = STORE ? zq + zqbase : nullptr;
+            float *zqp = (STORE && XT == 0) ? zq + zqbase : nullptr;
+            ZT *zqp16 = (STORE && XT != 0) ? (ZT *)zq + zqbase : nullptr;
 #pragma unroll
             for (int s = 0; s < S; ++s) {          // fully unrolled: zr[] must stay in registers
                 float e = ep[2 * s];
                 float diff = __fsub_rn(e, zr[s]);
                 if (STORE) {
                     const float v = __fadd_rn(zr[s], diff);
+                    if constexpr (XT != 0) {
+                        zqp16[(size_t)2 * s * HWo] = dvq_narrow<XT>(v);
+                    } else
                     if (!ROUTED) {
                         zqp[(size_t)2 * s * HWo] = v;
                     } else {
@@ -509,10 +521,32 @@ template <int D, bool ROUTED>
 static int launch_exact(const float *z, const float *tiles, const float *E, const float *mask,
                         int HW, int K, long N, float *zq, long long *codes, double *partials,
                         const int *list, const int *list_count, DvqLossTail tail, const DvqRouted &rv,
-                        hipStream_t st, const DvqConv *fold_conv)
+                        hipStream_t st, const DvqConv *fold_conv, int xt)
 {
     const size_t shmem = 2 * (32 * D + 64) * sizeof(float);
     int blocks = (int)((N + 127) / 128);
+    if constexpr (!ROUTED) {
+        if (xt != 0) {                                       // 16-bit latents: the dense op, every token or the list
+            if (fold_conv != nullptr || (xt != 1 && xt != 2)) return -1000;
+            if (list == nullptr) {
+                if (xt == 1)
+                    return dvq_launch_lds<vq_assign_exact_kernel<D, false, false, false, 1>>(dim3(blocks), dim3(256), shmem, st, z, tiles, E, mask,
+                                                                                            HW, K, N, zq, codes, partials, list, list_count,
+                                                                                            tail, rv, DvqConv{});
+                return dvq_launch_lds<vq_assign_exact_kernel<D, false, false, false, 2>>(dim3(blocks), dim3(256), shmem, st, z, tiles, E, mask, HW,
+                                                                                        K, N, zq, codes, partials, list, list_count, tail, rv,
+                                                                                        DvqConv{});
+            }
+            if (blocks > DVQ_EXACT_LIST_BLOCKS) blocks = DVQ_EXACT_LIST_BLOCKS;
+            if (xt == 1)
+                return dvq_launch_lds<vq_assign_exact_kernel<D, true, false, false, 1>>(dim3(blocks), dim3(256), shmem, st, z, tiles, E, mask, HW,
+                                                                                       K, N, zq, codes, partials, list, list_count, tail, rv,
+                                                                                       DvqConv{});
+            return dvq_launch_lds<vq_assign_exact_kernel<D, true, false, false, 2>>(dim3(blocks), dim3(256), shmem, st, z, tiles, E, mask, HW, K,
+                                                                                   N, zq, codes, partials, list, list_count, tail, rv,
+                                                                                   DvqConv{});
+        }
+    } else if (xt != 0) return -1000;
     if (list == nullptr)
         return dvq_launch_lds<vq_assign_exact_kernel<D, false, ROUTED>>(dim3(blocks), dim3(256), shmem, st, z, tiles, E, mask, HW,
                                                                          K, N, zq, codes, partials, list, list_count, tail, rv,
@@ -532,14 +566,14 @@ static const DvqRouted kNoRoute = {};
 int dvq_launch_exact_list(const float *z, const float *prep, const float *E, const float *mask,
                           int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
                           const int *list, const int *list_count, DvqLossTail tail, const DvqRouted *rv,
-                          hipStream_t st, const DvqConv *fold_conv)
+                          hipStream_t st, const DvqConv *fold_conv, int xt)
 {
     const bool routed = rv != nullptr;
     const DvqRouted &r = routed ? *rv : kNoRoute;
     switch (D) {
-    case 64:  return (routed ? launch_exact<64, true> : launch_exact<64, false>)(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, r, st, fold_conv);
-    case 128: return (routed ? launch_exact<128, true> : launch_exact<128, false>)(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, r, st, fold_conv);
-    case 256: return (routed ? launch_exact<256, true> : launch_exact<256, false>)(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, r, st, fold_conv);
+    case 64:  return (routed ? launch_exact<64, true> : launch_exact<64, false>)(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, r, st, fold_conv, xt);
+    case 128: return (routed ? launch_exact<128, true> : launch_exact<128, false>)(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, r, st, fold_conv, xt);
+    case 256: return (routed ? launch_exact<256, true> : launch_exact<256, false>)(z, prep, E, mask, HW, K, N, zq, codes, partials, list, list_count, tail, r, st, fold_conv, xt);
     default:  return -1000;
     }
 }
@@ -548,10 +582,10 @@ int dvq_launch_exact_list(const float *z, const float *prep, const float *E, con
 // token count = B * HWout; ids beyond the last slot are invalid)
 int dvq_launch_exact(const float *z, const float *prep, const float *E, const float *mask,
                      int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
-                     const DvqRouted *rv, hipStream_t st)
+                     const DvqRouted *rv, hipStream_t st, int xt)
 {
     const DvqLossTail none = {nullptr, nullptr, nullptr, 0, 0.0, 0.0f, nullptr, 0};
-    return dvq_launch_exact_list(z, prep, E, mask, D, HW, K, N, zq, codes, partials, nullptr, nullptr, none, rv, st, nullptr);
+    return dvq_launch_exact_list(z, prep, E, mask, D, HW, K, N, zq, codes, partials, nullptr, nullptr, none, rv, st, nullptr, xt);
 }
 
 int dvq_launch_loss_finalize(const double *partials, int nparts, double inv_numel, float beta,

@@ -301,7 +301,7 @@ __global__ void zero_counters_kernel(int *__restrict__ counters, int nwords)
 int dvq_launch_exact_list(const float *z, const float *prep, const float *E, const float *mask,
                           int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
                           const int *list, const int *list_count, DvqLossTail tail, const DvqRouted *rv,
-                          hipStream_t st, const DvqConv *fold_conv = nullptr);
+                          hipStream_t st, const DvqConv *fold_conv = nullptr, int xt = 0);
 
 #ifdef DVQ_TUNING
 // device buffer the tuning build's pass 1 writes its per-token diagnostics to (null = off): tokdbg [N][4] f32 = best, second,
@@ -433,10 +433,14 @@ static bool staged_select_ok(const DvqRouted &rv)
 //   | dense                       | HW == 1 and aligned                             | flat <D, false>                            |
 //   | dense                       | D == 256 and fits                               | cached <D, 0, false>                       |
 //   | dense                       | otherwise                                       | plain <D, 0, false, false>                 |
+// 16-bit latents (xt != 0; dense only): always the x16 form -- the plain kernel on 2-byte accesses, for every HW (HW == 1: the
+// row-major tensor, a lane per token) and every N: the wide, split, flat and cached forms do not exist for them, so a small
+// batch runs unsplit.
 static P1Plan pass1_plan(int D, int HW, int K, long N, bool aligned, const FilterWs &w, bool force_wide, const DvqRouted *rv,
-                         bool conv, bool fold)
+                         bool conv, bool fold, int xt = 0)
 {
     const bool dense = rv == nullptr && !conv && !fold;
+    if (xt != 0) return {P1Form::x16, 0, false, false, false, 1, xt};
     if (dense && D == 256 && (force_wide || (K >= DVQ_WIDE_MIN_K && N >= 256L * 512)))   // large codebook and enough tokens to fill
         return {P1Form::wide, 0, false, false, false, 1};                                 // every CU with two 256-token workgroups
     const int ks = split_slices(K, N);
@@ -459,6 +463,13 @@ static int launch_pass1(int D, const P1Plan &p, const P1Args &a)
     const int tiles = dvq_num_tiles(a.K);
     const int per_wg = (p.form == P1Form::split) ? (tiles + p.ks - 1) / p.ks : tiles;
     const bool res = per_wg <= DVQ_SEED_TABLE_TILES && !p1_keeps_seed_piece(D, p.form, p.fold, p.flat);
+    if (p.form == P1Form::x16)
+        switch (D) {
+        case 64:  return res ? dvq_launch_pass1_x16_d64_res(p, a) : dvq_launch_pass1_x16_d64(p, a);
+        case 128: return res ? dvq_launch_pass1_x16_d128_res(p, a) : dvq_launch_pass1_x16_d128(p, a);
+        case 256: return res ? dvq_launch_pass1_x16_d256_res(p, a) : dvq_launch_pass1_x16_d256(p, a);
+        default:  return -1000;
+        }
     switch (D) {
     case 64:  return res ? dvq_launch_pass1_d64_res(p, a) : dvq_launch_pass1_d64(p, a);
     case 128: return res ? dvq_launch_pass1_d128_res(p, a) : dvq_launch_pass1_d128(p, a);
@@ -472,11 +483,14 @@ static int launch_pass1(int D, const P1Plan &p, const P1Args &a)
 // pass 1); N = B * HWout, mask = the codebook_mask pass 1 writes.
 // Kernels of one op: [zero kernel unless ws_clean] -> pass 1 -> resolver -> list kernel (exact list, loss finalize, and its
 // finishing workgroup puts the counter block back to zero: the op leaves its workspace clean).
+// xt != 0 (dense op only): z and zq hold 16-bit latents of that type (dvq_common.h); every kernel of the chain widens them where
+// it reads them and narrows z_q where it writes it.  The workspace, its carve and the counters are those of the fp32 op.
 int dvq_launch_filter(const float *z, const void *prep, const float *E, const float *mask,
                       int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
                       void *ws_extra, bool pass1_only, bool force_wide, float *loss, float beta,
-                      const DvqRouted *rv, hipStream_t st, const DvqConv *cv, const DvqFold *fd, bool ws_clean)
+                      const DvqRouted *rv, hipStream_t st, const DvqConv *cv, const DvqFold *fd, bool ws_clean, int xt)
 {
+    if (xt != 0 && (rv != nullptr || cv != nullptr || fd != nullptr || pass1_only || force_wide)) return -1000;
     char *base = (char *)prep + dvq_prep_f16_offset(K, D);
     base = (char *)(((uintptr_t)base + 255) / 256 * 256);
     // fd: pass 1 and the resolver's enumeration run on the folded codebook (same section layout); the exact chains, the
@@ -498,14 +512,14 @@ int dvq_launch_filter(const float *z, const void *prep, const float *E, const fl
     const int np1 = (int)((N + 127) / 128);
     const DvqConv *conv = fd != nullptr ? &fd->cv : cv;      // the conv folded into the codebook or computed by pass 1
     const bool aligned = (((uintptr_t)z | (uintptr_t)zq) & 15) == 0;
-    const P1Plan plan = pass1_plan(D, HW, K, N, aligned, w, force_wide, rv, fd == nullptr && cv != nullptr, fd != nullptr);
+    const P1Plan plan = pass1_plan(D, HW, K, N, aligned, w, force_wide, rv, fd == nullptr && cv != nullptr, fd != nullptr, xt);
     const P1Args args = {z, img + dvq_img16_offset(K, D), meta, E, mask, HW, K, N, zq, codes, partials, w,
                          routed ? *rv : DvqRouted{}, conv != nullptr ? *conv : DvqConv{}, st};
     rc = launch_pass1(D, plan, args);                        // (pass 1's code loop runs on v_mfma_f32_16x16x32_f16: image "16")
     if (rc || pass1_only) return rc;
     const int HWout = routed ? rv->HWout : HW, Wout = routed ? rv->Wout : 0;
     rc = dvq_launch_resolver(D, img, meta, en_all, E, HWout, K, zq, codes, partials ? partials + np1 : nullptr,
-                           w, Wout, nullptr, fd, st, partials, np1);
+                           w, Wout, nullptr, fd, st, partials, np1, xt);
     if (rc) return rc;
     double *partials3 = partials ? partials + np1 + w.cap / RES_SLOTS : nullptr;
     // the list kernel is the last of the op: it also sums the partials into loss[0..1] and cleans the counter block; the
@@ -518,7 +532,7 @@ int dvq_launch_filter(const float *z, const void *prep, const float *E, const fl
     // branches) -- qconv.hip's arithmetic, what pass 1's prologue computes too (and with h_all it writes the h it scored over pass
     // 1's row of the token)
     return dvq_launch_exact_list(z, (const float *)prep, E, mask, D, HWout, K, N, zq, codes, partials3, w.exact_list, list_count,
-                                 tail, rv, st, conv);
+                                 tail, rv, st, conv, xt);
 }
 
 // ---- routed op ---------------------------------------------------------------------------------
@@ -527,7 +541,7 @@ int dvq_launch_filter(const float *z, const void *prep, const float *E, const fl
 // exact mode: a prepass writes indices / codebook_mask / gate_out, then every position by the exact chain.
 int dvq_launch_exact(const float *z, const float *prep, const float *E, const float *mask,
                      int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
-                     const DvqRouted *rv, hipStream_t st);
+                     const DvqRouted *rv, hipStream_t st, int xt = 0);
 int dvq_launch_loss_finalize(const double *partials, int nparts, double inv_numel, float beta,
                              float *loss, hipStream_t st);
 
@@ -565,5 +579,5 @@ int dvq_launch_routed(int G, int gate_mode, const void *gate, float thr, const f
         return dvq_launch_loss_finalize(partials, (int)((N + 127) / 128), 1.0 / ((double)N * D), beta, loss, st);
     }
     return dvq_launch_filter(nullptr, prep, E, cmask, D, HWout, K, N, zq, codes, partials, ws_extra, pass1_only, false,
-                             loss, beta, &rv, st, cv, fd, ws_clean);
+                             loss, beta, &rv, st, cv, fd, ws_clean, 0);
 }

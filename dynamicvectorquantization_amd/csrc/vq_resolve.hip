@@ -70,7 +70,9 @@ struct ResLds {
 // Returns (thread 0) the chunk's loss correction; *not_last is set for a slice that is not the chunk's last.
 // HW = positions per image of the OUTPUT grid; a routed token (RecMeta.rep > 1) covers rep x rep positions, rows Wout apart,
 // all rewritten with the same values.
-template <int D, bool FOLD>
+// XT != 0 (dense op on 16-bit latents, dvq_common.h): zq holds that type; the rewritten row is narrowed at the store, from the fp32
+// latents of the record (the widened input), its loss terms taken before.
+template <int D, bool FOLD, int XT = 0>
 __device__ __forceinline__ double resolve_chunk(
     char *__restrict__ L, const int base, const int nlive, const int t_begin, const int t_end,
     const char *__restrict__ img, const float *__restrict__ en_all, const float *__restrict__ E, int HW, int Wout,
@@ -429,11 +431,11 @@ __device__ __forceinline__ double resolve_chunk(
             for (int j = 0; j < 4; ++j) {
                 float dn = __fsub_rn(en_[j], zv[j]), dold = __fsub_rn(eo[j], zv[j]);
                 if (zq != nullptr && !take_back_only) {
-                    float *zp = zq + ((size_t)bimg * D + k0 + j) * HW + hw;
+                    typename DvqLat<XT>::T *zp = (typename DvqLat<XT>::T *)zq + ((size_t)bimg * D + k0 + j) * HW + hw;
                     // FOLD: z_q := e[code] as in pass 1 (the record holds h by now; fl(h + fl(e - h)) is within 1e-6 of it)
                     const float v = FOLD ? en_[j] : __fadd_rn(zv[j], dn);
                     for (int ry = 0; ry < rep; ++ry)
-                        for (int rx = 0; rx < rep; ++rx) zp[(size_t)ry * Wout + rx] = v;
+                        for (int rx = 0; rx < rep; ++rx) zp[(size_t)ry * Wout + rx] = dvq_narrow<XT>(v);
                 }
                 float tn = take_back_only ? 0.0f : __fmul_rn(__fmul_rn(dn, dn), m);
                 delta += tn - __fmul_rn(__fmul_rn(dold, dold), m);
@@ -460,7 +462,7 @@ __device__ __forceinline__ double resolve_chunk(
     return tot;
 }
 
-template <int D, bool FOLD>
+template <int D, bool FOLD, int XT = 0>
 __global__ __launch_bounds__(DVQ_RES_WAVES * 64, DVQ_RES_WAVES > 4 ? 1 : 2) void vq_resolve_kernel(
     const char *__restrict__ img, const DvqF16Meta *__restrict__ meta, const float *__restrict__ en_all,
     const float *__restrict__ E, int HW, int K,
@@ -500,7 +502,7 @@ __global__ __launch_bounds__(DVQ_RES_WAVES * 64, DVQ_RES_WAVES > 4 ? 1 : 2) void
     DVQ_RSTAMP(1);
     bool not_last;
     const int wave0 = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);   // (a scalar: thread 0 is found again below without
-    const double tot = resolve_chunk<D, FOLD>(L, base, nlive, t_begin, t_end, img, en_all, E, HW, Wout, zq, codes, counters,   // keeping threadIdx.x in a register)
+    const double tot = resolve_chunk<D, FOLD, XT>(L, base, nlive, t_begin, t_end, img, en_all, E, HW, Wout, zq, codes, counters,   // keeping threadIdx.x in a register)
                                               exact_list, records, nslice, chunk_sync + 2 * blockIdx.x, h_spill, cv,
                                               partials != nullptr, &not_last);
     const bool thread0 = wave0 == 0 && __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) == 0;
@@ -519,10 +521,19 @@ int dvq_resolver_slices(int K)
 int dvq_launch_resolver(int D, const char *img, const DvqF16Meta *meta, const float *en_all, const float *E,
                         int HWout, int K, float *zq, long long *codes, double *partials,
                         const FilterWs &w, int Wout, float *h_spill, const DvqFold *fd, hipStream_t st,
-                        const double *p1_partials, int np1)
+                        const double *p1_partials, int np1, int xt)
 {
     const bool fold = fd != nullptr;
     decltype(&vq_resolve_kernel<64, false>) kernel;
+    if (xt != 0) {
+        if (fold || (xt != 1 && xt != 2)) return -1000;
+        switch (D) {
+        case 64:  kernel = xt == 1 ? vq_resolve_kernel<64, false, 1> : vq_resolve_kernel<64, false, 2>; break;
+        case 128: kernel = xt == 1 ? vq_resolve_kernel<128, false, 1> : vq_resolve_kernel<128, false, 2>; break;
+        case 256: kernel = xt == 1 ? vq_resolve_kernel<256, false, 1> : vq_resolve_kernel<256, false, 2>; break;
+        default:  return -1000;
+        }
+    } else
     switch (D) {
     case 64:  kernel = fold ? vq_resolve_kernel<64, true> : vq_resolve_kernel<64, false>; break;
     case 128: kernel = fold ? vq_resolve_kernel<128, true> : vq_resolve_kernel<128, false>; break;

@@ -316,10 +316,18 @@ def vq_assign(z, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=T
     stage-2 tokenisation): pass 1 scores z against E W and computes no conv; only undecided tokens get their conv output and the
     reference chain.  codes = the reference argmin for a conv output within 1e-5 sum |w||x| of the real-number conv (the same
     contract as conv= alone: near-ties of that tolerance may resolve differently); z_q = codebook[code] (within 1e-6 relative of
-    fl(h + fl(e - h)))."""
-    z = _lib.require_cuda_f32(z, "z")
+    fl(h + fl(e - h))).
+    float16 / bfloat16 z (an encoder run under autocast; `dvq_vq_assign_nchw_x16`): codes and loss are those of the op on
+    z.float(), z_q that op's rounded once to z.dtype (what `.to(z.dtype)` gives) -- no cast pass on either side.  The codebook,
+    mask and loss stay float32.  Kernel widths and the zero-padded ones only: the narrow widths, conv= and fold= raise TypeError
+    (they take float32)."""
+    z = _lib.require_cuda_latents(z, "z") if (conv is None and not fold) else _lib.require_cuda_f32(z, "z")
     codebook = _lib.require_cuda_f32(codebook, "codebook")
     B, D = z.shape[0], z.shape[1]
+    x16 = _lib.X16.get(z.dtype, 0)
+    if x16 and D in NARROW_WIDTHS + (3,):
+        raise TypeError("z must be float32 at the narrow width %d (16-bit latents: 64, 128, 256 channels or a multiple of 32 "
+                        "below 256), got %s" % (D, z.dtype))
     HW = 1
     for s in z.shape[2:]:
         HW *= s
@@ -363,6 +371,15 @@ def vq_assign(z, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=T
                     _lib.ptr(loss), ws_ptr, ws_bytes, _lib.stream_ptr(z.device))
         return zq, codes, loss
     ws = prep.workspace(B, D, HW, K, mode, z.device)
+    if x16:
+        # 16-bit latents: one entry point for NCHW and row-major (HW == 1) tensors; the workspace is the float32 op's
+        with _lib.on_device(z.device):
+            pbuf = prep.get(codebook)
+            checked.dvq_vq_assign_nchw_x16(
+                z.data_ptr(), x16, codebook.data_ptr(), pbuf.data_ptr(), _lib.ptr(mask), B, D, HW, K, float(beta),
+                _lib.ptr(zq), codes.data_ptr(), _lib.ptr(loss), *ws.begin(mode), _lib.stream_ptr(z.device))
+            ws.end(mode)
+        return zq, codes, loss
     if fold:
         with _lib.on_device(z.device):
             qbuf, pbuf, fbuf = _fold_args(conv, prep, codebook, loss is not None, mode)
@@ -714,7 +731,9 @@ class _VQStraightThrough(torch.autograd.Function):
     the rows chosen at forward time are what the gradient uses, so the EMA update may overwrite the weight in place between
     forward and backward -- a snapshot of the [K, D] codebook (1 MiB) is saved, not the [B, HW, D] gathered rows.
     d/dz runs as ONE kernel (`dvq_vq_backward_nchw_f32`: read z and g_zq, gather e from the snapshot, write g_z) in the same fp32
-    operation order as the torch expression below, which remains the path for CPU tensors / odd channel counts."""
+    operation order as the torch expression below, which remains the path for CPU tensors / odd channel counts.
+    float16 / bfloat16 z: `dvq_vq_backward_nchw_x16` (g_zq of z's dtype or None; g_z comes back in it).  The CODEBOOK gradient of
+    16-bit latents (`dvq_vq_backward_codebook_nchw_f32` is float32-only) takes the torch expression on z.float()."""
 
     @staticmethod
     def forward(ctx, z, weight, mask, prep, K, coef_z, coef_e, mode):
@@ -745,8 +764,9 @@ class _VQStraightThrough(torch.autograd.Function):
         need_z, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         scale = 2.0 / z.numel()
         gz, gw = None, None
-        fused = (need_z and z.is_cuda and z.dtype == torch.float32 and D % 16 == 0 and z.is_contiguous()
-                 and (g_zq is None or (g_zq.dtype == torch.float32 and g_zq.is_cuda)))
+        x16 = _lib.X16.get(z.dtype, 0) if z.is_cuda else 0
+        fused = (need_z and z.is_cuda and (z.dtype == torch.float32 or x16) and D % 16 == 0 and z.is_contiguous()
+                 and (g_zq is None or (g_zq.dtype == z.dtype and g_zq.device == z.device)))
         if need_z and g_loss is None:
             gz = g_zq
         elif fused:
@@ -756,9 +776,14 @@ class _VQStraightThrough(torch.autograd.Function):
             m = None if mask is None else _lib.require_cuda_f32(mask, "codebook_mask")
             gz = torch.empty_like(z)
             with _lib.on_device(z.device):
-                checked.dvq_vq_backward_nchw_f32(
-                    z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), _lib.ptr(gq), gl.data_ptr(),
-                    float(ctx.coef_z * scale), B, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device))
+                if x16:
+                    checked.dvq_vq_backward_nchw_x16(
+                        z.data_ptr(), x16, snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), _lib.ptr(gq), gl.data_ptr(),
+                        float(ctx.coef_z * scale), B, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device))
+                else:
+                    checked.dvq_vq_backward_nchw_f32(
+                        z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), _lib.ptr(gq), gl.data_ptr(),
+                        float(ctx.coef_z * scale), B, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device))
         if need_w and g_loss is not None and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and snap.shape[0] <= 8192:
             HW = z[0, 0].numel()
             gw = torch.zeros(ctx.wshape, dtype=z.dtype, device=z.device)
@@ -772,13 +797,13 @@ class _VQStraightThrough(torch.autograd.Function):
         diff = None
         if (need_z and gz is None) or (need_w and g_loss is not None):
             e = embed_gather(snap, codes.reshape(B, -1)) if z.is_cuda else snap[codes.reshape(B, -1)]   # [B, HW, D]
-            diff = z - e.permute(0, 2, 1).reshape(z.shape)
+            diff = (z.float() if x16 else z) - e.permute(0, 2, 1).reshape(z.shape)
             if mask is not None:
                 diff = diff * mask.reshape(B, 1, *z.shape[2:])
         if need_z and gz is None:
-            gz = (g_zq if g_zq is not None else 0) + g_loss * (ctx.coef_z * scale) * diff
+            gz = ((g_zq if g_zq is not None else 0) + g_loss * (ctx.coef_z * scale) * diff).to(z.dtype)
         if need_w or (gw is None and ctx.needs_input_grad[1]):
-            gw = torch.zeros(ctx.wshape, dtype=z.dtype, device=z.device)
+            gw = torch.zeros(ctx.wshape, dtype=snap.dtype, device=z.device)
             if g_loss is not None and need_w:
                 ge = (-(g_loss * (ctx.coef_e * scale)) * diff).reshape(B, D, -1).permute(0, 2, 1).reshape(-1, D)
                 gw.index_add_(0, codes.reshape(-1), ge)
@@ -897,14 +922,19 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
         flat = torch.empty(n_embed * embed_dim + n_embed, dtype=torch.float32, device=vectors.device)
         vsum = flat[:n_embed * embed_dim].view(n_embed, embed_dim)
         cluster_size = flat[n_embed * embed_dim:]
-        if nchw is not None and nchw.is_cuda and nchw.dtype == torch.float32:
+        if nchw is not None and nchw.is_cuda and (nchw.dtype == torch.float32 or nchw.dtype in _lib.X16):
             z = nchw.contiguous()
             B, HW = z.shape[0], z[0, 0].numel()
             codes = idxs.reshape(B, HW).contiguous()
             with _lib.on_device(z.device):
-                checked.dvq_ema_accumulate_nchw_f32(
-                    z.data_ptr(), codes.data_ptr(), B, embed_dim, HW, n_embed, cluster_size.data_ptr(),
-                    vsum.data_ptr(), _lib.stream_ptr(z.device))
+                if z.dtype in _lib.X16:                  # 16-bit latents: summed in float32 from the exact widened values
+                    checked.dvq_ema_accumulate_nchw_x16(
+                        z.data_ptr(), _lib.X16[z.dtype], codes.data_ptr(), B, embed_dim, HW, n_embed, cluster_size.data_ptr(),
+                        vsum.data_ptr(), _lib.stream_ptr(z.device))
+                else:
+                    checked.dvq_ema_accumulate_nchw_f32(
+                        z.data_ptr(), codes.data_ptr(), B, embed_dim, HW, n_embed, cluster_size.data_ptr(),
+                        vsum.data_ptr(), _lib.stream_ptr(z.device))
         else:
             cluster_size.copy_(torch.bincount(idxs, minlength=n_embed))
             vsum.zero_().index_add_(0, idxs, vectors.to(torch.float32))
@@ -917,7 +947,7 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
         statistics buffer; the restart vectors are broadcast from rank 0 as in :100."""
         n_embed, embed_dim = self.weight.shape[0] - 1, self.weight.shape[-1]
         idxs = idxs.reshape(-1)
-        if nchw is None or not (nchw.is_cuda and nchw.dtype == torch.float32):
+        if nchw is None or not (nchw.is_cuda and (nchw.dtype == torch.float32 or nchw.dtype in _lib.X16)):
             vectors = vectors.reshape(-1, embed_dim)      # token rows (with NCHW latents on the GPU they are never materialised:
             nchw = None                                   # `vectors` stays the permuted VIEW [B, HW, D], rows are picked by index)
         cluster_size, vectors_sum_per_cluster, flat = self._cluster_sums(vectors, idxs, nchw)
@@ -936,7 +966,8 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
         fewer input vectors than codes (the reference tiles them with noise), a replaced torch.randperm with too few vectors for
         the pick kernel -- takes the two methods one after the other."""
         n_embed, embed_dim = self.weight.shape[0] - 1, self.weight.shape[-1]
-        ok = (nchw is not None and nchw.is_cuda and nchw.dtype == torch.float32 and self.weight.is_cuda
+        x16 = nchw is not None and nchw.is_cuda and nchw.dtype in _lib.X16
+        ok = (nchw is not None and nchw.is_cuda and (nchw.dtype == torch.float32 or x16) and self.weight.is_cuda
               and self.weight.dtype == torch.float32 and self.weight.is_contiguous()
               and self.embed_ema.is_contiguous() and self.embed_ema.dtype == torch.float32)
         n_vectors = idxs.numel()
@@ -955,16 +986,18 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
         if self.restart_unused_codes:
             pick = _restart_pick(n_vectors, n_embed, z.device).contiguous()
             restart = 2
-            if ddp:                                          # every rank restarts from rank 0's vectors (quantize2_mask.py:100)
-                rows = vectors[torch.div(pick, HW, rounding_mode="floor"), pick % HW].contiguous()
-                dist.broadcast(rows, 0)
+            if ddp or x16:                                   # every rank restarts from rank 0's vectors (quantize2_mask.py:100);
+                # 16-bit latents: dvq_ema_update_f32 reads float32 rows, so the K picked rows are gathered and widened here
+                rows = vectors[torch.div(pick, HW, rounding_mode="floor"), pick % HW].to(torch.float32).contiguous()
+                if ddp:
+                    dist.broadcast(rows, 0)
                 restart = 1
         cs_new = torch.empty_like(self.cluster_size_ema)
         with _lib.on_device(z.device):
             checked.dvq_ema_update_f32(
                 vectors_sum.data_ptr(), cluster_size.data_ptr(), float(self.decay), float(self.eps), n_embed, embed_dim,
                 self.cluster_size_ema.data_ptr(), cs_new.data_ptr(), self.embed_ema.data_ptr(), self.weight.data_ptr(),
-                restart, _lib.ptr(rows), z.data_ptr(), B, HW, _lib.ptr(pick), _lib.stream_ptr(z.device))
+                restart, _lib.ptr(rows), 0 if x16 else z.data_ptr(), B, HW, _lib.ptr(pick), _lib.stream_ptr(z.device))
         self.cluster_size_ema.copy_(cs_new)
         self._prep.invalidate()
 
@@ -1837,6 +1870,7 @@ class VectorQuantizer(InvalidatesPrepared, nn.Module):
         if self.training:
             self._prep.invalidate()                      # the optimizer may have stepped through .data
         self._prep.track_users = self.training
+        _lib.refuse_x16(z, "z")
         z_q, loss, codes = _vq_straight_through(z, self.embedding.weight, None, self._prep, self.n_e,
                                                     1.0, float(self.beta), self.assign_mode)
         with torch.no_grad():
@@ -1965,6 +1999,7 @@ class EMAVectorQuantizer(InvalidatesPrepared, nn.Module):
             self._prep.invalidate()                      # load_state_dict / .data writers between steps
         self._prep.track_users = self.training
         # coefficients (1, 0): the op's loss output is 0 * m + m = m = mean((z_q.detach() - z)^2) exactly, its gradient 2 (z - e) / numel
+        _lib.refuse_x16(z, "z")
         z_q, mse, codes = _vq_straight_through(z, self.embedding.weight, None, self._prep, self.num_tokens, 1.0, 0.0,
                                                    self.assign_mode)
         flat = codes.reshape(-1)

@@ -30,6 +30,9 @@
  *     dvq_vq_assign_narrow_*_f32 below; every other entry point refuses them as before.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.17.0 DVQ_DTYPE_F16 / DVQ_DTYPE_BF16, dvq_vq_assign_nchw_x16, dvq_vq_backward_nchw_x16, dvq_ema_accumulate_nchw_x16 (new): the dense
+ *          assign, its backward and the EMA statistics on fp16 / bf16 latents (an encoder run under autocast), everything else float32.
+ *          Nothing else changed.
  *   0.16.0 dvq_vq_cdist_sample_assign_f32, dvq_ortho_loss_workspace_bytes, dvq_ortho_loss_forward_f32, dvq_ortho_loss_backward_f32,
  *          dvq_lucid_update_f32 (new): the lucidrains-style codebooks (quantize_lucidrains.py) -- the sampled assign against -cdist, the
  *          orthogonal regulariser with its gradient, and the per-step codebook update with code expiry.  Nothing else changed.
@@ -935,6 +938,43 @@ DVQ_API int dvq_ortho_loss_backward_f32(const float *t, const float *rinv, const
 DVQ_API int dvq_lucid_update_f32(int kind, const float *counts, const float *sums, float decay, float eps, float threshold,
                                  int K, int D, const float *cluster_size, float *cluster_size_out, const float *embed_avg,
                                  float *embed, const float *x, int B, int HW, const int64_t *pick, void *stream);
+
+/*
+ * 16-bit latents: the dense assign, its backward and the EMA statistics on fp16 / bf16 tensors (an encoder trunk run under autocast
+ * hands the quantizer such latents; casting them to float32 and z_q back costs two extra passes over [B, D, H, W]).
+ * Only LATENT-SHAPED tensors change type: z, zq, g_zq, g_z are `dtype` (DVQ_DTYPE_F16: IEEE binary16; DVQ_DTYPE_BF16: bfloat16),
+ * 2-byte aligned; the codebook, prep buffer, mask, loss, statistics and g_loss stay float32.  With zf = float32(z) (exact; fp16
+ * subnormals included):
+ *   dvq_vq_assign_nchw_x16     codes: bit for bit those of dvq_vq_assign_nchw_f32 on zf (first-index / NaN rules included);
+ *                              loss[0..1]: that op's on zf, from fp32 (e - zf) before any narrowing (1e-5 relative);
+ *                              zq = narrow(fl(zf + fl(e - zf))): the fp32 op's value rounded ONCE to `dtype`, to nearest even (the bits
+ *                              of torch's zq_f32.to(dtype); NaN stays NaN, payload unspecified; fp16 overflow gives +-inf).
+ *                              z / zq [B, D, HW] of `dtype` (HW == 1: row-major [N, D], B = N); zq nullable.  prep: the unchanged
+ *                              dvq_codebook_prepare_f32 buffer.  ws >= dvq_vq_assign_workspace_bytes(B, D, HW, K, mode), the layout
+ *                              group is "dense" (DVQ_MODE_WS_CLEAN is honoured, also between this op and dvq_vq_assign_nchw_f32 of the
+ *                              same shape); dvq_vq_assign_fallback_count_offset applies.  mode: DVQ_MODE_FILTER or DVQ_MODE_EXACT
+ *                              (DVQ_MODE_FILTER_PASS1 / DVQ_MODE_FILTER_WIDE: DVQ_EUNSUPPORTED).  D in {64, 128, 256}; the narrow widths
+ *                              (3, 4, 8, 16) and every other D: DVQ_EUNSUPPORTED.  Pass 1 runs the lane-per-token form for every shape
+ *                              (no split / wide / row-major form: a small batch runs unsplit).
+ *                              DVQ_EINVAL: dtype not 1 / 2; null z / codebook / prep / codes; z or zq not 2-byte aligned; the size rules of
+ *                              the f32 op.  DVQ_EWORKSPACE: ws too small.
+ *   dvq_vq_backward_nchw_x16   g_z = narrow(g_zq_f + (g_loss * coef_scale) * ((zf - e) * m)), the fp32 operation order of
+ *                              dvq_vq_backward_nchw_f32 on the widened inputs, narrowed once.  z, g_zq (nullable), g_z of `dtype`;
+ *                              g_loss (nullable, not both) a float32 device scalar; argument rules as the f32 op.
+ *   dvq_ema_accumulate_nchw_x16  cluster_size / vectors_sum over zf, float32, accumulated as dvq_ema_accumulate_nchw_f32 does (float
+ *                              atomics: equal to rounding, 1e-5).  Any 2-byte aligned z, any HW.
+ * Vector and buffer stores only.  dvq_ema_update_f32 has no 16-bit twin: pass restart = 1 with the K restart rows gathered and widened.
+ */
+#define DVQ_DTYPE_F16 1   // IEEE binary16
+#define DVQ_DTYPE_BF16 2  // bfloat16: the upper 16 bits of a float32
+DVQ_API int dvq_vq_assign_nchw_x16(const void *z, int dtype, const float *codebook, const void *prep, const float *mask,
+                                   int B, int D, int HW, int K, float beta, void *zq, int64_t *codes, float *loss,
+                                   void *ws, size_t ws_bytes, int mode, void *stream);
+DVQ_API int dvq_vq_backward_nchw_x16(const void *z, int dtype, const float *codebook, const int64_t *codes, const float *mask,
+                                     const void *g_zq, const float *g_loss, float coef_scale, int B, int D, int HW, int K,
+                                     void *g_z, void *stream);
+DVQ_API int dvq_ema_accumulate_nchw_x16(const void *z, int dtype, const int64_t *codes, int B, int D, int HW, int K,
+                                        float *cluster_size, float *vectors_sum, void *stream);
 
 #ifdef __cplusplus
 }
