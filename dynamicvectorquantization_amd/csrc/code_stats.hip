@@ -14,7 +14,7 @@
 // Grain form: codes [B, H, W] of a dual / triple granularity model with its grain map [B, hc, wc] (0 = coarsest): every REGION is
 // counted once, into the row of its grain -- position (y, x) counts iff y and x are multiples of s = (H / hc) >> grain, which is
 // the position the permuter emits for that region.
-#include "dvq_common.h"
+#include "launchers.h"
 
 #define CS_NT 256
 #define CS_LDS_MAX_FLAT 16384              // counters in LDS, flat form: 64 KiB, two workgroups per CU still stream the one-hot

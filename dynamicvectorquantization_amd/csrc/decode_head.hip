@@ -20,7 +20,7 @@
 //   stream   F and L are read and h_in is written with 16 bytes per lane along the token axis, 256 contiguous bytes per
 //            16 lanes, when HW % 4 == 0 and the three bases are 16-byte aligned; else lane = token with 4-byte accesses.
 // The grid is (ceil(B * HW / 64), ceil(C / 64)): sized from B * HW * C, so B = 16 still gives 1024 workgroups at C = 256.
-#include "dvq_common.h"
+#include "launchers.h"
 
 typedef float dh_f32x4 __attribute__((ext_vector_type(4)));
 

@@ -5,7 +5,7 @@
 #include <stdio.h>
 
 #include "../../include/dvq.h"
-#include "dvq_filter.h"
+#include "launchers.h"
 
 #define DVQ_VERSION 1700   // 0.17.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
@@ -20,141 +20,6 @@ void dvq_set_error(const char *fmt, ...)
     va_end(ap);
 }
 
-// launchers implemented next to their kernels
-int dvq_launch_prep_f32(const float *E, int K, int D, void *prep, hipStream_t st);
-int dvq_launch_prep_f16(const float *E, int K, int D, void *prep, hipStream_t st);
-int dvq_launch_exact(const float *z, const float *prep, const float *E, const float *mask,
-                     int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
-                     const DvqRouted *rv, hipStream_t st, int xt = 0);
-int dvq_launch_filter(const float *z, const void *prep, const float *E, const float *mask,
-                      int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
-                      void *ws_extra, bool pass1_only, bool force_wide, float *loss, float beta,
-                      const DvqRouted *rv, hipStream_t st, const DvqConv *cv, const DvqFold *fd, bool ws_clean, int xt = 0);
-int dvq_launch_routed(int G, int gate_mode, const void *gate, float thr, const float *h_coarse,
-                      const float *h_median, const float *h_fine, const void *prep, const float *E,
-                      int B, int D, int hc, int wc, int K, float beta, float *zq, long long *codes,
-                      float *loss, long long *indices, float *cmask, long long *gate_out,
-                      double *partials, void *ws_extra, bool exact, bool pass1_only, hipStream_t st, const DvqConv *cv,
-                      const DvqFold *fd, bool ws_clean);
-size_t dvq_fold_prep_bytes_impl(int K, int D);
-int dvq_launch_fold_prep(const float *E, int K, int D, const void *cbprep, const float *Wt, const float *bias, void *fprep,
-                         hipStream_t st);
-size_t dvq_filter_ws_extra_bytes(int D, int HW, int K, long N);
-bool dvq_filter_supported(int D, int HW, int K, long N);
-int dvq_launch_loss_finalize(const double *partials, int nparts, double inv_numel, float beta,
-                             float *loss, hipStream_t st);
-int dvq_launch_route_select(int G, int gate_mode, const void *gate, const float *h_coarse,
-                            const float *h_median, const float *h_fine, int B, int C, int hc, int wc,
-                            float *h_out, long long *indices, float *cmask, float thr, long long *gate_out,
-                            hipStream_t st);
-int dvq_launch_entropy_gate(const float *ent, long n, float thr, long long *gate, hipStream_t st);
-int dvq_launch_vq_backward_z(const float *z, const float *E, const long long *codes, const float *mask, const float *g_zq,
-                             const float *g_loss, float coef_scale, int D, int HW, int K, long N, float *gz, hipStream_t st);
-int dvq_launch_vq_backward_z_x16(const void *z, int xt, const float *E, const long long *codes, const float *mask, const void *g_zq,
-                                 const float *g_loss, float coef_scale, int D, int HW, int K, long N, void *gz, hipStream_t st);
-int dvq_launch_ema_accumulate_x16(const void *z, int xt, const long long *codes, int D, int HW, long N, int K,
-                                  float *cluster_size, float *vectors_sum, hipStream_t st);
-int dvq_launch_codebook_grad(const float *z, const float *E, const long long *codes, const float *mask, const float *g_loss,
-                             float coef_scale, int D, int HW, long N, int K, float *gw, hipStream_t st);
-int dvq_launch_embed_gather(const float *E, int K, int D, const long long *idx, long n, float *out,
-                            hipStream_t st);
-
-int dvq_launch_permute_count(const long long *grain, int B, int ncell, int *counts, int *maxes, hipStream_t st);
-int dvq_launch_permute_forward(const long long *codes, const long long *grain, int B, int hc, int wc,
-                               int row_first, int Lc, int Lf, const long long *special,
-                               long long *cc, long long *cp, long long *cs, long long *fc, long long *fp,
-                               long long *fs, hipStream_t st);
-int dvq_launch_permute_backward(const long long *cc, const long long *fc, const long long *cp,
-                                const long long *fp, int B, int Lc, int Lf, int hc, int wc,
-                                long long cpos_eos, long long fpos_eos, long long *target, hipStream_t st);
-int dvq_permute_max_cells(void);
-int dvq_launch_sample_head(const float *logits, long long lstride, int B, int V, float temperature, const long long *rules,
-                           const long long *hist, long long hstride, int hlen, float *flag, int top_k, float top_p,
-                           int sample, const float *q, long long *tokens, long long tstride, float *out_logits,
-                           float *out_probs, hipStream_t st);
-int dvq_launch_transfer_count(const long long *cp, long long cstride, int B, int Lc, int hc, long long ceos, int remain,
-                              int *counts, int *maxes, hipStream_t st);
-int dvq_launch_transfer_fill(const long long *cp, long long cstride, int B, int Lc, int hc, long long ceos, int remain,
-                             int row_first, int sos_mode, long long sos, long long feos, long long fpad, int L, long long *out,
-                             hipStream_t st);
-int dvq_sample_max_vocab(void);
-int dvq_sample_max_cells(void);
-int dvq_launch_decode_table(const float *E, int rows, int D, const float *W, const float *bias, int C, float *T, hipStream_t st);
-int dvq_launch_decode_head(const long long *codes, int B, int HW, const float *T, int rows, int C, const float *F, const float *L,
-                           float *out, hipStream_t st);
-int dvq_launch_ema_accumulate(const float *z, const long long *codes, int D, int HW, long N, int K,
-                              float *cluster_size, float *vectors_sum, hipStream_t st);
-int dvq_launch_code_stats(const long long *codes, long N, int K, long long *counts, long long *n_used, float *perplexity,
-                          float *onehot, hipStream_t st);
-int dvq_launch_code_stats_grain(const long long *codes, const long long *grain, int B, int H, int W, int hc, int wc, int G, int K,
-                                long long *counts, long long *n_tokens, long long *n_used, float *perplexity, hipStream_t st);
-int dvq_launch_entropy_map(const float *img, int B, int H, int W, float *out, hipStream_t st);
-size_t dvq_router_gate_ws_bytes(int nb, int B, int C, int hc, int wc, int groups, int Hid);
-size_t dvq_router_gate_prep_bytes_impl(int nb, int C, int Hid);
-int dvq_launch_router_gate_prepare(const float *W1, int nb, int C, int Hid, void *prep, hipStream_t st);
-int dvq_launch_restart_pick(unsigned long long seed, long long n, int k, long long *out, hipStream_t st);
-int dvq_launch_ema_update(const float *stats_sum, const float *stats_count, float decay, float eps, int K, int D,
-                          const float *cs_old, float *cs_new, float *embed_ema, float *weight, int restart, const float *restart_rows,
-                          const float *z, int HW, const long long *pick, hipStream_t st);
-int dvq_launch_router_gate_prepare_norm(const float *const *gn_w, const float *const *gn_b, int nb, int C, int Hid, void *prep,
-                                        hipStream_t st);
-int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn_w, const float *const *gn_b,
-                           int B, int C, int hc, int wc, int groups, float eps,
-                           const float *W1, const float *b1, const float *W2, const float *b2,
-                           int Hid, int act, const void *w1_prep, float *gate, void *ws, hipStream_t st);
-size_t dvq_route_train_ws_bytes(int nb, int B, int C, int hc, int wc, int groups, int H);
-int dvq_launch_route_train_fwd(const DvqRouteTrain *p, hipStream_t st);
-int dvq_launch_route_train_bwd(const DvqRouteTrain *p, hipStream_t st);
-
-int dvq_rq_blocks(long N, int D);
-void dvq_rq_layout(long N, int D, int depth, int want_grad, size_t *off_res0, size_t *off_res1, size_t *off_agg, size_t *off_s,
-                   size_t *total);
-int dvq_launch_rq_step(const float *x, const float *r_in, const float *E, int K, const long long *code, int B, int h, int w,
-                       int rH, int rW, int Dl, int i, int depth, int want_grad, long long *codes, float *out, void *ws,
-                       hipStream_t st);
-int dvq_launch_rq_loss(long N, int D, int depth, const void *ws, float *loss, hipStream_t st);
-int dvq_launch_rq_backward(const float *g_out, const float *g_loss, int B, int h, int w, int rH, int rW, int Dl, int depth,
-                           const void *ws, float *g_x, hipStream_t st);
-int dvq_launch_rq_embed(const float *const *E, const int *K, int depth, const long long *codes, int B, int h, int w, int rH, int rW,
-                        int Dl, int mode, int j, float *out, hipStream_t st);
-int dvq_launch_soft_assign(const float *x, const float *prep, int D, int K, long N, float temp, const float *q, float *soft,
-                           float *dist, float *sbuf, long long *codes, hipStream_t st);
-int dvq_launch_score_assign(const float *z, const float *prep, int D, int HW, int K, long N, int metric, float temp, const float *u,
-                            long long *codes, hipStream_t st);
-int dvq_launch_cdist_sample_assign(const float *z, const float *prep, int D, int HW, int K, long N, float temp, const float *u,
-                                   long long *codes, hipStream_t st);
-void dvq_ortho_grid(int h, int n, unsigned *gx, unsigned *gy);
-int dvq_launch_ortho_forward(const float *t, int h, int n, int D, float *rinv, float *loss, double *partials, hipStream_t st);
-void dvq_ortho_backward_slices(int h, int n, int *S, int *tper);
-int dvq_launch_ortho_backward(const float *t, const float *rinv, const float *gout, int h, int n, int D, float *grad, float *gpart,
-                              hipStream_t st);
-int dvq_launch_lucid_update(int kind, const float *counts, const float *sums, float decay, float eps, float threshold, int K, int D,
-                            const float *cs_old, float *cs_new, const float *embed_avg, float *embed, const float *x, int HW,
-                            long long N, const long long *pick, hipStream_t st);
-int dvq_apply_codes_blocks(long N);
-int dvq_launch_apply_codes(const float *z, const float *E, const long long *codes, const float *mask, int D, int HW, int K, long N,
-                           float *zq, double *partials, hipStream_t st);
-int dvq_launch_gumbel_bias(const float *bias, int K, int D, void *prep, hipStream_t st);
-int dvq_gumbel_blocks(long N);
-int dvq_launch_gumbel_assign(const float *z, const float *prep, const float *E, int C, int HW, int K, int d, long N, float tau,
-                             double log_kl_K, const float *q, float *zq, long long *codes, double *partials, hipStream_t st);
-int dvq_narrow_tile_codes(int D);
-int dvq_narrow_blocks(long N);
-int dvq_launch_narrow(const float *z, const float *E, const float *mask, int D, int HW, int K, long N, bool flat, float *zq,
-                      long long *codes, double *partials, hipStream_t st);
-int dvq_launch_gumbel_kl_finalize(const double *partials, int nparts, double inv_n, float *kl, hipStream_t st);
-size_t dvq_qconv_prep_bytes_impl(int D);
-int dvq_launch_qconv_prep(const float *Wt, const float *bias, int D, void *prep, hipStream_t st);
-int dvq_launch_qconv(const float *x, const DvqRouted *rv, const void *prep, int D, int HW, long N, float *hout,
-                     hipStream_t st);
-int dvq_launch_filter_scores_debug(const float *tokens, int n, const void *prep, int D, int K, float *G,
-                                   float *thr2W, float *xn, float *scale_b_out, hipStream_t st, int fold = 0);
-size_t dvq_xch_bytes(long cpi, long gpi, int b_max, int num_codes);
-int dvq_launch_xch_pack(const long long *codes, const long long *grain, const float *loss, double numel, int b_local,
-                        int b_max, long cpi, long gpi, int num_codes, void *buf, hipStream_t st);
-int dvq_launch_xch_unpack(const void *gathered, int world, int global_batch, long cpi, long gpi, int num_codes,
-                          long long *codes, long long *grain, float *mean, hipStream_t st);
-
 static int hip_rc(int rc, const char *what)
 {
     if (rc == 0) return DVQ_OK;
@@ -163,6 +28,63 @@ static int hip_rc(int rc, const char *what)
 }
 
 static bool dim_ok(int D) { return D == 64 || D == 128 || D == 256; }
+
+// ---- checks whose words repeat from entry point to entry point: each sets the message and returns its status, DVQ_OK to go on.
+// A site whose text or status differs in anything (dvq.h promises them as they are) stays written out where it is.
+static int null_pointer(const char *fn) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+
+static int check_positive(const char *fn, int B, int HW, int K)
+{
+    if (B > 0 && HW > 0 && K > 0) return DVQ_OK;
+    dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K);
+    return DVQ_EINVAL;
+}
+
+static int check_width(const char *fn, int D)
+{
+    if (dim_ok(D)) return DVQ_OK;
+    dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D);
+    return DVQ_EUNSUPPORTED;
+}
+
+// N tokens (below 2^31 where n31) of w0, w1, w2 elements each: every product below 2^40
+static int check_size(const char *fn, size_t N, bool n31, size_t w0 = 0, size_t w1 = 0, size_t w2 = 0)
+{
+    const size_t lim = (size_t)1 << 40;
+    if (!(n31 && N >= ((size_t)1 << 31)) && N * w0 < lim && N * w1 < lim && N * w2 < lim) return DVQ_OK;
+    dvq_set_error("%s: tensor too large", fn);
+    return DVQ_EUNSUPPORTED;
+}
+
+static int check_ws_aligned(const char *fn, const void *ws)     // (null passes)
+{
+    if (((uintptr_t)ws & 255) == 0) return DVQ_OK;
+    dvq_set_error("%s: workspace must be 256-byte aligned", fn);
+    return DVQ_EINVAL;
+}
+
+// a workspace of `need` bytes, then its alignment; null_as_0: a null workspace is reported as 0 bytes
+static int check_workspace(const char *fn, const void *ws, size_t ws_bytes, size_t need, bool null_as_0 = false)
+{
+    if (ws && ws_bytes >= need) return check_ws_aligned(fn, ws);
+    dvq_set_error("%s: workspace %zu < %zu bytes", fn, (ws || !null_as_0) ? ws_bytes : (size_t)0, need);
+    return DVQ_EWORKSPACE;
+}
+
+static int check_prep_buffer(const char *fn, const void *prep, size_t prep_bytes, size_t need)
+{
+    if (prep_bytes < need) { dvq_set_error("%s: prep buffer %zu < %zu bytes", fn, prep_bytes, need); return DVQ_EWORKSPACE; }
+    if (((uintptr_t)prep & 255) != 0) { dvq_set_error("%s: prep must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    return DVQ_OK;
+}
+
+// the *_x16 entry points: dtype names one of the two 16-bit types
+static int check_x16_dtype(const char *fn, int dtype)
+{
+    if (dtype == DVQ_DTYPE_F16 || dtype == DVQ_DTYPE_BF16) return DVQ_OK;
+    dvq_set_error("%s: dtype %d (DVQ_DTYPE_F16 = 1, DVQ_DTYPE_BF16 = 2)", fn, dtype);
+    return DVQ_EINVAL;
+}
 
 // loss partials: pass 1 / exact blocks (<= 2 ceil(N/128)), resolver blocks (<= max(32, ceil(N/128)))
 static size_t partials_bytes_for(long N)
@@ -190,9 +112,8 @@ int dvq_codebook_prepare_f32(const float *codebook, int K, int D, void *prep, si
                              void *stream)
 {
     if (!codebook || !prep || K <= 0) { dvq_set_error("dvq_codebook_prepare_f32: null pointer or K <= 0"); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("dvq_codebook_prepare_f32: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", D); return DVQ_EUNSUPPORTED; }
-    if (prep_bytes < dvq_codebook_prep_bytes(K, D)) { dvq_set_error("dvq_codebook_prepare_f32: prep buffer %zu < %zu bytes", prep_bytes, dvq_codebook_prep_bytes(K, D)); return DVQ_EWORKSPACE; }
-    if (((uintptr_t)prep & 255) != 0) { dvq_set_error("dvq_codebook_prepare_f32: prep must be 256-byte aligned"); return DVQ_EINVAL; }
+    if (int rc = check_width("dvq_codebook_prepare_f32", D)) return rc;
+    if (int rc = check_prep_buffer("dvq_codebook_prepare_f32", prep, prep_bytes, dvq_codebook_prep_bytes(K, D))) return rc;
     hipStream_t st = (hipStream_t)stream;
     int rc = dvq_launch_prep_f32(codebook, K, D, prep, st);
     if (rc) return hip_rc(rc, "codebook_prep_f32");
@@ -218,89 +139,63 @@ size_t dvq_vq_assign_fallback_count_offset(int B, int D, int HW, int K)
     return partials_bytes_for(N);
 }
 
-int dvq_vq_assign_nchw_f32(const float *z, const float *codebook, const void *prep,
-                           const float *mask, int B, int D, int HW, int K, float beta,
-                           float *zq, int64_t *codes, float *loss,
-                           void *ws, size_t ws_bytes, int mode, void *stream)
+// The dense assign, float32 latents (dtype 0) or 16-bit ones (DVQ_DTYPE_F16 / DVQ_DTYPE_BF16: z read and zq written as that type by
+// the same chain of kernels)
+static int assign_nchw(const char *fn, int dtype, const void *z, const float *codebook, const void *prep, const float *mask,
+                       int B, int D, int HW, int K, float beta, void *zq, int64_t *codes, float *loss,
+                       void *ws, size_t ws_bytes, int mode, void *stream)
 {
-    if (!z || !codebook || !prep || !codes) { dvq_set_error("dvq_vq_assign_nchw_f32: null pointer"); return DVQ_EINVAL; }
-    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("dvq_vq_assign_nchw_f32: B=%d HW=%d K=%d must be positive", B, HW, K); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("dvq_vq_assign_nchw_f32: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", D); return DVQ_EUNSUPPORTED; }
+    const bool x16 = dtype != 0;
+    if (!z || !codebook || !prep || !codes) return null_pointer(fn);
+    if (x16 && (((uintptr_t)z | (uintptr_t)zq) & 1) != 0) { dvq_set_error("%s: z and zq must be 2-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_positive(fn, B, HW, K)) return rc;
+    if (x16 && !dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; the narrow widths 3, 4, 8, 16 take float32 latents only: dvq_vq_assign_narrow_*_f32)", fn, D); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_width(fn, D)) return rc;
     const bool ws_clean = (mode & DVQ_MODE_WS_CLEAN) != 0;
     mode &= ~DVQ_MODE_WS_CLEAN;
     const bool pass1_only = (mode == DVQ_MODE_FILTER_PASS1);
     const bool force_wide = (mode == DVQ_MODE_FILTER_WIDE);
+    if (x16 && (pass1_only || force_wide)) { dvq_set_error("%s: mode %d (pass 1 alone / the wide form) exists for float32 latents only", fn, mode); return DVQ_EUNSUPPORTED; }
     if (pass1_only || force_wide) mode = DVQ_MODE_FILTER;
-    if (mode != DVQ_MODE_EXACT && mode != DVQ_MODE_FILTER) { dvq_set_error("dvq_vq_assign_nchw_f32: unknown mode %d", mode); return DVQ_EINVAL; }
-    if ((size_t)B * HW * D >= ((size_t)1 << 40)) { dvq_set_error("dvq_vq_assign_nchw_f32: tensor too large"); return DVQ_EUNSUPPORTED; }
-    const long N = (long)B * HW;
-    if (loss && !ws) { dvq_set_error("dvq_vq_assign_nchw_f32: loss requested without workspace"); return DVQ_EINVAL; }
-    if ((loss || mode == DVQ_MODE_FILTER) && (!ws || ws_bytes < dvq_vq_assign_workspace_bytes(B, D, HW, K, mode))) {
-        dvq_set_error("dvq_vq_assign_nchw_f32: workspace %zu < %zu bytes", ws_bytes, dvq_vq_assign_workspace_bytes(B, D, HW, K, mode));
-        return DVQ_EWORKSPACE;
-    }
-    if (ws && ((uintptr_t)ws & 255) != 0) { dvq_set_error("dvq_vq_assign_nchw_f32: workspace must be 256-byte aligned"); return DVQ_EINVAL; }
-    hipStream_t st = (hipStream_t)stream;
-    double *partials = loss ? (double *)ws : nullptr;
-    size_t partials_bytes = partials_bytes_for(N);
-    int nparts;
-    int rc;
-    if (mode == DVQ_MODE_FILTER && dvq_filter_supported(D, HW, K, N)) {
-        rc = dvq_launch_filter(z, prep, codebook, mask, D, HW, K, N, zq, (long long *)codes, partials,
-                               (char *)ws + partials_bytes, pass1_only, force_wide, loss, beta, nullptr, st, nullptr, nullptr, ws_clean);
-        return hip_rc(rc, "vq_assign_filter");     // the loss finalize is fused into its last kernel
-    } else {
-        rc = dvq_launch_exact(z, (const float *)prep, codebook, mask, D, HW, K, N, zq,
-                              (long long *)codes, partials, nullptr, st);
-        if (rc) return hip_rc(rc, "vq_assign_exact");
-        nparts = (int)((N + 127) / 128);
-    }
-    if (loss) {
-        rc = dvq_launch_loss_finalize(partials, nparts, 1.0 / ((double)N * D), beta, loss, st);
-        if (rc) return hip_rc(rc, "vq_loss_finalize");
-    }
-    return DVQ_OK;
-}
-
-// 16-bit latents (dtype: DVQ_DTYPE_F16 / DVQ_DTYPE_BF16): the same chain of kernels, z read and zq written as that type
-int dvq_vq_assign_nchw_x16(const void *z, int dtype, const float *codebook, const void *prep, const float *mask,
-                           int B, int D, int HW, int K, float beta, void *zq, int64_t *codes, float *loss,
-                           void *ws, size_t ws_bytes, int mode, void *stream)
-{
-    const char *fn = "dvq_vq_assign_nchw_x16";
-    if (dtype != DVQ_DTYPE_F16 && dtype != DVQ_DTYPE_BF16) { dvq_set_error("%s: dtype %d (DVQ_DTYPE_F16 = 1, DVQ_DTYPE_BF16 = 2)", fn, dtype); return DVQ_EINVAL; }
-    if (!z || !codebook || !prep || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
-    if ((((uintptr_t)z | (uintptr_t)zq) & 1) != 0) { dvq_set_error("%s: z and zq must be 2-byte aligned", fn); return DVQ_EINVAL; }
-    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; the narrow widths 3, 4, 8, 16 take float32 latents only: dvq_vq_assign_narrow_*_f32)", fn, D); return DVQ_EUNSUPPORTED; }
-    const bool ws_clean = (mode & DVQ_MODE_WS_CLEAN) != 0;
-    mode &= ~DVQ_MODE_WS_CLEAN;
-    if (mode == DVQ_MODE_FILTER_PASS1 || mode == DVQ_MODE_FILTER_WIDE) { dvq_set_error("%s: mode %d (pass 1 alone / the wide form) exists for float32 latents only", fn, mode); return DVQ_EUNSUPPORTED; }
     if (mode != DVQ_MODE_EXACT && mode != DVQ_MODE_FILTER) { dvq_set_error("%s: unknown mode %d", fn, mode); return DVQ_EINVAL; }
-    if ((size_t)B * HW * D >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_size(fn, (size_t)B * HW, false, D)) return rc;
     const long N = (long)B * HW;
     if (loss && !ws) { dvq_set_error("%s: loss requested without workspace", fn); return DVQ_EINVAL; }
-    if ((loss || mode == DVQ_MODE_FILTER) && (!ws || ws_bytes < dvq_vq_assign_workspace_bytes(B, D, HW, K, mode))) {
-        dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, dvq_vq_assign_workspace_bytes(B, D, HW, K, mode));
-        return DVQ_EWORKSPACE;
-    }
-    if (ws && ((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = (loss || mode == DVQ_MODE_FILTER) ? check_workspace(fn, ws, ws_bytes, dvq_vq_assign_workspace_bytes(B, D, HW, K, mode))
+                                                   : check_ws_aligned(fn, ws)) return rc;
     hipStream_t st = (hipStream_t)stream;
     double *partials = loss ? (double *)ws : nullptr;
     if (mode == DVQ_MODE_FILTER && dvq_filter_supported(D, HW, K, N)) {
         const int rc = dvq_launch_filter((const float *)z, prep, codebook, mask, D, HW, K, N, (float *)zq, (long long *)codes, partials,
-                                         (char *)ws + partials_bytes_for(N), false, false, loss, beta, nullptr, st, nullptr, nullptr,
-                                         ws_clean, dtype);
-        return hip_rc(rc, "vq_assign_filter_x16");
+                                         (char *)ws + partials_bytes_for(N), pass1_only, force_wide, loss, beta, nullptr, st, nullptr,
+                                         nullptr, ws_clean, dtype);
+        return hip_rc(rc, x16 ? "vq_assign_filter_x16" : "vq_assign_filter");     // the loss finalize is fused into its last kernel
     }
     int rc = dvq_launch_exact((const float *)z, (const float *)prep, codebook, mask, D, HW, K, N, (float *)zq, (long long *)codes, partials,
                               nullptr, st, dtype);
-    if (rc) return hip_rc(rc, "vq_assign_exact_x16");
+    if (rc) return hip_rc(rc, x16 ? "vq_assign_exact_x16" : "vq_assign_exact");
     if (loss) {
         rc = dvq_launch_loss_finalize(partials, (int)((N + 127) / 128), 1.0 / ((double)N * D), beta, loss, st);
         if (rc) return hip_rc(rc, "vq_loss_finalize");
     }
     return DVQ_OK;
+}
+
+int dvq_vq_assign_nchw_f32(const float *z, const float *codebook, const void *prep,
+                           const float *mask, int B, int D, int HW, int K, float beta,
+                           float *zq, int64_t *codes, float *loss,
+                           void *ws, size_t ws_bytes, int mode, void *stream)
+{
+    return assign_nchw("dvq_vq_assign_nchw_f32", 0, z, codebook, prep, mask, B, D, HW, K, beta, zq, codes, loss, ws, ws_bytes, mode, stream);
+}
+
+int dvq_vq_assign_nchw_x16(const void *z, int dtype, const float *codebook, const void *prep, const float *mask,
+                           int B, int D, int HW, int K, float beta, void *zq, int64_t *codes, float *loss,
+                           void *ws, size_t ws_bytes, int mode, void *stream)
+{
+    const char *fn = "dvq_vq_assign_nchw_x16";
+    if (int rc = check_x16_dtype(fn, dtype)) return rc;
+    return assign_nchw(fn, dtype, z, codebook, prep, mask, B, D, HW, K, beta, zq, codes, loss, ws, ws_bytes, mode, stream);
 }
 
 // row-major latents: the same op on [N, D, 1] (the filter path reads / writes a token's row with 16-byte accesses when HW == 1)
@@ -333,8 +228,8 @@ int dvq_vq_assign_qconv_f32(const float *x, const void *qconv_prep, const float 
                             void *ws, size_t ws_bytes, int mode, void *stream)
 {
     const char *fn = "dvq_vq_assign_qconv_f32";
-    if (!x || !codebook || !prep || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
-    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
+    if (!x || !codebook || !prep || !codes) return null_pointer(fn);
+    if (int rc = check_positive(fn, B, HW, K)) return rc;
     const bool ws_clean = (mode & DVQ_MODE_WS_CLEAN) != 0;
     mode &= ~DVQ_MODE_WS_CLEAN;
     const bool pass1_only = (mode == DVQ_MODE_FILTER_PASS1);
@@ -343,13 +238,9 @@ int dvq_vq_assign_qconv_f32(const float *x, const void *qconv_prep, const float 
     int rc = conv_desc(fn, qconv_prep, h_buf, h_all, D, &cv);
     if (rc) return rc;
     const long N = (long)B * HW;
-    if (N >= (1L << 31) || (size_t)N * D >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_size(fn, (size_t)N, true, D)) return rc;
     if (!dvq_filter_supported(D, HW, K, N)) { dvq_set_error("%s: shape unsupported by the filter path (D=%d HW=%d K=%d: K < 2^20, D * HW < 2^29)", fn, D, HW, K); return DVQ_EUNSUPPORTED; }
-    if (!ws || ws_bytes < dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_FILTER)) {
-        dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_FILTER));
-        return DVQ_EWORKSPACE;
-    }
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_FILTER))) return rc;
     double *partials = loss ? (double *)ws : nullptr;
     rc = dvq_launch_filter(x, prep, codebook, mask, D, HW, K, N, zq, (long long *)codes, partials,
                            (char *)ws + partials_bytes_for(N), pass1_only, false, loss, beta, nullptr, (hipStream_t)stream, &cv, nullptr, ws_clean);
@@ -381,7 +272,7 @@ int dvq_fold_prepare_f32(const float *codebook, int K, int D, const void *codebo
 {
     const char *fn = "dvq_fold_prepare_f32";
     if (!codebook || !codebook_prep || !conv_weight || !fold_prep || K <= 0) { dvq_set_error("%s: null pointer or K <= 0", fn); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_width(fn, D)) return rc;
     if (fold_prep_bytes < dvq_fold_prep_bytes(K, D)) { dvq_set_error("%s: fold_prep buffer %zu < %zu bytes", fn, fold_prep_bytes, dvq_fold_prep_bytes(K, D)); return DVQ_EWORKSPACE; }
     if (((uintptr_t)fold_prep & 255) != 0 || ((uintptr_t)codebook_prep & 255) != 0) { dvq_set_error("%s: prep buffers must be 256-byte aligned", fn); return DVQ_EINVAL; }
     return hip_rc(dvq_launch_fold_prep(codebook, K, D, codebook_prep, conv_weight, conv_bias, fold_prep, (hipStream_t)stream), fn);
@@ -394,20 +285,16 @@ int dvq_vq_assign_fold_f32(const float *x, const void *qconv_prep, const void *f
     const char *fn = "dvq_vq_assign_fold_f32";
     const bool ws_clean = (mode & DVQ_MODE_WS_CLEAN) != 0;
     mode &= ~DVQ_MODE_WS_CLEAN;
-    if (!x || !codebook || !prep || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
-    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    if (!x || !codebook || !prep || !codes) return null_pointer(fn);
+    if (int rc = check_positive(fn, B, HW, K)) return rc;
+    if (int rc = check_width(fn, D)) return rc;
     DvqFold fd;
     int rc = fold_desc(fn, qconv_prep, fold_prep, D, &fd);
     if (rc) return rc;
     const long N = (long)B * HW;
-    if (N >= (1L << 31) || (size_t)N * D >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_size(fn, (size_t)N, true, D)) return rc;
     if (!dvq_filter_supported(D, HW, K, N)) { dvq_set_error("%s: shape unsupported by the filter path (D=%d HW=%d K=%d: K < 2^20, D * HW < 2^29)", fn, D, HW, K); return DVQ_EUNSUPPORTED; }
-    if (!ws || ws_bytes < dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_FILTER)) {
-        dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_FILTER));
-        return DVQ_EWORKSPACE;
-    }
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_FILTER))) return rc;
     if (mode != DVQ_MODE_FILTER && mode != DVQ_MODE_FILTER_PASS1) { dvq_set_error("%s: mode %d (the fold is a form of the filter path)", fn, mode); return DVQ_EINVAL; }
     rc = dvq_launch_filter(x, prep, codebook, nullptr, D, HW, K, N, zq, (long long *)codes, nullptr,
                            (char *)ws + partials_bytes_for(N), mode == DVQ_MODE_FILTER_PASS1, false, nullptr, 0.0f, nullptr,
@@ -451,12 +338,12 @@ static int routed_common(const char *fn, int nb, const void *gate, int gate_kind
                          const void *fold_prep = nullptr)
 {
     if (!gate || !h_coarse || !h_fine || !codebook || !prep || !codes || !indices || !cmask || (nb == 3 && !h_median)) {
-        dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL;
+        return null_pointer(fn);
     }
     if (B <= 0 || hc <= 0 || wc <= 0 || K <= 0) { dvq_set_error("%s: B=%d hc=%d wc=%d K=%d must be positive", fn, B, hc, wc, K); return DVQ_EINVAL; }
     if (gate_kind != DVQ_GATE_F32 && gate_kind != DVQ_GATE_I64 && gate_kind != DVQ_GATE_ENTROPY) { dvq_set_error("%s: gate_kind %d", fn, gate_kind); return DVQ_EINVAL; }
     if (gate_kind == DVQ_GATE_ENTROPY && nb != 2) { dvq_set_error("%s: the entropy gate is a dual-granularity router", fn); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_width(fn, D)) return rc;
     int SC;
     if (!routed_dims(nb, hc, wc, &SC)) { dvq_set_error("%s: hc*wc=%ld exceeds %d coarse cells", fn, (long)hc * wc, DVQ_ROUTE_MAX_CELLS_ABI); return DVQ_EUNSUPPORTED; }
     const bool ws_clean = (mode & DVQ_MODE_WS_CLEAN) != 0;
@@ -479,11 +366,7 @@ static int routed_common(const char *fn, int nb, const void *gate, int gate_kind
     const long N = (long)B * SC * hc * SC * wc;
     if (N >= (1L << 31) || (size_t)N * D >= ((size_t)1 << 40) || B > 32768) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
     if (!dvq_filter_supported(D, SC * hc * SC * wc, K, N)) { dvq_set_error("%s: shape unsupported by the filter path (D=%d HW=%d K=%d: K < 2^20, D * HW < 2^29)", fn, D, SC * hc * SC * wc, K); return DVQ_EUNSUPPORTED; }
-    if (!ws || ws_bytes < dvq_vq_assign_routed_workspace_bytes(nb, B, D, hc, wc, K, mode)) {
-        dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, dvq_vq_assign_routed_workspace_bytes(nb, B, D, hc, wc, K, mode));
-        return DVQ_EWORKSPACE;
-    }
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_vq_assign_routed_workspace_bytes(nb, B, D, hc, wc, K, mode))) return rc;
     hipStream_t st = (hipStream_t)stream;
     double *partials = loss ? (double *)ws : nullptr;
     const size_t pbytes = partials_bytes_for(routed_ids(nb, B, N));
@@ -576,18 +459,25 @@ int dvq_vq_assign_routed_fold_triple_f32(const void *gate, int gate_kind,
                          nullptr, 0, false, fold_prep);
 }
 
-int dvq_vq_backward_nchw_f32(const float *z, const float *codebook, const int64_t *codes, const float *mask,
-                             const float *g_zq, const float *g_loss, float coef_scale,
-                             int B, int D, int HW, int K, float *g_z, void *stream)
+// dtype 0: float32 z, g_zq and g_z; DVQ_DTYPE_F16 / DVQ_DTYPE_BF16: all three of that type
+static int backward_nchw(const char *fn, int dtype, const void *z, const float *codebook, const int64_t *codes, const float *mask,
+                         const void *g_zq, const float *g_loss, float coef_scale, int B, int D, int HW, int K, void *g_z, void *stream)
 {
-    const char *fn = "dvq_vq_backward_nchw_f32";
-    if (!z || !codebook || !codes || !g_z) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!z || !codebook || !codes || !g_z) return null_pointer(fn);
     if (!g_zq && !g_loss) { dvq_set_error("%s: neither g_zq nor g_loss given", fn); return DVQ_EINVAL; }
     if (B <= 0 || HW <= 0 || K <= 0 || D <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     if (D % 16 != 0) { dvq_set_error("%s: D=%d must be a multiple of 16", fn, D); return DVQ_EUNSUPPORTED; }
     if ((((uintptr_t)codebook) & 15) != 0) { dvq_set_error("%s: codebook must be 16-byte aligned", fn); return DVQ_EINVAL; }
-    return hip_rc(dvq_launch_vq_backward_z(z, codebook, (const long long *)codes, mask, g_zq, g_loss, coef_scale, D, HW, K,
+    if (dtype != 0 && (((uintptr_t)z | (uintptr_t)g_zq | (uintptr_t)g_z) & 1) != 0) { dvq_set_error("%s: z, g_zq and g_z must be 2-byte aligned", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_vq_backward_z(z, dtype, codebook, (const long long *)codes, mask, g_zq, g_loss, coef_scale, D, HW, K,
                                            (long)B * HW, g_z, (hipStream_t)stream), fn);
+}
+
+int dvq_vq_backward_nchw_f32(const float *z, const float *codebook, const int64_t *codes, const float *mask,
+                             const float *g_zq, const float *g_loss, float coef_scale,
+                             int B, int D, int HW, int K, float *g_z, void *stream)
+{
+    return backward_nchw("dvq_vq_backward_nchw_f32", 0, z, codebook, codes, mask, g_zq, g_loss, coef_scale, B, D, HW, K, g_z, stream);
 }
 
 int dvq_vq_backward_nchw_x16(const void *z, int dtype, const float *codebook, const int64_t *codes, const float *mask,
@@ -595,15 +485,8 @@ int dvq_vq_backward_nchw_x16(const void *z, int dtype, const float *codebook, co
                              void *g_z, void *stream)
 {
     const char *fn = "dvq_vq_backward_nchw_x16";
-    if (dtype != DVQ_DTYPE_F16 && dtype != DVQ_DTYPE_BF16) { dvq_set_error("%s: dtype %d (DVQ_DTYPE_F16 = 1, DVQ_DTYPE_BF16 = 2)", fn, dtype); return DVQ_EINVAL; }
-    if (!z || !codebook || !codes || !g_z) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
-    if (!g_zq && !g_loss) { dvq_set_error("%s: neither g_zq nor g_loss given", fn); return DVQ_EINVAL; }
-    if (B <= 0 || HW <= 0 || K <= 0 || D <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
-    if (D % 16 != 0) { dvq_set_error("%s: D=%d must be a multiple of 16", fn, D); return DVQ_EUNSUPPORTED; }
-    if ((((uintptr_t)codebook) & 15) != 0) { dvq_set_error("%s: codebook must be 16-byte aligned", fn); return DVQ_EINVAL; }
-    if ((((uintptr_t)z | (uintptr_t)g_zq | (uintptr_t)g_z) & 1) != 0) { dvq_set_error("%s: z, g_zq and g_z must be 2-byte aligned", fn); return DVQ_EINVAL; }
-    return hip_rc(dvq_launch_vq_backward_z_x16(z, dtype, codebook, (const long long *)codes, mask, g_zq, g_loss, coef_scale, D, HW, K,
-                                               (long)B * HW, g_z, (hipStream_t)stream), fn);
+    if (int rc = check_x16_dtype(fn, dtype)) return rc;
+    return backward_nchw(fn, dtype, z, codebook, codes, mask, g_zq, g_loss, coef_scale, B, D, HW, K, g_z, stream);
 }
 
 int dvq_vq_backward_codebook_nchw_f32(const float *z, const float *codebook, const int64_t *codes, const float *mask,
@@ -611,7 +494,7 @@ int dvq_vq_backward_codebook_nchw_f32(const float *z, const float *codebook, con
                                       float *g_weight, void *stream)
 {
     const char *fn = "dvq_vq_backward_codebook_nchw_f32";
-    if (!z || !codebook || !codes || !g_loss || !g_weight) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!z || !codebook || !codes || !g_loss || !g_weight) return null_pointer(fn);
     if (B <= 0 || HW <= 0 || K <= 0 || D <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     if (K > 8192) { dvq_set_error("%s: K=%d > 8192 (index_add the differences instead)", fn, K); return DVQ_EUNSUPPORTED; }
     return hip_rc(dvq_launch_codebook_grad(z, codebook, (const long long *)codes, mask, g_loss, coef_scale, D, HW, (long)B * HW, K,
@@ -621,7 +504,7 @@ int dvq_vq_backward_codebook_nchw_f32(const float *z, const float *codebook, con
 int dvq_embed_gather_f32(const float *codebook, int K, int D, const int64_t *idx, int64_t n,
                          float *out, void *stream)
 {
-    if (!codebook || !idx || !out) { dvq_set_error("dvq_embed_gather_f32: null pointer"); return DVQ_EINVAL; }
+    if (!codebook || !idx || !out) return null_pointer("dvq_embed_gather_f32");
     if (K <= 0 || D <= 0 || n < 0) { dvq_set_error("dvq_embed_gather_f32: bad sizes"); return DVQ_EINVAL; }
     if (D % 4 != 0) { dvq_set_error("dvq_embed_gather_f32: D=%d must be a multiple of 4", D); return DVQ_EUNSUPPORTED; }
     if (n == 0) return DVQ_OK;
@@ -630,7 +513,7 @@ int dvq_embed_gather_f32(const float *codebook, int K, int D, const int64_t *idx
 
 int dvq_entropy_gate_f32(const float *entropy, int64_t n, float thr, int64_t *gate, void *stream)
 {
-    if (!entropy || !gate) { dvq_set_error("dvq_entropy_gate_f32: null pointer"); return DVQ_EINVAL; }
+    if (!entropy || !gate) return null_pointer("dvq_entropy_gate_f32");
     if (n < 0) { dvq_set_error("dvq_entropy_gate_f32: n < 0"); return DVQ_EINVAL; }
     if (n == 0) return DVQ_OK;
     return hip_rc(dvq_launch_entropy_gate(entropy, (long)n, thr, (long long *)gate, (hipStream_t)stream), "entropy_gate");
@@ -639,7 +522,7 @@ int dvq_entropy_gate_f32(const float *entropy, int64_t n, float thr, int64_t *ga
 static int route_args_ok(const char *fn, const void *gate, int gate_dtype, const float *a, const float *b,
                          int B, int C, int hc, int wc, float *h_out, int64_t *indices, float *cmask)
 {
-    if (!gate || !a || !b || !h_out || !indices || !cmask) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!gate || !a || !b || !h_out || !indices || !cmask) return null_pointer(fn);
     if (gate_dtype != DVQ_GATE_F32 && gate_dtype != DVQ_GATE_I64) { dvq_set_error("%s: gate_dtype %d", fn, gate_dtype); return DVQ_EINVAL; }
     if (B <= 0 || C <= 0 || hc <= 0 || wc <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     return DVQ_OK;
@@ -678,31 +561,34 @@ int dvq_route_select_triple_f32(const void *gate, int gate_dtype, const float *h
                                           h_out, (long long *)indices, cmask, 0.0f, nullptr, (hipStream_t)stream), "route_select_triple");
 }
 
+static int ema_accumulate_nchw(const char *fn, int dtype, const void *z, const int64_t *codes, int B, int D, int HW, int K,
+                               float *cluster_size, float *vectors_sum, void *stream)
+{
+    if (!z || !codes || !cluster_size || !vectors_sum) return null_pointer(fn);
+    if (dtype != 0 && ((uintptr_t)z & 1) != 0) { dvq_set_error("%s: z must be 2-byte aligned", fn); return DVQ_EINVAL; }
+    if (B <= 0 || D <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_ema_accumulate(z, dtype, (const long long *)codes, D, HW, (long)B * HW, K, cluster_size, vectors_sum,
+                                            (hipStream_t)stream), dtype != 0 ? fn : "ema_accumulate");
+}
+
 int dvq_ema_accumulate_nchw_f32(const float *z, const int64_t *codes, int B, int D, int HW, int K,
                                 float *cluster_size, float *vectors_sum, void *stream)
 {
-    if (!z || !codes || !cluster_size || !vectors_sum) { dvq_set_error("dvq_ema_accumulate_nchw_f32: null pointer"); return DVQ_EINVAL; }
-    if (B <= 0 || D <= 0 || HW <= 0 || K <= 0) { dvq_set_error("dvq_ema_accumulate_nchw_f32: sizes must be positive"); return DVQ_EINVAL; }
-    return hip_rc(dvq_launch_ema_accumulate(z, (const long long *)codes, D, HW, (long)B * HW, K, cluster_size, vectors_sum,
-                                            (hipStream_t)stream), "ema_accumulate");
+    return ema_accumulate_nchw("dvq_ema_accumulate_nchw_f32", 0, z, codes, B, D, HW, K, cluster_size, vectors_sum, stream);
 }
 
 int dvq_ema_accumulate_nchw_x16(const void *z, int dtype, const int64_t *codes, int B, int D, int HW, int K,
                                 float *cluster_size, float *vectors_sum, void *stream)
 {
     const char *fn = "dvq_ema_accumulate_nchw_x16";
-    if (dtype != DVQ_DTYPE_F16 && dtype != DVQ_DTYPE_BF16) { dvq_set_error("%s: dtype %d (DVQ_DTYPE_F16 = 1, DVQ_DTYPE_BF16 = 2)", fn, dtype); return DVQ_EINVAL; }
-    if (!z || !codes || !cluster_size || !vectors_sum) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
-    if (((uintptr_t)z & 1) != 0) { dvq_set_error("%s: z must be 2-byte aligned", fn); return DVQ_EINVAL; }
-    if (B <= 0 || D <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
-    return hip_rc(dvq_launch_ema_accumulate_x16(z, dtype, (const long long *)codes, D, HW, (long)B * HW, K, cluster_size, vectors_sum,
-                                                (hipStream_t)stream), fn);
+    if (int rc = check_x16_dtype(fn, dtype)) return rc;
+    return ema_accumulate_nchw(fn, dtype, z, codes, B, D, HW, K, cluster_size, vectors_sum, stream);
 }
 
 int dvq_code_stats_f32(const int64_t *codes, int64_t N, int K, int64_t *counts, int64_t *n_used, float *perplexity, float *onehot,
                        void *stream)
 {
-    if (!counts || !n_used || !perplexity || (!codes && N > 0)) { dvq_set_error("dvq_code_stats_f32: null pointer"); return DVQ_EINVAL; }
+    if (!counts || !n_used || !perplexity || (!codes && N > 0)) return null_pointer("dvq_code_stats_f32");
     if (K < 1 || N < 0) { dvq_set_error("dvq_code_stats_f32: K=%d N=%lld (K >= 1, N >= 0)", K, (long long)N); return DVQ_EINVAL; }
     if (K >= (1 << 20)) { dvq_set_error("dvq_code_stats_f32: K=%d (K < 2^20)", K); return DVQ_EUNSUPPORTED; }
     return hip_rc(dvq_launch_code_stats((const long long *)codes, (long)N, K, (long long *)counts, (long long *)n_used, perplexity, onehot,
@@ -713,7 +599,7 @@ int dvq_code_stats_grain_f32(const int64_t *codes, const int64_t *grain, int B, 
                              int64_t *counts, int64_t *n_tokens, int64_t *n_used, float *perplexity, void *stream)
 {
     const char *fn = "dvq_code_stats_grain_f32";
-    if (!codes || !grain || !counts || !n_tokens || !n_used || !perplexity) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!codes || !grain || !counts || !n_tokens || !n_used || !perplexity) return null_pointer(fn);
     if (B < 1 || hc < 1 || wc < 1 || K < 1 || (G != 2 && G != 3)) { dvq_set_error("%s: B=%d hc=%d wc=%d K=%d G=%d (sizes >= 1, G 2 or 3)", fn, B, hc, wc, K, G); return DVQ_EINVAL; }
     const int S = 1 << (G - 1);
     if (hc > (1 << 20) || wc > (1 << 20) || H != hc * S || W != wc * S) {
@@ -726,7 +612,7 @@ int dvq_code_stats_grain_f32(const int64_t *codes, const int64_t *grain, int B, 
 
 int dvq_restart_pick_i64(uint64_t seed, int64_t n, int k, int64_t *out, void *stream)
 {
-    if (!out) { dvq_set_error("dvq_restart_pick_i64: null pointer"); return DVQ_EINVAL; }
+    if (!out) return null_pointer("dvq_restart_pick_i64");
     if (k < 1 || k > 2048 || n < 16 * (int64_t)k || n > 0xFFFFFFFFll) {
         dvq_set_error("dvq_restart_pick_i64: k=%d n=%lld (1 <= k <= 2048, 16 k <= n < 2^32)", k, (long long)n); return DVQ_EUNSUPPORTED;
     }
@@ -737,7 +623,7 @@ int dvq_ema_update_f32(const float *stats_sum, const float *stats_count, float d
                        const float *cluster_size_ema, float *cluster_size_out, float *embed_ema, float *weight,
                        int restart, const float *restart_rows, const float *z, int B, int HW, const int64_t *pick, void *stream)
 {
-    if (!stats_sum || !stats_count || !cluster_size_ema || !cluster_size_out || !embed_ema || !weight) { dvq_set_error("dvq_ema_update_f32: null pointer"); return DVQ_EINVAL; }
+    if (!stats_sum || !stats_count || !cluster_size_ema || !cluster_size_out || !embed_ema || !weight) return null_pointer("dvq_ema_update_f32");
     if (K <= 0 || D <= 0) { dvq_set_error("dvq_ema_update_f32: sizes must be positive"); return DVQ_EINVAL; }
     if (cluster_size_out == cluster_size_ema) { dvq_set_error("dvq_ema_update_f32: cluster_size_out must not alias cluster_size_ema (every workgroup sums the OLD counts)"); return DVQ_EINVAL; }
     if (restart < 0 || restart > 2) { dvq_set_error("dvq_ema_update_f32: restart must be 0, 1 or 2"); return DVQ_EINVAL; }
@@ -796,7 +682,7 @@ int dvq_router_gate_f32(int nb, const float *h_coarse, const float *h_median, co
 {
     const char *fn = "dvq_router_gate_f32";
     if (nb != 2 && nb != 3) { dvq_set_error("%s: num_branches=%d (2 or 3)", fn, nb); return DVQ_EINVAL; }
-    if (!h_coarse || !h_fine || !w2 || !b2 || !gate) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!h_coarse || !h_fine || !w2 || !b2 || !gate) return null_pointer(fn);
     if ((nb == 3) != (h_median != nullptr)) { dvq_set_error("%s: h_median must be given exactly when num_branches == 3", fn); return DVQ_EINVAL; }
     if (B <= 0 || C <= 0 || hc <= 0 || wc <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     if (activation != DVQ_ACT_NONE && activation != DVQ_ACT_SILU && activation != DVQ_ACT_RELU) { dvq_set_error("%s: unknown activation %d", fn, activation); return DVQ_EINVAL; }
@@ -807,11 +693,7 @@ int dvq_router_gate_f32(int nb, const float *h_coarse, const float *h_median, co
     }
     if (C % 8 != 0 || nb * C > 1280) { dvq_set_error("%s: C=%d unsupported (C %% 8 == 0, num_branches*C <= 1280)", fn, C); return DVQ_EUNSUPPORTED; }
     if (num_groups > 0 && ((size_t)(C / num_groups) * hc * wc) % 4 != 0) { dvq_set_error("%s: group size not a multiple of 4 floats", fn); return DVQ_EUNSUPPORTED; }
-    if (!ws || ws_bytes < dvq_router_gate_workspace_bytes(nb, B, C, hc, wc, num_groups, hidden)) {
-        dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, dvq_router_gate_workspace_bytes(nb, B, C, hc, wc, num_groups, hidden));
-        return DVQ_EWORKSPACE;
-    }
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_router_gate_workspace_bytes(nb, B, C, hc, wc, num_groups, hidden))) return rc;
     const float *h[3], *gw[3], *gb[3];
     if (nb == 2) {
         h[0] = h_coarse; h[1] = h_fine; h[2] = nullptr;
@@ -835,7 +717,7 @@ static int route_train_args(const char *fn, DvqRouteTrain *a, int nb, const floa
                             const float *b2, int hidden, int activation, const float *gumbels, float tau, void *ws, size_t ws_bytes)
 {
     if (nb != 2 && nb != 3) { dvq_set_error("%s: num_branches=%d (2 or 3)", fn, nb); return DVQ_EINVAL; }
-    if (!h_coarse || !h_fine || !w2 || !b2) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!h_coarse || !h_fine || !w2 || !b2) return null_pointer(fn);
     if ((nb == 3) != (h_median != nullptr)) { dvq_set_error("%s: h_median must be given exactly when num_branches == 3", fn); return DVQ_EINVAL; }
     if (B <= 0 || C <= 0 || hc <= 0 || wc <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     if (activation != DVQ_ACT_NONE && activation != DVQ_ACT_SILU && activation != DVQ_ACT_RELU) { dvq_set_error("%s: unknown activation %d", fn, activation); return DVQ_EINVAL; }
@@ -849,9 +731,7 @@ static int route_train_args(const char *fn, DvqRouteTrain *a, int nb, const floa
     const int S = nb == 2 ? 2 : 4;
     if (C % 8 != 0 || nb * C > 1280 || hidden > 1280) { dvq_set_error("%s: C=%d hidden=%d unsupported (C %% 8 == 0, num_branches*C <= 1280, hidden <= 1280)", fn, C, hidden); return DVQ_EUNSUPPORTED; }
     if ((long)S * wc > 4096 || (double)B * C * S * hc * S * wc >= 2147483648.0) { dvq_set_error("%s: grid %dx%d x B=%d too large", fn, hc, wc, B); return DVQ_EUNSUPPORTED; }
-    const size_t need = dvq_route_train_ws_bytes(nb, B, C, hc, wc, num_groups, hidden);
-    if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, need); return DVQ_EWORKSPACE; }
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_route_train_ws_bytes(nb, B, C, hc, wc, num_groups, hidden))) return rc;
     *a = DvqRouteTrain{};
     a->nb = nb; a->B = B; a->C = C; a->hc = hc; a->wc = wc; a->groups = num_groups; a->eps = eps;
     const float *hs[3] = {h_coarse, nb == 3 ? h_median : h_fine, h_fine};
@@ -929,7 +809,7 @@ int dvq_route_train_backward_f32(int nb, const float *h_coarse, const float *h_m
 
 int dvq_entropy_map_f32(const float *images, int B, int H, int W, int patch, float *out, void *stream)
 {
-    if (!images || !out) { dvq_set_error("dvq_entropy_map_f32: null pointer"); return DVQ_EINVAL; }
+    if (!images || !out) return null_pointer("dvq_entropy_map_f32");
     if (B <= 0 || H <= 0 || W <= 0) { dvq_set_error("dvq_entropy_map_f32: sizes must be positive"); return DVQ_EINVAL; }
     if (patch != 16 || H % 16 != 0 || W % 16 != 0) { dvq_set_error("dvq_entropy_map_f32: patch=%d H=%d W=%d (patch 16, H and W multiples of 16)", patch, H, W); return DVQ_EUNSUPPORTED; }
     if ((long)B * (H / 16) * (W / 16) >= (1L << 30)) { dvq_set_error("dvq_entropy_map_f32: %ld patches (at most 2^30 per call)", (long)B * (H / 16) * (W / 16)); return DVQ_EUNSUPPORTED; }
@@ -946,7 +826,7 @@ static int perm_dims_ok(const char *fn, int B, int hc, int wc)
 int dvq_permute_dual_count_i64(const int64_t *grain, int B, int hc, int wc, int32_t *counts, int32_t *maxes,
                                void *stream)
 {
-    if (!grain || !counts || !maxes) { dvq_set_error("dvq_permute_dual_count_i64: null pointer"); return DVQ_EINVAL; }
+    if (!grain || !counts || !maxes) return null_pointer("dvq_permute_dual_count_i64");
     int rc = perm_dims_ok("dvq_permute_dual_count_i64", B, hc, wc);
     if (rc) return rc;
     return hip_rc(dvq_launch_permute_count((const long long *)grain, B, hc * wc, counts, maxes, (hipStream_t)stream), "permute_count");
@@ -959,7 +839,7 @@ int dvq_permute_dual_forward_i64(const int64_t *codes, const int64_t *grain, int
                                  void *stream)
 {
     if (!codes || !grain || !special || !coarse_content || !coarse_position || !coarse_segment || !fine_content ||
-        !fine_position || !fine_segment) { dvq_set_error("dvq_permute_dual_forward_i64: null pointer"); return DVQ_EINVAL; }
+        !fine_position || !fine_segment) return null_pointer("dvq_permute_dual_forward_i64");
     int rc = perm_dims_ok("dvq_permute_dual_forward_i64", B, hc, wc);
     if (rc) return rc;
     if (order != 0 && order != 1) { dvq_set_error("dvq_permute_dual_forward_i64: order %d (0 region-first, 1 row-first)", order); return DVQ_EINVAL; }
@@ -977,7 +857,7 @@ int dvq_permute_dual_backward_i64(const int64_t *coarse_content, const int64_t *
                                   int64_t coarse_position_eos, int64_t fine_position_eos,
                                   int64_t *target, void *stream)
 {
-    if (!coarse_content || !fine_content || !coarse_position || !fine_position || !target) { dvq_set_error("dvq_permute_dual_backward_i64: null pointer"); return DVQ_EINVAL; }
+    if (!coarse_content || !fine_content || !coarse_position || !fine_position || !target) return null_pointer("dvq_permute_dual_backward_i64");
     int rc = perm_dims_ok("dvq_permute_dual_backward_i64", B, hc, wc);
     if (rc) return rc;
     if (Lc <= 0 || Lf <= 0) { dvq_set_error("dvq_permute_dual_backward_i64: Lc, Lf must be positive"); return DVQ_EINVAL; }
@@ -991,19 +871,18 @@ size_t dvq_qconv_prep_bytes(int D) { return dim_ok(D) ? dvq_qconv_prep_bytes_imp
 
 int dvq_qconv_prepare_f32(const float *weight, const float *bias, int D, void *prep, size_t prep_bytes, void *stream)
 {
-    if (!weight || !prep) { dvq_set_error("dvq_qconv_prepare_f32: null pointer"); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("dvq_qconv_prepare_f32: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", D); return DVQ_EUNSUPPORTED; }
-    if (prep_bytes < dvq_qconv_prep_bytes(D)) { dvq_set_error("dvq_qconv_prepare_f32: prep buffer %zu < %zu bytes", prep_bytes, dvq_qconv_prep_bytes(D)); return DVQ_EWORKSPACE; }
-    if (((uintptr_t)prep & 255) != 0) { dvq_set_error("dvq_qconv_prepare_f32: prep must be 256-byte aligned"); return DVQ_EINVAL; }
+    if (!weight || !prep) return null_pointer("dvq_qconv_prepare_f32");
+    if (int rc = check_width("dvq_qconv_prepare_f32", D)) return rc;
+    if (int rc = check_prep_buffer("dvq_qconv_prepare_f32", prep, prep_bytes, dvq_qconv_prep_bytes(D))) return rc;
     return hip_rc(dvq_launch_qconv_prep(weight, bias, D, prep, (hipStream_t)stream), "qconv_prep");
 }
 
 int dvq_qconv_f32(const float *x, const void *prep, int B, int D, int HW, float *h, void *stream)
 {
-    if (!x || !prep || !h) { dvq_set_error("dvq_qconv_f32: null pointer"); return DVQ_EINVAL; }
+    if (!x || !prep || !h) return null_pointer("dvq_qconv_f32");
     if (B <= 0 || HW <= 0) { dvq_set_error("dvq_qconv_f32: sizes must be positive"); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("dvq_qconv_f32: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", D); return DVQ_EUNSUPPORTED; }
-    if ((long)B * HW >= (1L << 31)) { dvq_set_error("dvq_qconv_f32: tensor too large"); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_width("dvq_qconv_f32", D)) return rc;
+    if (int rc = check_size("dvq_qconv_f32", (size_t)B * HW, true)) return rc;
     return hip_rc(dvq_launch_qconv(x, nullptr, prep, D, HW, (long)B * HW, h, (hipStream_t)stream), "qconv");
 }
 
@@ -1015,15 +894,15 @@ int dvq_qconv_select_f32(int num_branches, const void *gate, int gate_kind, floa
     const char *fn = "dvq_qconv_select_f32";
     if (num_branches != 2 && num_branches != 3) { dvq_set_error("%s: num_branches=%d (2 or 3)", fn, num_branches); return DVQ_EINVAL; }
     if (!gate || !h_coarse || !h_fine || !prep || !h || !indices || !cmask || (num_branches == 3 && !h_median)) {
-        dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL;
+        return null_pointer(fn);
     }
     if (B <= 0 || hc <= 0 || wc <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     if (gate_kind != DVQ_GATE_F32 && gate_kind != DVQ_GATE_I64 && gate_kind != DVQ_GATE_ENTROPY) { dvq_set_error("%s: gate_kind %d", fn, gate_kind); return DVQ_EINVAL; }
     if (gate_kind == DVQ_GATE_ENTROPY && num_branches != 2) { dvq_set_error("%s: the entropy gate is a dual-granularity router", fn); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_width(fn, D)) return rc;
     const int SC = (num_branches == 2) ? 2 : 4;
     const long N = (long)B * SC * hc * SC * wc;
-    if (N >= (1L << 31)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_size(fn, (size_t)N, true)) return rc;
     DvqRouted rv{};
     rv.G = num_branches; rv.B = B; rv.D = D; rv.hc = hc; rv.wc = wc; rv.Wout = SC * wc; rv.HWout = SC * hc * SC * wc;
     rv.gate = gate; rv.gate_mode = (gate_kind == DVQ_GATE_ENTROPY) ? 2 : (gate_kind == DVQ_GATE_I64 ? 1 : 0);
@@ -1041,7 +920,7 @@ int dvq_qconv_select_f32(int num_branches, const void *gate, int gate_kind, floa
 int dvq_debug_filter_scores_f32(const float *tokens, int n, const void *prep, int D, int K, float *scores,
                                 float *threshold, float *xn, float *scale, void *stream)
 {
-    if (!tokens || !prep || !scores || !threshold || !xn) { dvq_set_error("dvq_debug_filter_scores_f32: null pointer"); return DVQ_EINVAL; }
+    if (!tokens || !prep || !scores || !threshold || !xn) return null_pointer("dvq_debug_filter_scores_f32");
     if (n <= 0 || K <= 0) { dvq_set_error("dvq_debug_filter_scores_f32: n, K must be positive"); return DVQ_EINVAL; }
     if (!dim_ok(D)) { dvq_set_error("dvq_debug_filter_scores_f32: D=%d unsupported", D); return DVQ_EUNSUPPORTED; }
     return hip_rc(dvq_launch_filter_scores_debug(tokens, n, prep, D, K, scores, threshold, xn, scale, (hipStream_t)stream),
@@ -1051,7 +930,7 @@ int dvq_debug_filter_scores_f32(const float *tokens, int n, const void *prep, in
 int dvq_debug_fold_scores_f32(const float *tokens, int n, const void *fold_prep, int D, int K, float *scores,
                               float *threshold, float *xn, float *scale, void *stream)
 {
-    if (!tokens || !fold_prep || !scores || !threshold || !xn) { dvq_set_error("dvq_debug_fold_scores_f32: null pointer"); return DVQ_EINVAL; }
+    if (!tokens || !fold_prep || !scores || !threshold || !xn) return null_pointer("dvq_debug_fold_scores_f32");
     if (n <= 0 || K <= 0) { dvq_set_error("dvq_debug_fold_scores_f32: n, K must be positive"); return DVQ_EINVAL; }
     if (!dim_ok(D)) { dvq_set_error("dvq_debug_fold_scores_f32: D=%d unsupported", D); return DVQ_EUNSUPPORTED; }
     return hip_rc(dvq_launch_filter_scores_debug(tokens, n, fold_prep, D, K, scores, threshold, xn, scale, (hipStream_t)stream, 1),
@@ -1068,7 +947,7 @@ int dvq_exchange_pack(const int64_t *codes, const int64_t *grain, const float *l
                       int b_max, int64_t codes_per_image, int64_t grain_per_image, int num_codes, void *buf,
                       void *stream)
 {
-    if (!codes || !buf) { dvq_set_error("dvq_exchange_pack: null pointer"); return DVQ_EINVAL; }
+    if (!codes || !buf) return null_pointer("dvq_exchange_pack");
     if (b_local < 0 || b_max <= 0 || b_local > b_max || codes_per_image <= 0 || grain_per_image < 0 || num_codes <= 0) {
         dvq_set_error("dvq_exchange_pack: bad sizes"); return DVQ_EINVAL;
     }
@@ -1083,7 +962,7 @@ int dvq_exchange_unpack(const void *gathered, int world, int global_batch, int64
                         int64_t grain_per_image, int num_codes, int64_t *codes, int64_t *grain, float *mean,
                         void *stream)
 {
-    if (!gathered || !codes) { dvq_set_error("dvq_exchange_unpack: null pointer"); return DVQ_EINVAL; }
+    if (!gathered || !codes) return null_pointer("dvq_exchange_unpack");
     if (world <= 0 || global_batch <= 0 || codes_per_image <= 0 || grain_per_image < 0 || num_codes <= 0) {
         dvq_set_error("dvq_exchange_unpack: bad sizes"); return DVQ_EINVAL;
     }
@@ -1135,12 +1014,12 @@ int dvq_rq_step_f32(const float *x, const float *r, const float *codebook, int K
                     int64_t *codes, float *out, void *ws, size_t ws_bytes, void *stream)
 {
     const char *fn = "dvq_rq_step_f32";
-    if (!x || !r || !codebook || !code || !codes || !out || !ws) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!x || !r || !codebook || !code || !codes || !out || !ws) return null_pointer(fn);
     if (K <= 0) { dvq_set_error("%s: K=%d must be positive", fn, K); return DVQ_EINVAL; }
     const int rc = rq_geom_check(fn, B, h, w, rH, rW, Dl, D, depth);
     if (rc != DVQ_OK) return rc;
     if (i < 0 || i >= depth) { dvq_set_error("%s: i=%d outside [0, depth=%d)", fn, i, depth); return DVQ_EINVAL; }
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_ws_aligned(fn, ws)) return rc;
     const long N = (long)B * h * w;
     if (ws_bytes < rq_ws_bytes(N, D, depth, want_grad ? 1 : 0)) {
         dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, rq_ws_bytes(N, D, depth, want_grad ? 1 : 0)); return DVQ_EWORKSPACE;
@@ -1152,10 +1031,10 @@ int dvq_rq_step_f32(const float *x, const float *r, const float *codebook, int K
 int dvq_rq_loss_f32(int64_t N, int D, int depth, const void *ws, size_t ws_bytes, float *loss, void *stream)
 {
     const char *fn = "dvq_rq_loss_f32";
-    if (!ws || !loss) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!ws || !loss) return null_pointer(fn);
     if (N <= 0 || depth < 1 || depth > DVQ_RQ_MAX_DEPTH) { dvq_set_error("%s: N=%lld depth=%d out of range", fn, (long long)N, depth); return DVQ_EINVAL; }
     if (!rq_width_ok(D) || N * D >= ((int64_t)1 << 31)) { dvq_set_error("%s: D=%d unsupported", fn, D); return DVQ_EUNSUPPORTED; }
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_ws_aligned(fn, ws)) return rc;
     if (ws_bytes < rq_ws_bytes((long)N, D, depth, 0)) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws_bytes, rq_ws_bytes((long)N, D, depth, 0)); return DVQ_EWORKSPACE; }
     return hip_rc(dvq_launch_rq_loss((long)N, D, depth, ws, loss, (hipStream_t)stream), "rq_loss");
 }
@@ -1164,10 +1043,10 @@ int dvq_rq_backward_f32(const float *g_out, const float *g_loss, int B, int h, i
                         int depth, const void *ws, size_t ws_bytes, float *g_x, void *stream)
 {
     const char *fn = "dvq_rq_backward_f32";
-    if (!ws || !g_x) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!ws || !g_x) return null_pointer(fn);
     const int rc = rq_geom_check(fn, B, h, w, rH, rW, Dl, D, depth);
     if (rc != DVQ_OK) return rc;
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_ws_aligned(fn, ws)) return rc;
     const long N = (long)B * h * w;
     if (ws_bytes < rq_ws_bytes(N, D, depth, 1)) { dvq_set_error("%s: workspace %zu < %zu bytes (the want_grad workspace of the forward)", fn, ws_bytes, rq_ws_bytes(N, D, depth, 1)); return DVQ_EWORKSPACE; }
     return hip_rc(dvq_launch_rq_backward(g_out, g_loss, B, h, w, rH, rW, Dl, depth, ws, g_x, (hipStream_t)stream), "rq_backward");
@@ -1177,7 +1056,7 @@ int dvq_rq_embed_code_f32(const float *const *codebooks, const int *K, int depth
                           int B, int h, int w, int rH, int rW, int Dl, int D, int mode, int j, float *out, void *stream)
 {
     const char *fn = "dvq_rq_embed_code_f32";
-    if (!codebooks || !K || !codes || !out) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!codebooks || !K || !codes || !out) return null_pointer(fn);
     const int rc = rq_geom_check(fn, B, h, w, rH, rW, Dl, D, depth);
     if (rc != DVQ_OK) return rc;
     for (int t = 0; t < depth; ++t)
@@ -1195,7 +1074,7 @@ int dvq_sample_head_f32(const float *logits, int64_t logits_row_stride, int B, i
 {
     const char *fn = "dvq_sample_head_f32";
     if (!logits || !rules || !flag || !tokens || (sample && !q) || (history_len > 0 && !history)) {
-        dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL;
+        return null_pointer(fn);
     }
     if (B <= 0 || V <= 0) { dvq_set_error("%s: B=%d V=%d must be positive", fn, B, V); return DVQ_EINVAL; }
     if (V > dvq_sample_max_vocab()) { dvq_set_error("%s: V=%d exceeds %d", fn, V, dvq_sample_max_vocab()); return DVQ_EUNSUPPORTED; }
@@ -1220,7 +1099,7 @@ int dvq_sample_head_f32(const float *logits, int64_t logits_row_stride, int B, i
 
 static int transfer_args_ok(const char *fn, const int64_t *coarse_position, int64_t row_stride, int B, int Lc, int hc, int variant)
 {
-    if (!coarse_position) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!coarse_position) return null_pointer(fn);
     if (B <= 0 || Lc <= 0 || hc <= 0 || row_stride < Lc) { dvq_set_error("%s: B=%d Lc=%d hc=%d stride=%lld", fn, B, Lc, hc, (long long)row_stride); return DVQ_EINVAL; }
     if ((long)hc * hc > dvq_sample_max_cells()) { dvq_set_error("%s: hc*hc=%ld exceeds %d coarse cells", fn, (long)hc * hc, dvq_sample_max_cells()); return DVQ_EUNSUPPORTED; }
     if (variant != DVQ_TRANSFER_SAMPLED && variant != DVQ_TRANSFER_REMAIN) { dvq_set_error("%s: variant %d", fn, variant); return DVQ_EINVAL; }
@@ -1233,7 +1112,7 @@ int dvq_sample_transfer_count_i64(const int64_t *coarse_position, int64_t row_st
     const char *fn = "dvq_sample_transfer_count_i64";
     int rc = transfer_args_ok(fn, coarse_position, row_stride, B, Lc, hc, variant);
     if (rc) return rc;
-    if (!counts || !max_count) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!counts || !max_count) return null_pointer(fn);
     return hip_rc(dvq_launch_transfer_count((const long long *)coarse_position, row_stride, B, Lc, hc, coarse_position_eos,
                                             variant, counts, max_count, (hipStream_t)stream), "transfer_count");
 }
@@ -1245,7 +1124,7 @@ int dvq_sample_transfer_fill_i64(const int64_t *coarse_position, int64_t row_str
     const char *fn = "dvq_sample_transfer_fill_i64";
     int rc = transfer_args_ok(fn, coarse_position, row_stride, B, Lc, hc, variant);
     if (rc) return rc;
-    if (!out) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!out) return null_pointer(fn);
     if (order != 0 && order != 1) { dvq_set_error("%s: order %d (0 region-first, 1 row-first)", fn, order); return DVQ_EINVAL; }
     if (sos_mode < DVQ_TRANSFER_SOS_NONE || sos_mode > DVQ_TRANSFER_SOS_COPY) { dvq_set_error("%s: sos_mode %d", fn, sos_mode); return DVQ_EINVAL; }
     if (L < 1) { dvq_set_error("%s: L=%d must be positive", fn, L); return DVQ_EINVAL; }
@@ -1284,7 +1163,7 @@ int dvq_decode_head_f32(const int64_t *codes, int B, int HW, const float *table,
                         const float *pos_second, float *h_in, void *stream)
 {
     const char *fn = "dvq_decode_head_f32";
-    if (!codes || !table || !h_in) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!codes || !table || !h_in) return null_pointer(fn);
     if (B <= 0 || HW <= 0 || rows <= 0 || C <= 0) { dvq_set_error("%s: B=%d HW=%d rows=%d C=%d must be positive", fn, B, HW, rows, C); return DVQ_EINVAL; }
     if (C % 4 != 0 || C > DVQ_DECODE_MAX_C) { dvq_set_error("%s: C=%d must be a multiple of 4, at most %d", fn, C, DVQ_DECODE_MAX_C); return DVQ_EINVAL; }
     if ((size_t)B * HW >= ((size_t)1 << 31) - 64 || (size_t)B * HW * C >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EINVAL; }
@@ -1305,17 +1184,17 @@ int dvq_vq_soft_assign_flat_f32(const float *x, const float *codebook, const voi
                                 const float *q, float *soft, float *dist, int64_t *codes, void *ws, size_t ws_bytes, void *stream)
 {
     const char *fn = "dvq_vq_soft_assign_flat_f32";
-    if (!x || !codebook || !prep || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!x || !codebook || !prep || !codes) return null_pointer(fn);
     if (N <= 0 || N >= ((int64_t)1 << 31) || K <= 0) { dvq_set_error("%s: N=%lld K=%d out of range", fn, (long long)N, K); return DVQ_EINVAL; }
     if (!(temp > 0.0f) || !(temp < __builtin_inff())) { dvq_set_error("%s: temp=%g must be finite and positive", fn, (double)temp); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_width(fn, D)) return rc;
     if ((size_t)N * (size_t)K >= ((size_t)1 << 40)) { dvq_set_error("%s: N * K too large", fn); return DVQ_EUNSUPPORTED; }
     if ((((uintptr_t)x | (uintptr_t)q | (uintptr_t)soft | (uintptr_t)dist) & 3) != 0 || ((uintptr_t)prep & 255) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
     float *sbuf = soft;
     if (!soft && q) {                                            // the draw alone: the scores live in the workspace
         const size_t need = dvq_vq_soft_assign_workspace_bytes(N, D, K);
         if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes (soft == NULL with q)", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EINVAL; }
-        if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+        if (int rc = check_ws_aligned(fn, ws)) return rc;
         sbuf = (float *)ws;
     }
     return hip_rc(dvq_launch_soft_assign(x, (const float *)prep, D, K, (long)N, temp, q, soft, dist, sbuf, (long long *)codes,
@@ -1327,12 +1206,12 @@ int dvq_vq_score_assign_f32(const float *x, const void *prep, int B, int D, int 
                             const float *u, int64_t u_numel, int64_t *codes, void *stream)
 {
     const char *fn = "dvq_vq_score_assign_f32";
-    if (!x || !prep || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
-    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
+    if (!x || !prep || !codes) return null_pointer(fn);
+    if (int rc = check_positive(fn, B, HW, K)) return rc;
     if (metric != DVQ_METRIC_L2 && metric != DVQ_METRIC_DOT) { dvq_set_error("%s: unknown metric %d", fn, metric); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_width(fn, D)) return rc;
     const size_t N = (size_t)B * (size_t)HW;
-    if (N >= ((size_t)1 << 31) || N * (size_t)D >= ((size_t)1 << 40) || N * (size_t)K >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_size(fn, N, true, D, K)) return rc;
     if ((((uintptr_t)x | (uintptr_t)u) & 3) != 0 || ((uintptr_t)prep & 255) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
     if (u) {
         if (!(temp > 0.0f) || !(temp < __builtin_inff())) { dvq_set_error("%s: temp=%g must be finite and positive when u is given", fn, (double)temp); return DVQ_EINVAL; }
@@ -1346,18 +1225,16 @@ int dvq_vq_apply_codes_nchw_f32(const float *z, const int64_t *codes, const floa
                                 int K, float beta, float *zq, float *loss, void *ws, size_t ws_bytes, void *stream)
 {
     const char *fn = "dvq_vq_apply_codes_nchw_f32";
-    if (!z || !codes || !codebook) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
-    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
+    if (!z || !codes || !codebook) return null_pointer(fn);
+    if (int rc = check_positive(fn, B, HW, K)) return rc;
     if (D <= 0 || D % 16 != 0) { dvq_set_error("%s: D=%d must be a positive multiple of 16", fn, D); return DVQ_EUNSUPPORTED; }
     const size_t N = (size_t)B * (size_t)HW;
-    if (N >= ((size_t)1 << 31) || N * (size_t)D >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_size(fn, N, true, D)) return rc;
     if ((((uintptr_t)z | (uintptr_t)zq | (uintptr_t)mask) & 3) != 0 || ((uintptr_t)codebook & 15) != 0 || ((uintptr_t)codes & 7) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
     if (!zq && !loss) { dvq_set_error("%s: nothing to compute (zq and loss are both null)", fn); return DVQ_EINVAL; }
     double *partials = nullptr;
     if (loss) {
-        const size_t need = dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_EXACT);
-        if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EWORKSPACE; }
-        if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+        if (int rc = check_workspace(fn, ws, ws_bytes, dvq_vq_assign_workspace_bytes(B, D, HW, K, DVQ_MODE_EXACT), true)) return rc;
         partials = (double *)ws;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -1409,19 +1286,19 @@ int dvq_vq_gumbel_assign_f32(const float *z, const void *prep, const float *embe
                              float kl_K, const float *q, float *zq, int64_t *codes, float *kl, void *ws, size_t ws_bytes, void *stream)
 {
     const char *fn = "dvq_vq_gumbel_assign_f32";
-    if (!z || !prep || !embed || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!z || !prep || !embed || !codes) return null_pointer(fn);
     if (B <= 0 || HW <= 0 || K <= 0 || d <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d d=%d must be positive", fn, B, HW, K, d); return DVQ_EINVAL; }
     if (!dim_ok(C)) { dvq_set_error("%s: C=%d unsupported (kernel widths 64, 128, 256)", fn, C); return DVQ_EUNSUPPORTED; }
     if (q && (!(tau > 0.0f) || !(tau < __builtin_inff()))) { dvq_set_error("%s: tau=%g must be finite and positive when q is given", fn, (double)tau); return DVQ_EINVAL; }
     if (!(kl_K > 0.0f) || !(kl_K < __builtin_inff())) { dvq_set_error("%s: kl_K=%g must be finite and positive", fn, (double)kl_K); return DVQ_EINVAL; }
     const size_t N = (size_t)B * (size_t)HW;
-    if (N >= ((size_t)1 << 31) || N * (size_t)C >= ((size_t)1 << 40) || N * (size_t)K >= ((size_t)1 << 40) || N * (size_t)d >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_size(fn, N, true, C, K, d)) return rc;
     if ((((uintptr_t)z | (uintptr_t)embed | (uintptr_t)q | (uintptr_t)zq | (uintptr_t)kl) & 3) != 0 || ((uintptr_t)prep & 255) != 0 || ((uintptr_t)codes & 7) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
     double *partials = nullptr;
     if (kl) {
         const size_t need = dvq_vq_gumbel_assign_workspace_bytes(B, HW);
         if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes (kl is wanted)", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EINVAL; }
-        if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+        if (int rc = check_ws_aligned(fn, ws)) return rc;
         partials = (double *)ws;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -1456,7 +1333,7 @@ static int narrow_common(const char *fn, const float *z, const float *codebook, 
     if (loss) {
         const size_t need = dvq_vq_assign_narrow_workspace_bytes(N);
         if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes (loss is wanted)", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EINVAL; }
-        if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+        if (int rc = check_ws_aligned(fn, ws)) return rc;
         partials = (double *)ws;
     }
     hipStream_t st = (hipStream_t)stream;
@@ -1473,8 +1350,8 @@ int dvq_vq_assign_narrow_nchw_f32(const float *z, const float *codebook, const f
                                   float *zq, int64_t *codes, float *loss, void *ws, size_t ws_bytes, void *stream)
 {
     const char *fn = "dvq_vq_assign_narrow_nchw_f32";
-    if (!z || !codebook || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
-    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
+    if (!z || !codebook || !codes) return null_pointer(fn);
+    if (int rc = check_positive(fn, B, HW, K)) return rc;
     return narrow_common(fn, z, codebook, mask, (int64_t)B * HW, D, HW, K, false, beta, zq, codes, loss, ws, ws_bytes, stream);
 }
 
@@ -1482,7 +1359,7 @@ int dvq_vq_assign_narrow_flat_f32(const float *z, const float *codebook, const f
                                   float *zq, int64_t *codes, float *loss, void *ws, size_t ws_bytes, void *stream)
 {
     const char *fn = "dvq_vq_assign_narrow_flat_f32";
-    if (!z || !codebook || !codes) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!z || !codebook || !codes) return null_pointer(fn);
     if (N <= 0 || K <= 0) { dvq_set_error("%s: N=%lld K=%d must be positive", fn, (long long)N, K); return DVQ_EINVAL; }
     return narrow_common(fn, z, codebook, mask, N, D, 1, K, true, beta, zq, codes, loss, ws, ws_bytes, stream);
 }
@@ -1493,10 +1370,10 @@ int dvq_vq_cdist_sample_assign_f32(const float *x, const void *prep, int B, int 
 {
     const char *fn = "dvq_vq_cdist_sample_assign_f32";
     if (!x || !prep || !codes || !u) { dvq_set_error("%s: null pointer (u is required: temp == 0 is the plain assign)", fn); return DVQ_EINVAL; }
-    if (B <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d must be positive", fn, B, HW, K); return DVQ_EINVAL; }
-    if (!dim_ok(D)) { dvq_set_error("%s: D=%d unsupported (kernel widths 64, 128, 256; a multiple of 32 below 256 runs EXACTLY at the next width with zero channels appended to latents and codebook, as the Python drop-in does)", fn, D); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_positive(fn, B, HW, K)) return rc;
+    if (int rc = check_width(fn, D)) return rc;
     const size_t N = (size_t)B * (size_t)HW;
-    if (N >= ((size_t)1 << 31) || N * (size_t)D >= ((size_t)1 << 40) || N * (size_t)K >= ((size_t)1 << 40)) { dvq_set_error("%s: tensor too large", fn); return DVQ_EUNSUPPORTED; }
+    if (int rc = check_size(fn, N, true, D, K)) return rc;
     if ((((uintptr_t)x | (uintptr_t)u) & 3) != 0 || ((uintptr_t)prep & 255) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
     if (!(temp > 0.0f) || !(temp < __builtin_inff())) { dvq_set_error("%s: temp=%g must be finite and positive", fn, (double)temp); return DVQ_EINVAL; }
     if (u_numel < 0 || (size_t)u_numel != N * (size_t)K) { dvq_set_error("%s: u has %lld elements, expected N * K = %zu", fn, (long long)u_numel, N * (size_t)K); return DVQ_EINVAL; }
@@ -1525,13 +1402,11 @@ size_t dvq_ortho_loss_workspace_bytes(int h, int n, int d)
 int dvq_ortho_loss_forward_f32(const float *t, int h, int n, int d, float *rinv, float *loss, void *ws, size_t ws_bytes, void *stream)
 {
     const char *fn = "dvq_ortho_loss_forward_f32";
-    if (!t || !rinv || !loss) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!t || !rinv || !loss) return null_pointer(fn);
     if (!ortho_shape_ok(fn, h, n, d)) return DVQ_EINVAL;
     if (!dim_ok(d) || h > 65535 || n >= (1 << 24)) { dvq_set_error("%s: h=%d n=%d d=%d unsupported (d in 64, 128, 256; h < 2^16, n < 2^24)", fn, h, n, d); return DVQ_EUNSUPPORTED; }
     if (((uintptr_t)t & 15) != 0 || (((uintptr_t)rinv | (uintptr_t)loss) & 3) != 0) { dvq_set_error("%s: misaligned pointer (t: 16 bytes)", fn); return DVQ_EINVAL; }
-    const size_t need = dvq_ortho_loss_workspace_bytes(h, n, d);
-    if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EWORKSPACE; }
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_ortho_loss_workspace_bytes(h, n, d), true)) return rc;
     return hip_rc(dvq_launch_ortho_forward(t, h, n, d, rinv, loss, (double *)ws, (hipStream_t)stream), "ortho_loss_forward");
 }
 
@@ -1539,14 +1414,12 @@ int dvq_ortho_loss_backward_f32(const float *t, const float *rinv, const float *
                                 void *ws, size_t ws_bytes, void *stream)
 {
     const char *fn = "dvq_ortho_loss_backward_f32";
-    if (!t || !rinv || !grad_out || !grad) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!t || !rinv || !grad_out || !grad) return null_pointer(fn);
     if (!ortho_shape_ok(fn, h, n, d)) return DVQ_EINVAL;
     if (!dim_ok(d) || h > 65535 || n >= (1 << 24)) { dvq_set_error("%s: h=%d n=%d d=%d unsupported (d in 64, 128, 256; h < 2^16, n < 2^24)", fn, h, n, d); return DVQ_EUNSUPPORTED; }
     if ((((uintptr_t)t | (uintptr_t)grad) & 15) != 0 || (((uintptr_t)rinv | (uintptr_t)grad_out) & 3) != 0) { dvq_set_error("%s: misaligned pointer (t, grad: 16 bytes)", fn); return DVQ_EINVAL; }
     if (t == grad) { dvq_set_error("%s: grad must not alias t", fn); return DVQ_EINVAL; }
-    const size_t need = dvq_ortho_loss_workspace_bytes(h, n, d);
-    if (!ws || ws_bytes < need) { dvq_set_error("%s: workspace %zu < %zu bytes", fn, ws ? ws_bytes : (size_t)0, need); return DVQ_EWORKSPACE; }
-    if (((uintptr_t)ws & 255) != 0) { dvq_set_error("%s: workspace must be 256-byte aligned", fn); return DVQ_EINVAL; }
+    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_ortho_loss_workspace_bytes(h, n, d), true)) return rc;
     return hip_rc(dvq_launch_ortho_backward(t, rinv, grad_out, h, n, d, grad, (float *)ws, (hipStream_t)stream), "ortho_loss_backward");
 }
 
@@ -1556,7 +1429,7 @@ int dvq_lucid_update_f32(int kind, const float *counts, const float *sums, float
 {
     const char *fn = "dvq_lucid_update_f32";
     if (kind != 0 && kind != 1) { dvq_set_error("%s: kind must be 0 (Euclidean) or 1 (cosine), got %d", fn, kind); return DVQ_EINVAL; }
-    if (!counts || !cluster_size || !cluster_size_out || !embed) { dvq_set_error("%s: null pointer", fn); return DVQ_EINVAL; }
+    if (!counts || !cluster_size || !cluster_size_out || !embed) return null_pointer(fn);
     if (kind == 0 && !embed_avg) { dvq_set_error("%s: kind 0 needs embed_avg", fn); return DVQ_EINVAL; }
     if (kind == 1 && !sums) { dvq_set_error("%s: kind 1 needs sums", fn); return DVQ_EINVAL; }
     if (K <= 0 || D <= 0) { dvq_set_error("%s: K=%d D=%d must be positive", fn, K, D); return DVQ_EINVAL; }

@@ -13,7 +13,7 @@
 // end: 8 M instead of 67 M global atomics at B = 256) was built and measured in round 3: 370 us against this kernel's 288 --
 // a ds_add_f32 wave-instruction takes 192 cycles whatever its address pattern (tools/micro/lds_atomic_rate.hip: three
 // cycles per lane, 170 G adds/s over the chip, below the 233 G/s the L2 atomics reach here); profiles/archive/r03_ema_lds_negative.json.
-#include "dvq_common.h"
+#include "launchers.h"
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -367,9 +367,12 @@ __global__ __launch_bounds__(1024) void ema_accumulate_sorted_kernel(const float
     }
 }
 
-int dvq_launch_ema_accumulate(const float *z, const long long *codes, int D, int HW, long N, int K,
+// xt = 0: float32 latents, the sorted kernel where its shape conditions hold, else the tile-transpose kernel.  16-bit latents
+// (xt = DVQ_DTYPE_F16 / DVQ_DTYPE_BF16): always the tile-transpose kernel.  Equal codes of a tile are combined up to K = 8192.
+int dvq_launch_ema_accumulate(const void *zv, int xt, const long long *codes, int D, int HW, long N, int K,
                               float *cluster_size, float *vectors_sum, hipStream_t st)
 {
+    if (xt < 0 || xt > 2) return -1000;
     // zeroed by a kernel, not hipMemsetAsync: memset nodes misbehave under hipGraph replay on ROCm 7.2
     {
         size_t n = (size_t)K * D;
@@ -378,6 +381,20 @@ int dvq_launch_ema_accumulate(const float *z, const long long *codes, int D, int
         if (blocks < 1) blocks = 1;
         hipLaunchKernelGGL(ema_zero_kernel, dim3(blocks), dim3(256), 0, st, cluster_size, (size_t)K, vectors_sum, n);
     }
+    if (xt != 0) {
+        const dim3 grid((unsigned)((N + 63) / 64));
+        const bool combine = K <= 8192;
+        const size_t shm = combine ? (size_t)K * sizeof(int) : 0;
+        if (xt == 1) {
+            auto kernel = combine ? ema_accumulate_kernel<true, 1> : ema_accumulate_kernel<false, 1>;
+            hipLaunchKernelGGL(kernel, grid, dim3(256), shm, st, (const _Float16 *)zv, codes, D, HW, N, K, cluster_size, vectors_sum);
+        } else {
+            auto kernel = combine ? ema_accumulate_kernel<true, 2> : ema_accumulate_kernel<false, 2>;
+            hipLaunchKernelGGL(kernel, grid, dim3(256), shm, st, (const __bf16 *)zv, codes, D, HW, N, K, cluster_size, vectors_sum);
+        }
+        return (int)hipGetLastError();
+    }
+    const float *z = (const float *)zv;
     if (K <= 4096 && (HW & 3) == 0 && (D & 15) == 0 && N >= 32 * EMS_BT) {
         const size_t shm = (size_t)EMS_BC * EMS_STR * 4 + (size_t)EMS_BT * 6 + ((size_t)K + 1) * 4;
         int ncu = 256, dev = 0;
@@ -393,31 +410,6 @@ int dvq_launch_ema_accumulate(const float *z, const long long *codes, int D, int
     else
         hipLaunchKernelGGL(ema_accumulate_kernel<false>, dim3((unsigned)((N + 63) / 64)), dim3(256), 0, st, z, codes, D, HW, N, K,
                            cluster_size, vectors_sum);
-    return (int)hipGetLastError();
-}
-
-// 16-bit latents (xt = DVQ_DTYPE_F16 / DVQ_DTYPE_BF16): the tile-transpose kernel, equal codes combined up to K = 8192
-int dvq_launch_ema_accumulate_x16(const void *z, int xt, const long long *codes, int D, int HW, long N, int K,
-                                  float *cluster_size, float *vectors_sum, hipStream_t st)
-{
-    if (xt != 1 && xt != 2) return -1000;
-    {
-        size_t n = (size_t)K * D;
-        int blocks = (int)((n / 4 + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(ema_zero_kernel, dim3(blocks), dim3(256), 0, st, cluster_size, (size_t)K, vectors_sum, n);
-    }
-    const dim3 grid((unsigned)((N + 63) / 64));
-    const bool combine = K <= 8192;
-    const size_t shm = combine ? (size_t)K * sizeof(int) : 0;
-    if (xt == 1) {
-        auto kernel = combine ? ema_accumulate_kernel<true, 1> : ema_accumulate_kernel<false, 1>;
-        hipLaunchKernelGGL(kernel, grid, dim3(256), shm, st, (const _Float16 *)z, codes, D, HW, N, K, cluster_size, vectors_sum);
-    } else {
-        auto kernel = combine ? ema_accumulate_kernel<true, 2> : ema_accumulate_kernel<false, 2>;
-        hipLaunchKernelGGL(kernel, grid, dim3(256), shm, st, (const __bf16 *)z, codes, D, HW, N, K, cluster_size, vectors_sum);
-    }
     return (int)hipGetLastError();
 }
 

@@ -42,7 +42,7 @@
 // three times as long as the others and the unluckiest waves set the kernel's time), as a second loop after the main one 71;
 // this form 49 us at B = 256 in the steady state (0.51 of 8 TB/s; 13.5 us at B = 64).
 // Transcendental math -> parity is to 1e-5, not bit-exact (tests/test_entropy.py).
-#include "dvq_common.h"
+#include "launchers.h"
 #include <type_traits>
 
 namespace {

@@ -7,7 +7,7 @@
 // [world x bytes] buffer into int64 codes / grain indices of the GLOBAL batch and the global mean
 // (the per-rank pairs are added in rank order, so every rank gets the same bits).  No allocation, no
 // host round trip: the step issues pack + all_gather + unpack and nothing else.
-#include "dvq_common.h"
+#include "launchers.h"
 
 struct XchLayout {
     long cpi, gpi;          // codes / grain indices per image

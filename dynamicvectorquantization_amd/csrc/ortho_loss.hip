@@ -27,7 +27,7 @@
 // own order 8 g + 4 h + q; the A operand, channel d of row j, is read from the staged tile in that order), D / 32 accumulators of
 // 32 channels x 32 rows, each tile's contribution summed on its own and added once.  One plain 16-byte store per four channels of
 // a gradient row; no atomics, bit-reproducible.
-#include "dvq_common.h"
+#include "launchers.h"
 
 #define OL_ROWCHUNK 8          // row tiles a forward workgroup scores against its four column tiles
 

@@ -9,7 +9,7 @@
 // PAD written by the same kernel.  forward_back keeps the reference's sequential semantics (a later
 // sequence entry overwrites an earlier one at the same position, entries after EOS are ignored)
 // with an LDS "last writer" table built by atomicMax.  Pure integer work: bit-exact.
-#include "dvq_common.h"
+#include "launchers.h"
 
 constexpr int PERM_MAX_CELLS = 1024;      // coarse cells per image (reference: 16 x 16 = 256)
 

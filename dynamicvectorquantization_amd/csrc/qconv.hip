@@ -16,7 +16,7 @@
 // Mapping (as the assign kernels): output channels are the MFMA rows (A operand, 32 per tile, streamed through a
 // double-buffered LDS image), output positions the columns; a wave owns 32 consecutive positions of a row, so
 // every store instruction writes 128-B runs of one output channel row.
-#include "dvq_filter.h"
+#include "launchers.h"
 
 // prep buffer: [meta 256 B][tile t < D/32: hi image S16 KiB | lo image S16 KiB | bias of the tile's 32 rows + pad (256 B)]
 //              [bias in channel order, D floats]   (QconvMeta, qconv_tile_bytes, qconv_row_channel: dvq_filter.h)

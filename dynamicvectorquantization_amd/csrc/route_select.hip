@@ -8,7 +8,7 @@
 // traffic is the algorithmic 1 read + 1 write per element; the reference materialises two
 // upsampled copies and reads all branches.  Pure data movement -> HBM-bound: each thread moves
 // 16 B, consecutive lanes consecutive addresses; LDS only holds the image's grain map (1 B / cell).
-#include "dvq_common.h"
+#include "launchers.h"
 
 // MODE 0: f32 gate logits, 1: int64 gate, 2: f32 entropy map + threshold (the fixed-entropy router fused in:
 // gate = [(ent <= thr), (ent > thr)], whose argmax is (ent > thr); NaN compares false twice -> 0)

@@ -25,7 +25,7 @@
 //                        never reach HBM.
 // A different summation order than ATen/MKL and 2^-22 instead of 2^-24 products: tolerance parity
 // (logits within 1e-4 of the reference, ~1e-6 in practice), by design.
-#include "dvq_common.h"
+#include "launchers.h"
 #include <cstdlib>
 #include <type_traits>
 

@@ -21,7 +21,7 @@
 //   6. rt_dh_kernel       per branch one pass over its pixels: GroupNorm + pool backward plus the select's gradient
 // The pool is linear and dy is constant over a pooling window, so every GroupNorm reduction is taken on cell-level tensors; only
 // the final dh reads the feature maps.  All arithmetic fp32 (matrix products: v_mfma_f32_16x16x4_f32, exact fp32 products).
-#include "dvq_common.h"
+#include "launchers.h"
 
 #define RT_NS_MAX 16          // split-K slabs of the reductions over cells (fixed per shape: reproducible)
 

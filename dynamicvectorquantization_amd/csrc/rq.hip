@@ -15,7 +15,7 @@
 // n = (b, hh, ww) and channel j = (a rW + c) Dl + l is latent element (b, hh rH + a, ww rW + c, l).
 // These are HBM / L2 streaming kernels: 16-byte accesses where Dl % 4 == 0 and every pointer is 16-byte aligned, 4-byte ones
 // otherwise.  No kernel here touches the assign's own buffers.
-#include "dvq_common.h"
+#include "launchers.h"
 #include "../../include/dvq.h"
 
 struct DvqRqGeom {

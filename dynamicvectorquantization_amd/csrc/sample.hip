@@ -22,7 +22,7 @@
 //   draw       argmax(p / q) (torch.multinomial's own algorithm, q = Exp(1) draws given by the caller) or
 //              argmax(p); first index on ties.
 // Transfer: count + fill kernels like permute.hip (ballot scan of the marked cells; ranks in LDS for row-first).
-#include "dvq_common.h"
+#include "launchers.h"
 
 constexpr int SAMPLE_MAX_V = 8192;
 constexpr int SAMPLE_MAX_CELLS = 1024;

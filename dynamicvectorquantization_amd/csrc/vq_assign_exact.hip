@@ -19,7 +19,7 @@
 // 0-31 / 32-63 read two 128-B runs of consecutive tokens per load) and streams the codebook as
 // prepared 32-code LDS tile images (double-buffered global->LDS DMA, one barrier per tile).
 // Compute-bound on the fp32 MFMA rate (2*K*D flop per token).
-#include "dvq_filter.h"
+#include "launchers.h"
 #include <type_traits>
 
 // ROUTED: token = output position of a routed batch (dvq_filter.h: DvqRouted), read from the encoder branch that

@@ -29,6 +29,7 @@
 //                                 <= 2^(a+b) [u(1+u)(xn+en) + (u + gamma_D)(1+gamma_D) ||z|| ||e_j||]
 // W is the sum with ||e_j||, en_j, ||eta_j|| replaced by their maxima over the codebook.
 #include "dvq_pass1.h"
+#include "launchers.h"
 
 #ifndef DVQ_WIDE_MIN_K
 #define DVQ_WIDE_MIN_K 2048      // codebook size from which pass 1 takes the two-blocks-per-wave form (whole op at B = 256: -2 % at 1024, +8 % at 2048, +10 % at 4096 and 16384)
@@ -45,7 +46,6 @@
 // writes them; a thread converts octets of channels and stores them into BOTH images (the 32x32x16 order and the 16x16x32 order
 // hold the same fp16 values); the rounding residuals go through LDS so that a code's squared residual norm is summed in the order
 // it always was (lane-strided, xor tree); etamax was zeroed by the f32 prep.
-int dvq_prep_codes_per_workgroup(int K);                 // vq_assign_exact.hip
 template <int CPW>
 __global__ __launch_bounds__(256) void codebook_prep_f16_kernel(const float *__restrict__ E, int K, int D,
                                                                 const float *__restrict__ tiles32,
@@ -298,11 +298,6 @@ __global__ void zero_counters_kernel(int *__restrict__ counters, int nwords)
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-int dvq_launch_exact_list(const float *z, const float *prep, const float *E, const float *mask,
-                          int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
-                          const int *list, const int *list_count, DvqLossTail tail, const DvqRouted *rv,
-                          hipStream_t st, const DvqConv *fold_conv = nullptr, int xt = 0);
-
 #ifdef DVQ_TUNING
 // device buffer the tuning build's pass 1 writes its per-token diagnostics to (null = off): tokdbg [N][4] f32 = best, second,
 // 2W, code; stamps [workgroup][8] u64 = stage times of the split form of pass 1 and of the resolver (null = off).  Every unit
@@ -385,9 +380,6 @@ static int list_blocks(long N)
     long nb = (N + 127) / 128;
     return (int)(nb < DVQ_EXACT_LIST_BLOCKS ? nb : DVQ_EXACT_LIST_BLOCKS);
 }
-
-int dvq_launch_routed_prepass(int G, int gate_mode, const void *gate, float thr, int B, int hc, int wc,
-                              long long *indices, float *cmask, long long *gate_out, hipStream_t st);
 
 static FilterWs carve_ws(void *ws_extra, long N, int D)
 {
@@ -539,12 +531,6 @@ int dvq_launch_filter(const float *z, const void *prep, const float *E, const fl
 // filter mode: zero counters -> pass 1 with the select fused in (it derives the grain of every position's cell from the
 // gate and writes indices / codebook_mask / gate_out itself: no prepass, no tables) -> resolver -> list + loss finalize.
 // exact mode: a prepass writes indices / codebook_mask / gate_out, then every position by the exact chain.
-int dvq_launch_exact(const float *z, const float *prep, const float *E, const float *mask,
-                     int D, int HW, int K, long N, float *zq, long long *codes, double *partials,
-                     const DvqRouted *rv, hipStream_t st, int xt = 0);
-int dvq_launch_loss_finalize(const double *partials, int nparts, double inv_numel, float beta,
-                             float *loss, hipStream_t st);
-
 int dvq_launch_routed(int G, int gate_mode, const void *gate, float thr, const float *h_coarse,
                       const float *h_median, const float *h_fine, const void *prep, const float *E,
                       int B, int D, int hc, int wc, int K, float beta, float *zq, long long *codes,

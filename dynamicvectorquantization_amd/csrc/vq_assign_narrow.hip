@@ -29,7 +29,7 @@
 // Epilogue: e = E[code] from global memory, z_q in the input layout, the code as int64, one double loss partial per workgroup
 // (summed in a fixed order by vq_loss_finalize_kernel: no float atomics, the same bits every run).
 #include "../../include/dvq.h"
-#include "dvq_common.h"
+#include "launchers.h"
 
 #define NARROW_TILE_FLOATS 4096                        // 16 KiB of codebook rows per tile
 

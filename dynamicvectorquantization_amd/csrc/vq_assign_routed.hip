@@ -9,7 +9,7 @@
 //   routed_prepass_kernel   one workgroup per image: argmax of the gate (or entropy > threshold) per coarse cell
 //                           -> indices [B, hc, wc], codebook_mask [B, 1, H, W], and (entropy gate) the router's
 //                           int64 gate [B, hc, wc, 2].
-#include "dvq_filter.h"
+#include "launchers.h"
 
 template <int G>
 __global__ __launch_bounds__(256) void routed_prepass_kernel(

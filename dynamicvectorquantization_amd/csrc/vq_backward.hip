@@ -15,7 +15,7 @@
 // 16-bit latents (XT != 0, dvq_common.h; dvq_vq_backward_nchw_x16): z, g_zq and g_z are fp16 / bf16 -- 3 x 2 bytes per element --
 // widened where they are read, the same fp32 expression, narrowed once at the store.  Lane = token with 2-byte accesses: a wave
 // instruction covers two 64-byte runs.
-#include "dvq_common.h"
+#include "launchers.h"
 
 template <int XT>
 __global__ __launch_bounds__(256) void vq_backward_z_kernel(
@@ -58,20 +58,15 @@ __global__ __launch_bounds__(256) void vq_backward_z_kernel(
     }
 }
 
-int dvq_launch_vq_backward_z(const float *z, const float *E, const long long *codes, const float *mask, const float *g_zq,
-                             const float *g_loss, float coef_scale, int D, int HW, int K, long N, float *gz, hipStream_t st)
-{
-    hipLaunchKernelGGL(vq_backward_z_kernel<0>, dim3((unsigned)((N + 127) / 128)), dim3(256), 0, st, z, E, codes, mask, g_zq, g_loss,
-                       coef_scale, D, HW, K, N, gz);
-    return (int)hipGetLastError();
-}
-
-// xt = DVQ_DTYPE_F16 / DVQ_DTYPE_BF16: z, g_zq (nullable) and gz of that type
-int dvq_launch_vq_backward_z_x16(const void *z, int xt, const float *E, const long long *codes, const float *mask, const void *g_zq,
-                                 const float *g_loss, float coef_scale, int D, int HW, int K, long N, void *gz, hipStream_t st)
+// xt = 0 (float32) / DVQ_DTYPE_F16 / DVQ_DTYPE_BF16: z, g_zq (nullable) and gz of that type
+int dvq_launch_vq_backward_z(const void *z, int xt, const float *E, const long long *codes, const float *mask, const void *g_zq,
+                             const float *g_loss, float coef_scale, int D, int HW, int K, long N, void *gz, hipStream_t st)
 {
     const dim3 grid((unsigned)((N + 127) / 128));
-    if (xt == 1)
+    if (xt == 0)
+        hipLaunchKernelGGL(vq_backward_z_kernel<0>, grid, dim3(256), 0, st, (const float *)z, E, codes, mask, (const float *)g_zq,
+                           g_loss, coef_scale, D, HW, K, N, (float *)gz);
+    else if (xt == 1)
         hipLaunchKernelGGL(vq_backward_z_kernel<1>, grid, dim3(256), 0, st, (const _Float16 *)z, E, codes, mask, (const _Float16 *)g_zq,
                            g_loss, coef_scale, D, HW, K, N, (_Float16 *)gz);
     else if (xt == 2)

@@ -11,7 +11,7 @@
 //
 // Buffer: [DvqFoldMeta, 256 B][image "32"][image "16"]  (offsets as in the codebook prep's f16 section)
 //         [scratch: E' as K x D doubles | per-code statistics 4 doubles | per-column statistics of W^T W, 2 doubles]
-#include "dvq_filter.h"
+#include "launchers.h"
 
 static size_t fold_img_bytes(int K, int D)
 {

@@ -30,7 +30,7 @@
 //           then; stores of a wave cover 128-byte runs along the tokens; the rows of embed are L2-resident).  The reference's
 //           value is f embed[code] with f = fl(fl(1 - y) + y), y the winner's soft probability: |f - 1| <= 2^-23.
 // No atomics, no host synchronisation, vector stores only.
-#include "dvq_common.h"
+#include "launchers.h"
 
 template <int D, bool NOISE>
 __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(

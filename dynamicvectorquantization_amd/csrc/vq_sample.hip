@@ -25,7 +25,7 @@
 // vq_apply_codes_kernel: z_q = fl(z + fl(e - z)) and the loss partial sum((e - z)^2 m) of given codes, the arithmetic of the exact
 // assign's tail (vq_assign_exact.hip) in the streaming form of vq_backward.hip; double partials, one per workgroup, finalised in a
 // fixed order by vq_loss_finalize_kernel.
-#include "dvq_common.h"
+#include "launchers.h"
 
 #define DVQ_METRIC_L2_ 0
 #define DVQ_METRIC_DOT_ 1

@@ -20,7 +20,7 @@
 // fixed order (lane-strided, then a butterfly); p = expf(s - max) / float(sum) written in place; argmax of p / q for the draw.
 // design (a) of DESIGN.md section 4.13: one MFMA sweep, one re-read of the rows; the alternative doubles the MFMA work that
 // bounds the kernel.
-#include "dvq_common.h"
+#include "launchers.h"
 
 template <int V>
 __device__ __forceinline__ void soft_ld(const float *p, float (&v)[V])
