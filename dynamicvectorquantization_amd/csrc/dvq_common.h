@@ -48,7 +48,7 @@ template <int XT> __device__ __forceinline__ unsigned short dvq_narrow_bits(floa
 //   [f16 section]      used by the filter kernel, see vq_assign_filter.hip.
 // ---------------------------------------------------------------------------------------------
 __host__ __device__ inline int dvq_num_tiles(int K) { return (K + DVQ_CODE_TILE - 1) / DVQ_CODE_TILE; }
-__host__ __device__ inline size_t dvq_tile_floats(int D) { return (size_t)32 * D + 64; }
+__host__ __device__ constexpr size_t dvq_tile_floats(int D) { return (size_t)32 * D + 64; }
 __host__ __device__ inline size_t dvq_prep_f32_tiles_bytes(int K, int D)
 {
     return (size_t)dvq_num_tiles(K) * dvq_tile_floats(D) * sizeof(float);
@@ -135,6 +135,13 @@ __device__ __forceinline__ void argmax_merge(float &v, int &i, float v2, int i2)
     else
         other = (v2 > v) || (v2 == v && i2 < i);
     if (other) { v = v2; i = i2; }
+}
+
+// (value, index) argmax of the draws argmax(p / q) and argmax(p) (sample.hip, vq_soft.hip's phase B), any visiting order: the
+// smallest index among equal maxima; a NaN never wins (argmax_take / argmax_merge above are torch.argmax: there a NaN is the maximum)
+__device__ __forceinline__ void argmax_pair(float &v, int &i, float ov, int oi)
+{
+    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
 
 // Loss finalize fused into the last kernel of the filter path (vq_assign_exact_kernel in list

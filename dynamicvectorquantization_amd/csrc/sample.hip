@@ -78,12 +78,6 @@ __device__ __forceinline__ float block_max_f32(float v, float *red)
     __syncthreads();
     return m;
 }
-// (value, index) argmax, the smallest index among equal maxima
-__device__ __forceinline__ void argmax_pair(float &v, int &i, float ov, int oi)
-{
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
-}
-
 __global__ __launch_bounds__(256) void sample_head_kernel(
     const float *__restrict__ logits, long long lstride, int V, float temperature, SampleRules r,
     const long long *__restrict__ hist, long long hstride, int hlen, float *__restrict__ flag,

@@ -19,7 +19,14 @@
 // 0-31 / 32-63 read two 128-B runs of consecutive tokens per load) and streams the codebook as
 // prepared 32-code LDS tile images (double-buffered global->LDS DMA, one barrier per tile).
 // Compute-bound on the fp32 MFMA rate (2*K*D flop per token).
+// dvq_exact_tile.h holds the pieces of that loop as helpers for vq_soft.hip, vq_sample.hip and vq_gumbel.hip.  THIS kernel keeps its
+// own text of the stage, the norm, the chain, the register -> code mapping, the merge and the token load, each marked with the helper
+// that mirrors it: taken through the helpers, every instantiation's machine code moved (operand and register order; the 16-bit
+// dense ones changed their register count), and a kernel whose code moves keeps its copy.  As written, all 33 instantiations are
+// byte-identical to what they were before the header existed (profiles/exact_tile_isa.json).  A change to one of the marked
+// pieces is made here and in the header.
 #include "launchers.h"
+#include "dvq_exact_tile.h"
 #include <type_traits>
 
 // ROUTED: token = output position of a routed batch (dvq_filter.h: DvqRouted), read from the encoder branch that
@@ -43,9 +50,7 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
     static_assert(XT == 0 || (!ROUTED && !FOLDCONV), "16-bit latents: the dense op");
     typedef typename DvqLat<XT>::T ZT;
     constexpr int S = D / 2;                         // MFMA steps (2 k each)
-    constexpr int TILE_FLOATS = 32 * D + 64;
-    constexpr int CHUNKS_PER_WAVE = (32 * D * 4 / 1024) / 4;   // 1-KiB DMA pieces per wave per tile
-    extern __shared__ __attribute__((aligned(16))) float lds[];   // 2 * TILE_FLOATS (+ 4 doubles)
+    extern __shared__ __attribute__((aligned(16))) float lds[];   // dvq_exact_lds_bytes(D); the loss reductions reuse it
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -86,7 +91,7 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
     } else {
         const long b = nn / HW;
         stride = HW;
-        zp = z + ((size_t)b * D + h) * HW + (size_t)(nn - b * HW);
+        zp = z + ((size_t)b * D + h) * HW + (size_t)(nn - b * HW);     // mirrors exact_load_token_nchw
     }
     const long bout = nn / HWo;
     const size_t zqbase = ((size_t)bout * D + h) * HWo + (size_t)(nn - bout * HWo);
@@ -178,7 +183,9 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
     for (int s = 0; s < S; ++s) zr[s] = zp[(size_t)2 * s * stride];
     }
 
-    auto stage = [&](int t, float *buf) {
+    constexpr int TILE_FLOATS = EXACT_TILE_FLOATS<D>;
+    constexpr int CHUNKS_PER_WAVE = EXACT_CHUNKS_PER_WAVE<D>;
+    auto stage = [&](int t, float *buf) {         // mirrors exact_stage
         const char *src = (const char *)(tiles + (size_t)t * TILE_FLOATS);
 #pragma unroll
         for (int i = 0; i < CHUNKS_PER_WAVE; ++i) {
@@ -187,12 +194,11 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
         }
         if (wave == 0) glds4(src + 32 * D * 4 + lane * 4, (char *)buf + 32 * D * 4);
     };
-
     const int T = dvq_num_tiles(K);
     if (LIST) __syncthreads();                // (next chunk) everyone is done with the buffers
     stage(0, lds);
 
-    // ---- xn: ATen-order sum of squares of this token (both lanes of a token get the same value)
+    // ---- xn: ATen-order sum of squares of this token (both lanes of a token get the same value); mirrors exact_token_sumsq
     float xn;
     {
         float p[16], o[16];
@@ -208,7 +214,6 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
         float t[8];
 #pragma unroll
         for (int l = 0; l < 8; ++l) {
-            // a[m], m = l + 8g: even m lives in the h = 0 lane's p[m/2], odd m in the h = 1 lane's
             float a4[4];
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
@@ -229,10 +234,10 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
     for (int t = 0; t < T; ++t) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                      // tile t landed; everyone is done with tile t-1
-        float *buf = lds + (t & 1) * TILE_FLOATS;
+        float *buf = exact_buf<D>(lds, t);
         if (t + 1 < T) stage(t + 1, lds + ((t + 1) & 1) * TILE_FLOATS);
 
-        f32x16 acc;
+        f32x16 acc;                           // mirrors exact_tile_dots
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
         const float *ap = buf + c * 8 + h * 4;
@@ -244,14 +249,13 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], zr[kg * 4 + 2], acc, 0, 0, 0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], zr[kg * 4 + 3], acc, 0, 0, 0);
         }
-        const float *entile = buf + 32 * D + 4 * h;
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            f32x4 en4 = *(const f32x4 *)(entile + 8 * g);
+            const f32x4 en4 = exact_tile_en4<D>(buf, h, g);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                int r = g * 4 + q;
-                int code = t * 32 + q + 8 * g + 4 * h;
+                const int r = g * 4 + q;
+                const int code = t * 32 + q + 8 * g + 4 * h;      // mirrors exact_code_of
                 float bias = __fadd_rn(xn, en4[q]);
                 float d = __builtin_fmaf(-2.0f, acc[r], bias);   // fl(bias - 2 dot), 2 dot exact
                 bool take = argmin_take(d, best) && (code < K);
@@ -261,7 +265,7 @@ __global__ __launch_bounds__(256, FOLDCONV ? 1 : 2) void vq_assign_exact_kernel(
         }
     }
 
-    {   // merge the two lane halves of each token
+    {   // merge the two lane halves of each token: mirrors exact_merge_halves_argmax, with argmin
         float ob = __shfl_xor(best, 32);
         int oi = __shfl_xor(bidx, 32);
         argmin_merge(best, bidx, ob, oi);
@@ -523,7 +527,7 @@ static int launch_exact(const float *z, const float *tiles, const float *E, cons
                         const int *list, const int *list_count, DvqLossTail tail, const DvqRouted &rv,
                         hipStream_t st, const DvqConv *fold_conv, int xt)
 {
-    const size_t shmem = 2 * (32 * D + 64) * sizeof(float);
+    const size_t shmem = dvq_exact_lds_bytes(D);
     int blocks = (int)((N + 127) / 128);
     if constexpr (!ROUTED) {
         if (xt != 0) {                                       // 16-bit latents: the dense op, every token or the list

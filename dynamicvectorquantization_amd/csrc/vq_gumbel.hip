@@ -5,11 +5,10 @@
 // operand is one-hot, a second softmax and a log for the KL term and an argmax -- about ten passes over [N, K] floats -- by ONE
 // sweep that reads z and the caller-drawn variates q once and writes N codes, one scalar and z_q.  Nothing of size N x K is written.
 //
-// vq_gumbel_assign_kernel: the tile loop is vq_score_assign_kernel's (vq_sample.hip): a wave keeps its 32 tokens' C channels in
-// registers, read in place from NCHW [B, C, HW] (HW == 1: row-major [N, C]); `proj.weight` [K, C] streams through LDS as the
-// codebook's prepared tile images (double-buffered global -> LDS DMA, one barrier per tile) whose 32-float `en` slot holds
-// proj.bias (dvq_gumbel_prepare_f32: the codebook prep's image builder, then gumbel_bias_kernel over the slot).  MFMA rows = 32
-// codes, columns = 32 tokens: lane (c, h) holds token c and, per tile, the 16 codes 32 t + 8 g + 4 h + {0..3}, g < 4.
+// vq_gumbel_assign_kernel: built on the exact-chain tile loop's pieces (dvq_exact_tile.h; codes in rows), the tokens' C channels
+// read in place from NCHW [B, C, HW] (HW == 1: row-major [N, C]).  What this kernel adds: `proj.weight` [K, C] takes the
+// codebook's place in the prepared tile images, whose 32-float `en` slot holds proj.bias (dvq_gumbel_prepare_f32: the codebook
+// prep's image builder, then gumbel_bias_kernel over the slot); the Gumbel argmax; the online KL state; the z_q epilogue.
 //   logit   l_k = fl(dot(z_n, W_k) + b_k): the sequential-k fp32 FMA chain of the score assign, the bias added after the chain
 //   code    q == nullptr: argmax_k l_k;  q given: argmax_k fl(fl(l_k + g_k) / tau), g_k = -logf(q_k), q [B, K, HW] the Exp(1)
 //           variates F.gumbel_softmax draws, in the logits' own layout: the 32 lanes of a half read 128 contiguous bytes per code,
@@ -31,6 +30,7 @@
 //           value is f embed[code] with f = fl(fl(1 - y) + y), y the winner's soft probability: |f - 1| <= 2^-23.
 // No atomics, no host synchronisation, vector stores only.
 #include "launchers.h"
+#include "dvq_exact_tile.h"
 
 template <int D, bool NOISE>
 __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
@@ -38,10 +38,7 @@ __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
     float tau, double log_kl_K, const float *__restrict__ q, float *__restrict__ zq, long long *__restrict__ codes,
     double *__restrict__ partials)
 {
-    constexpr int S2 = D / 2;                        // MFMA steps (2 k each)
-    constexpr int TILE_FLOATS = 32 * D + 64;
-    constexpr int CHUNKS_PER_WAVE = (32 * D * 4 / 1024) / 4;   // 1-KiB DMA pieces per wave per tile
-    extern __shared__ __attribute__((aligned(16))) float lds[];   // 2 * TILE_FLOATS
+    extern __shared__ __attribute__((aligned(16))) float lds[];   // dvq_exact_lds_bytes(D)
     __shared__ double red[4];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -51,25 +48,12 @@ __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
     const bool valid = n < N;
     const long nn = valid ? n : N - 1;               // lanes past the end re-read the last token; they store nothing
     const long b = nn / HW;
-    const long hw = nn - b * HW;
-    const float *zp = z + ((size_t)b * D + h) * HW + (size_t)hw;   // channel k = 2s + h at zp + 2s HW
-
-    float zr[S2];
-#pragma unroll
-    for (int s = 0; s < S2; ++s) zr[s] = zp[(size_t)2 * s * HW];
-
-    auto stage = [&](int t, float *buf) {
-        const char *src = (const char *)(tiles + (size_t)t * TILE_FLOATS);
-#pragma unroll
-        for (int i = 0; i < CHUNKS_PER_WAVE; ++i) {
-            int chunk = wave * CHUNKS_PER_WAVE + i;
-            glds16(src + chunk * 1024 + lane * 16, (char *)buf + chunk * 1024);
-        }
-        if (wave == 0) glds4(src + 32 * D * 4 + lane * 4, (char *)buf + 32 * D * 4);
-    };
+    const long hw = nn - b * HW;                     // (b, hw) also address q and z_q
+    float zr[D / 2];
+    exact_load_token_nchw<D>(z, HW, b, nn, h, zr);
 
     const int T = dvq_num_tiles(K);
-    stage(0, lds);
+    exact_stage<D>(tiles, 0, lds, wave, lane);
 
     const bool want_kl = partials != nullptr;        // (uniform: a kernel argument)
     float best = -__builtin_inff();
@@ -80,7 +64,7 @@ __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
     for (int t = 0; t < T; ++t) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                      // tile t landed; everyone is done with tile t-1
-        float *buf = lds + (t & 1) * TILE_FLOATS;
+        float *buf = exact_buf<D>(lds, t);
 
         // this tile's variates of the lane's token: in flight under the MFMA chain
         float qq[16];
@@ -89,36 +73,25 @@ __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
             for (int g = 0; g < 4; ++g) {
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const int code = t * 32 + 8 * g + 4 * h + j;
+                    const int code = exact_code_of(t, g, j, h);
                     qq[4 * g + j] = (code < K) ? __builtin_nontemporal_load(qcol + (size_t)code * (size_t)HW) : 1.0f;
                 }
             }
         }
-        if (t + 1 < T) stage(t + 1, lds + ((t + 1) & 1) * TILE_FLOATS);
+        if (t + 1 < T) exact_stage<D>(tiles, t + 1, exact_buf<D>(lds, t + 1), wave, lane);
 
         f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-        const float *ap = buf + c * 8 + h * 4;
-#pragma unroll
-        for (int kg = 0; kg < D / 8; ++kg) {
-            f32x4 a = *(const f32x4 *)(ap + kg * 256);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], zr[kg * 4 + 0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], zr[kg * 4 + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], zr[kg * 4 + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], zr[kg * 4 + 3], acc, 0, 0, 0);
-        }
-        const float *btile = buf + 32 * D + 4 * h;
+        exact_tile_dots<D>(buf, zr, c, h, acc);
         float l[16];
         // the tile's maximum over this lane's codes: fmaxf drops a NaN here, which reaches the sums through its own term
         float tm = -__builtin_inff();
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            const f32x4 b4 = *(const f32x4 *)(btile + 8 * g);
+            const f32x4 b4 = exact_tile_en4<D>(buf, h, g);      // proj.bias
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int r = g * 4 + j;
-                const int code = t * 32 + j + 8 * g + 4 * h;
+                const int code = exact_code_of(t, g, j, h);
                 l[r] = __fadd_rn(acc[r], b4[j]);
                 float s = l[r];
                 if constexpr (NOISE) s = __fadd_rn(s, -logf(qq[r])) / tau;
@@ -145,7 +118,7 @@ __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const int r = g * 4 + j;
-                    const int code = t * 32 + j + 8 * g + 4 * h;
+                    const int code = exact_code_of(t, g, j, h);
                     const float x = l[r] - m;        // <= 0
                     const float e = (code < K) ? expf(x) : 0.0f;
                     ts += e;
@@ -157,12 +130,7 @@ __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
         }
     }
 
-    {   // merge the two lane halves of each token
-        const float ob = __shfl_xor(best, 32);
-        const int oi = __shfl_xor(bidx, 32);
-        argmax_merge(best, bidx, ob, oi);
-    }
-    const int code = (bidx == 0x7fffffff) ? 0 : bidx;              // (unreachable for K >= 1: a first candidate is always taken)
+    const int code = exact_merge_halves_argmax(best, bidx);
     if (valid && h == 0) codes[n] = (long long)code;
 
     if (want_kl) {
@@ -241,7 +209,7 @@ template <int D>
 static int launch_gumbel(const float *z, const float *tiles, const float *E, int HW, int K, int d, long N, float tau, double log_kl_K,
                          const float *q, float *zq, long long *codes, double *partials, hipStream_t st)
 {
-    const size_t shmem = 2 * (32 * D + 64) * sizeof(float);
+    const size_t shmem = dvq_exact_lds_bytes(D);
     const dim3 grid((unsigned)dvq_gumbel_blocks(N)), block(256);
     if (q == nullptr)
         return dvq_launch_lds<vq_gumbel_assign_kernel<D, false>>(grid, block, shmem, st, z, tiles, E, HW, K, d, N, tau, log_kl_K, q, zq,

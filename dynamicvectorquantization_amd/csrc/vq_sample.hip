@@ -7,13 +7,11 @@
 // caller-drawn uniforms once and writes N codes; then the embedding gather, the (masked) loss and the straight-through add by one
 // streaming kernel.
 //
-// vq_score_assign_kernel: the tile loop is vq_assign_exact.hip's (and vq_soft.hip's: the same D/2 chained v_mfma_f32_32x32x2_f32 per
-// 32-code tile, the reference's sequential-k fp32 FMA chain, so every dot is the same bits): a wave keeps its 32 tokens' D channels in
-// registers -- read in place from NCHW [B, D, HW], or from row-major [N, D] as the case HW == 1 -- and the codebook streams through
-// LDS as the prepared tile images (double-buffered global -> LDS DMA, one barrier per tile).  MFMA rows = 32 codes, columns = 32
-// tokens: lane (c, h) holds token c and, per tile, the 16 codes 32 t + 8 g + 4 h + {0..3}, g < 4 -- four runs of four consecutive
-// codes, which is what lets a lane fetch its 16 uniforms of the tile as four 16-byte loads of row c of u, issued before the MFMA
-// chain that hides them, and keeps the running argmax lane-local (the two lane halves are merged once, after the loop).
+// vq_score_assign_kernel: built on the exact-chain tile loop's pieces (dvq_exact_tile.h; codes in rows, so the running argmax is
+// lane-local), every dot the same bits as the hard assign's.  The tokens are read in place from NCHW [B, D, HW], or from row-major
+// [N, D] as the case HW == 1.  What this kernel adds: a score per metric, and the noise -- a lane's 16 codes of a tile are four
+// runs of four consecutive codes, so it fetches its 16 uniforms as four 16-byte loads of row c of u, issued before the stage and
+// the MFMA chain that hide them.
 //   score   L2:  s = -d, d = fl(fl(xn + en) - 2 dot) (ATen-order norms): the reference's expression negated, bit for bit
 //           DOT: s = dot (operands L2-normalised by the caller)
 //           CDIST: s = -sqrtf(d < 0 ? 0 : d), d as L2 (quantize_lucidrains.py:123, `-torch.cdist`): the square root does not commute
@@ -25,11 +23,13 @@
 // vq_apply_codes_kernel: z_q = fl(z + fl(e - z)) and the loss partial sum((e - z)^2 m) of given codes, the arithmetic of the exact
 // assign's tail (vq_assign_exact.hip) in the streaming form of vq_backward.hip; double partials, one per workgroup, finalised in a
 // fixed order by vq_loss_finalize_kernel.
+#include "../../include/dvq.h"
 #include "launchers.h"
+#include "dvq_exact_tile.h"
 
-#define DVQ_METRIC_L2_ 0
-#define DVQ_METRIC_DOT_ 1
-#define DVQ_METRIC_CDIST_ 2      // s = -sqrt(max(d, 0)): torch.cdist's score (dvq_vq_cdist_sample_assign_f32 only; not a value of the ABI's `metric`)
+// the METRIC of the kernel template: dvq.h's DVQ_METRIC_L2 / DVQ_METRIC_DOT, and one more that is internal to this unit
+#define SCORE_INTERNAL_CDIST 2   // s = -sqrt(max(d, 0)): torch.cdist's score (dvq_vq_cdist_sample_assign_f32 only; not a value of the ABI's `metric`)
+static_assert(SCORE_INTERNAL_CDIST != DVQ_METRIC_L2 && SCORE_INTERNAL_CDIST != DVQ_METRIC_DOT, "the internal metric must not collide");
 
 // the reference's gumbel_noise of one uniform (common_utils.py:19-29): -log(clamp(-log(clamp(u, 1e-20)), 1e-20))
 __device__ __forceinline__ float gumbel_of(float u)
@@ -44,10 +44,7 @@ __global__ __launch_bounds__(256, 2) void vq_score_assign_kernel(
     const float *__restrict__ z, const float *__restrict__ tiles, int HW, int K, long N, float temp,
     const float *__restrict__ u, long long *__restrict__ codes)
 {
-    constexpr int S = D / 2;                         // MFMA steps (2 k each)
-    constexpr int TILE_FLOATS = 32 * D + 64;
-    constexpr int CHUNKS_PER_WAVE = (32 * D * 4 / 1024) / 4;   // 1-KiB DMA pieces per wave per tile
-    extern __shared__ __attribute__((aligned(16))) float lds[];   // 2 * TILE_FLOATS
+    extern __shared__ __attribute__((aligned(16))) float lds[];   // dvq_exact_lds_bytes(D)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -56,54 +53,14 @@ __global__ __launch_bounds__(256, 2) void vq_score_assign_kernel(
     const bool valid = n < N;
     const long nn = valid ? n : N - 1;               // lanes past the end re-read the last token; they store nothing
     const long b = nn / HW;
-    const float *zp = z + ((size_t)b * D + h) * HW + (size_t)(nn - b * HW);   // channel k = 2s + h at zp + 2s HW
-
-    float zr[S];
-#pragma unroll
-    for (int s = 0; s < S; ++s) zr[s] = zp[(size_t)2 * s * HW];
-
-    auto stage = [&](int t, float *buf) {
-        const char *src = (const char *)(tiles + (size_t)t * TILE_FLOATS);
-#pragma unroll
-        for (int i = 0; i < CHUNKS_PER_WAVE; ++i) {
-            int chunk = wave * CHUNKS_PER_WAVE + i;
-            glds16(src + chunk * 1024 + lane * 16, (char *)buf + chunk * 1024);
-        }
-        if (wave == 0) glds4(src + 32 * D * 4 + lane * 4, (char *)buf + 32 * D * 4);
-    };
+    float zr[D / 2];
+    exact_load_token_nchw<D>(z, HW, b, nn, h, zr);
 
     const int T = dvq_num_tiles(K);
-    stage(0, lds);
+    exact_stage<D>(tiles, 0, lds, wave, lane);
 
-    // ---- xn: ATen-order sum of squares of this token (vq_assign_exact.hip); the DOT metric has no norms
-    float xn = 0.0f;
-    if constexpr (METRIC != DVQ_METRIC_DOT_) {
-        float p[16], o[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            float a = sq_rn(zr[q]);
-#pragma unroll
-            for (int j = 1; j < S / 16; ++j) a = __fadd_rn(a, sq_rn(zr[q + 16 * j]));
-            p[q] = a;
-        }
-#pragma unroll
-        for (int q = 0; q < 16; ++q) o[q] = __shfl_xor(p[q], 32);
-        float tl[8];
-#pragma unroll
-        for (int l = 0; l < 8; ++l) {
-            float a4[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                int m = l + 8 * g;
-                float mine = p[m >> 1], other = o[m >> 1];
-                a4[g] = ((m & 1) == h) ? mine : other;
-            }
-            tl[l] = __fadd_rn(__fadd_rn(__fadd_rn(a4[0], a4[1]), a4[2]), a4[3]);
-        }
-        xn = tl[0];
-#pragma unroll
-        for (int l = 1; l < 8; ++l) xn = __fadd_rn(xn, tl[l]);
-    }
+    float xn = 0.0f;                                 // the DOT metric has no norms
+    if constexpr (METRIC != DVQ_METRIC_DOT) xn = exact_token_sumsq<D>(zr, h);
 
     float best = -__builtin_inff();
     int bidx = 0x7fffffff;
@@ -112,14 +69,14 @@ __global__ __launch_bounds__(256, 2) void vq_score_assign_kernel(
     for (int t = 0; t < T; ++t) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                      // tile t landed; everyone is done with tile t-1
-        float *buf = lds + (t & 1) * TILE_FLOATS;
+        float *buf = exact_buf<D>(lds, t);
 
         // this tile's uniforms of the lane's token: in flight under the MFMA chain
         float uu[16];
         if constexpr (NOISE) {
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-                const int code0 = t * 32 + 8 * g + 4 * h;
+                const int code0 = exact_code_of(t, g, 0, h);
                 if constexpr (VEC) {
                     f32x4 v = {0.5f, 0.5f, 0.5f, 0.5f};
                     if (code0 < K) v = __builtin_nontemporal_load((const f32x4 *)(urow + code0));     // K % 4 == 0: all four < K
@@ -131,34 +88,23 @@ __global__ __launch_bounds__(256, 2) void vq_score_assign_kernel(
                 }
             }
         }
-        if (t + 1 < T) stage(t + 1, lds + ((t + 1) & 1) * TILE_FLOATS);
+        if (t + 1 < T) exact_stage<D>(tiles, t + 1, exact_buf<D>(lds, t + 1), wave, lane);
 
         f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-        const float *ap = buf + c * 8 + h * 4;
-#pragma unroll
-        for (int kg = 0; kg < D / 8; ++kg) {
-            f32x4 a = *(const f32x4 *)(ap + kg * 256);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[0], zr[kg * 4 + 0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[1], zr[kg * 4 + 1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[2], zr[kg * 4 + 2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[3], zr[kg * 4 + 3], acc, 0, 0, 0);
-        }
-        const float *entile = buf + 32 * D + 4 * h;
+        exact_tile_dots<D>(buf, zr, c, h, acc);
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             f32x4 en4 = {0.0f, 0.0f, 0.0f, 0.0f};
-            if constexpr (METRIC != DVQ_METRIC_DOT_) en4 = *(const f32x4 *)(entile + 8 * g);
+            if constexpr (METRIC != DVQ_METRIC_DOT) en4 = exact_tile_en4<D>(buf, h, g);
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int r = g * 4 + q;
-                const int code = t * 32 + q + 8 * g + 4 * h;
+                const int code = exact_code_of(t, g, q, h);
                 float s;
-                if constexpr (METRIC == DVQ_METRIC_L2_) {
+                if constexpr (METRIC == DVQ_METRIC_L2) {
                     const float bias = __fadd_rn(xn, en4[q]);
                     s = -__builtin_fmaf(-2.0f, acc[r], bias);    // -(fl(bias - 2 dot)), 2 dot exact
-                } else if constexpr (METRIC == DVQ_METRIC_CDIST_) {
+                } else if constexpr (METRIC == SCORE_INTERNAL_CDIST) {
                     const float d = __builtin_fmaf(-2.0f, acc[r], __fadd_rn(xn, en4[q]));
                     s = -__fsqrt_rn(d < 0.0f ? 0.0f : d);        // (the conditional keeps a NaN; fmaxf would not)
                 } else {
@@ -172,19 +118,15 @@ __global__ __launch_bounds__(256, 2) void vq_score_assign_kernel(
         }
     }
 
-    {   // merge the two lane halves of each token
-        const float ob = __shfl_xor(best, 32);
-        const int oi = __shfl_xor(bidx, 32);
-        argmax_merge(best, bidx, ob, oi);
-    }
-    if (valid && h == 0) codes[n] = (long long)(bidx == 0x7fffffff ? 0 : bidx);    // every score -inf -> index 0
+    const int code = exact_merge_halves_argmax(best, bidx);
+    if (valid && h == 0) codes[n] = (long long)code;
 }
 
 template <int D, int METRIC>
 static int launch_score(const float *z, const float *tiles, int HW, int K, long N, float temp, const float *u, long long *codes,
                         int vec, hipStream_t st)
 {
-    const size_t shmem = 2 * (32 * D + 64) * sizeof(float);
+    const size_t shmem = dvq_exact_lds_bytes(D);
     const dim3 grid((unsigned)((N + 127) / 128)), block(256);
     if (u == nullptr)
         return dvq_launch_lds<vq_score_assign_kernel<D, METRIC, false, false>>(grid, block, shmem, st, z, tiles, HW, K, N, temp, u, codes);
@@ -198,14 +140,14 @@ int dvq_launch_score_assign(const float *z, const float *prep, int D, int HW, in
                             long long *codes, hipStream_t st)
 {
     const int vec = (K % 4 == 0) && ((uintptr_t)u & 15) == 0;     // 16-byte pieces of a row of u: every row start aligned
-    const bool dot = metric == DVQ_METRIC_DOT_;
+    const bool dot = metric == DVQ_METRIC_DOT;
     switch (D) {
-    case 64:  return dot ? launch_score<64, DVQ_METRIC_DOT_>(z, prep, HW, K, N, temp, u, codes, vec, st)
-                         : launch_score<64, DVQ_METRIC_L2_>(z, prep, HW, K, N, temp, u, codes, vec, st);
-    case 128: return dot ? launch_score<128, DVQ_METRIC_DOT_>(z, prep, HW, K, N, temp, u, codes, vec, st)
-                         : launch_score<128, DVQ_METRIC_L2_>(z, prep, HW, K, N, temp, u, codes, vec, st);
-    case 256: return dot ? launch_score<256, DVQ_METRIC_DOT_>(z, prep, HW, K, N, temp, u, codes, vec, st)
-                         : launch_score<256, DVQ_METRIC_L2_>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 64:  return dot ? launch_score<64, DVQ_METRIC_DOT>(z, prep, HW, K, N, temp, u, codes, vec, st)
+                         : launch_score<64, DVQ_METRIC_L2>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 128: return dot ? launch_score<128, DVQ_METRIC_DOT>(z, prep, HW, K, N, temp, u, codes, vec, st)
+                         : launch_score<128, DVQ_METRIC_L2>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 256: return dot ? launch_score<256, DVQ_METRIC_DOT>(z, prep, HW, K, N, temp, u, codes, vec, st)
+                         : launch_score<256, DVQ_METRIC_L2>(z, prep, HW, K, N, temp, u, codes, vec, st);
     default:  return -1000;
     }
 }
@@ -216,9 +158,9 @@ int dvq_launch_cdist_sample_assign(const float *z, const float *prep, int D, int
 {
     const int vec = (K % 4 == 0) && ((uintptr_t)u & 15) == 0;
     switch (D) {
-    case 64:  return launch_score<64, DVQ_METRIC_CDIST_>(z, prep, HW, K, N, temp, u, codes, vec, st);
-    case 128: return launch_score<128, DVQ_METRIC_CDIST_>(z, prep, HW, K, N, temp, u, codes, vec, st);
-    case 256: return launch_score<256, DVQ_METRIC_CDIST_>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 64:  return launch_score<64, SCORE_INTERNAL_CDIST>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 128: return launch_score<128, SCORE_INTERNAL_CDIST>(z, prep, HW, K, N, temp, u, codes, vec, st);
+    case 256: return launch_score<256, SCORE_INTERNAL_CDIST>(z, prep, HW, K, N, temp, u, codes, vec, st);
     default:  return -1000;
     }
 }

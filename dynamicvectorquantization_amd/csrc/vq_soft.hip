@@ -4,13 +4,10 @@
 // Replaces VQEmbedding.compute_distances + F.softmax(-distances / temp) + argmin / torch.multinomial
 // (reference modules/vector_quantization/quantize2_mask.py:29-48,193-205; quantize_rqvae.py:372-400, once per depth).
 //
-// The tile loop is vq_assign_exact.hip's: the wave keeps its 32 tokens' D channels in registers, the codebook streams through
-// LDS as the prepared 32-code tile images (double-buffered global -> LDS DMA, one barrier per tile), D/2 chained
-// v_mfma_f32_32x32x2_f32 per tile ARE the reference's sequential-k fp32 FMA chain.  One difference: the operands are swapped --
-// MFMA rows = 32 TOKENS, columns = 32 CODES (a product a*b is the same number either way, so every dot is the same bits) -- so that
-// accumulator register r of lane (c, h) holds token (r&3) + 8(r>>2) + 4h, code 32 t + c: one register across the wave is two
-// 128-byte runs of consecutive codes in two token rows, which is what a row-major [N, K] store wants.  The price is that a
-// token's running argmin lives in 32 lanes; they are merged once, after the loop.
+// Built on the exact-chain tile loop's pieces (dvq_exact_tile.h), every dot the same bits as the hard assign's.  What this kernel
+// adds: it takes the chain in the TOKEN_ROWS order -- accumulator register r of lane (c, h) holds token (r&3) + 8(r>>2) + 4h,
+// code 32 t + c -- because its outputs are row-major [N, K] rows.  The price is that a token's running argmin lives in 32 lanes;
+// they are merged once, after the loop.
 //
 // Phase A (tile loop): d = fl(fl(xn + en) - 2 dot) -> dist (optional); s = (-d) / temp -> the soft row (or the workspace when only
 // the draw is wanted); running first-index argmin per (lane, register).  The row maximum of s needs no second running value:
@@ -21,6 +18,7 @@
 // design (a) of DESIGN.md section 4.13: one MFMA sweep, one re-read of the rows; the alternative doubles the MFMA work that
 // bounds the kernel.
 #include "launchers.h"
+#include "dvq_exact_tile.h"
 
 template <int V>
 __device__ __forceinline__ void soft_ld(const float *p, float (&v)[V])
@@ -41,12 +39,6 @@ __device__ __forceinline__ void soft_st(float *p, const float (&v)[V])
     } else {
         *p = v[0];
     }
-}
-
-// (value, index) argmax, the smallest index among equal maxima; NaN never wins (sample.hip's convention)
-__device__ __forceinline__ void soft_argmax_pair(float &v, int &i, float ov, int oi)
-{
-    if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
 }
 
 // one row of phase B by one wave; V = 4: K % 4 == 0 and 16-byte aligned rows
@@ -76,12 +68,12 @@ __device__ __forceinline__ void soft_row(const float *srow, float *prow, const f
             float qv[V];
             soft_ld<V>(qrow + j, qv);
 #pragma unroll
-            for (int i = 0; i < V; ++i) soft_argmax_pair(bv, bi, p[i] / qv[i], j + i);
+            for (int i = 0; i < V; ++i) argmax_pair(bv, bi, p[i] / qv[i], j + i);
         }
     }
     if (qrow != nullptr) {
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) soft_argmax_pair(bv, bi, __shfl_xor(bv, off), __shfl_xor(bi, off));
+        for (int off = 32; off > 0; off >>= 1) argmax_pair(bv, bi, __shfl_xor(bv, off), __shfl_xor(bi, off));
         if (lane == 0) *code_out = (long long)(bi == 0x7fffffff ? 0 : bi);      // every ratio NaN -> index 0
     }
 }
@@ -93,10 +85,7 @@ __global__ __launch_bounds__(256, 2) void vq_soft_assign_kernel(
     const float *__restrict__ x, const float *__restrict__ tiles, int K, long N, float temp,
     const float *__restrict__ q, float *soft, float *__restrict__ dist, float *sbuf, long long *__restrict__ codes, int vec)
 {
-    constexpr int S = D / 2;                         // MFMA steps (2 k each)
-    constexpr int TILE_FLOATS = 32 * D + 64;
-    constexpr int CHUNKS_PER_WAVE = (32 * D * 4 / 1024) / 4;   // 1-KiB DMA pieces per wave per tile
-    extern __shared__ __attribute__((aligned(16))) float lds[];   // 2 * TILE_FLOATS
+    extern __shared__ __attribute__((aligned(16))) float lds[];   // dvq_exact_lds_bytes(D)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -105,51 +94,17 @@ __global__ __launch_bounds__(256, 2) void vq_soft_assign_kernel(
     const long nn = (n0 + c < N) ? n0 + c : N - 1;
     const float *zp = x + (size_t)nn * D + h;                    // channel k = 2s + h of token c at zp[2s]
 
-    float zr[S];
+    float zr[D / 2];
 #pragma unroll
-    for (int s = 0; s < S; ++s) zr[s] = zp[2 * s];
-
-    auto stage = [&](int t, float *buf) {
-        const char *src = (const char *)(tiles + (size_t)t * TILE_FLOATS);
-#pragma unroll
-        for (int i = 0; i < CHUNKS_PER_WAVE; ++i) {
-            int chunk = wave * CHUNKS_PER_WAVE + i;
-            glds16(src + chunk * 1024 + lane * 16, (char *)buf + chunk * 1024);
-        }
-        if (wave == 0) glds4(src + 32 * D * 4 + lane * 4, (char *)buf + 32 * D * 4);
-    };
+    for (int s = 0; s < D / 2; ++s) zr[s] = zp[2 * s];
 
     const int T = dvq_num_tiles(K);
-    stage(0, lds);
+    exact_stage<D>(tiles, 0, lds, wave, lane);
 
-    // ---- xn: ATen-order sum of squares of token c (vq_assign_exact.hip), then the 16 tokens of this lane's accumulator rows
+    // ---- xn of token c, then of the 16 tokens of this lane's accumulator rows
     float xnr[16];
     {
-        float p[16], o[16];
-#pragma unroll
-        for (int u = 0; u < 16; ++u) {
-            float a = sq_rn(zr[u]);
-#pragma unroll
-            for (int j = 1; j < S / 16; ++j) a = __fadd_rn(a, sq_rn(zr[u + 16 * j]));
-            p[u] = a;
-        }
-#pragma unroll
-        for (int u = 0; u < 16; ++u) o[u] = __shfl_xor(p[u], 32);
-        float tl[8];
-#pragma unroll
-        for (int l = 0; l < 8; ++l) {
-            float a4[4];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                int m = l + 8 * g;
-                float mine = p[m >> 1], other = o[m >> 1];
-                a4[g] = ((m & 1) == h) ? mine : other;
-            }
-            tl[l] = __fadd_rn(__fadd_rn(__fadd_rn(a4[0], a4[1]), a4[2]), a4[3]);
-        }
-        float xn = tl[0];
-#pragma unroll
-        for (int l = 1; l < 8; ++l) xn = __fadd_rn(xn, tl[l]);
+        const float xn = exact_token_sumsq<D>(zr, h);
 #pragma unroll
         for (int r = 0; r < 16; ++r) xnr[r] = __shfl(xn, (r & 3) + 8 * (r >> 2) + 4 * h);
     }
@@ -163,21 +118,11 @@ __global__ __launch_bounds__(256, 2) void vq_soft_assign_kernel(
     for (int t = 0; t < T; ++t) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();                      // tile t landed; everyone is done with tile t-1
-        float *buf = lds + (t & 1) * TILE_FLOATS;
-        if (t + 1 < T) stage(t + 1, lds + ((t + 1) & 1) * TILE_FLOATS);
+        float *buf = exact_buf<D>(lds, t);
+        if (t + 1 < T) exact_stage<D>(tiles, t + 1, exact_buf<D>(lds, t + 1), wave, lane);
 
         f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-        const float *ap = buf + c * 8 + h * 4;
-#pragma unroll
-        for (int kg = 0; kg < D / 8; ++kg) {
-            f32x4 a = *(const f32x4 *)(ap + kg * 256);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(zr[kg * 4 + 0], a[0], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(zr[kg * 4 + 1], a[1], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(zr[kg * 4 + 2], a[2], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(zr[kg * 4 + 3], a[3], acc, 0, 0, 0);
-        }
+        exact_tile_dots<D, true>(buf, zr, c, h, acc);
         const float en = buf[32 * D + c];
         const int code = t * 32 + c;
         const bool cvalid = code < K;
@@ -244,7 +189,7 @@ template <int D>
 static int launch_soft(const float *x, const float *tiles, int K, long N, float temp, const float *q, float *soft, float *dist,
                        float *sbuf, long long *codes, int vec, hipStream_t st)
 {
-    const size_t shmem = 2 * (32 * D + 64) * sizeof(float);
+    const size_t shmem = dvq_exact_lds_bytes(D);
     const dim3 grid((unsigned)((N + 127) / 128)), block(256);
     if (dist != nullptr && sbuf != nullptr)
         return dvq_launch_lds<vq_soft_assign_kernel<D, true, true>>(grid, block, shmem, st, x, tiles, K, N, temp, q, soft, dist, sbuf, codes, vec);
