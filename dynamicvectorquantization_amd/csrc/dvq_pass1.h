@@ -570,6 +570,16 @@ __device__ __forceinline__ void pass1_body(
                 zeta2 = __builtin_fmaf(r0, r0, zeta2);
                 zeta2 = __builtin_fmaf(r1, r1, zeta2);
             }
+            if constexpr (SEL == 2) {
+                // the copies of a coarser cell (every position but its first) score ZERO operands: their columns' results are
+                // never used -- the lane that owns the cell computes the same (best, second, code) from the same vector and
+                // hands them over behind the loop -- and a column of zeros costs the matrix cores less switching energy, which
+                // under the socket's power cap is time (section 5.1).  Norm, bound and zf above are the real vector's.
+                // (the empty asm ends the k-step's residual sums first, so that the words are replaced in place: selected while
+                // the conversion's results were still needed they took eight more registers, and the D = 256 kernels spilled)
+                asm volatile("" : "+v"(packed), "+v"(zeta2));
+                if (sel_mask < 0.0f) packed = u32x4{0u, 0u, 0u, 0u};
+            }
             const f16x8 zcur = __builtin_bit_cast(f16x8, packed);
             if (s & 1) {
                 // tokens 16 t2 + (lane & 15), k = 32 s' + 8 (lane >> 4) + j  <-  lane (c, h) = (16 t2 + (lane & 15), (lane >> 4) & 1),
@@ -736,6 +746,29 @@ __device__ __forceinline__ void pass1_body(
         code = (c >> 4) ? c1 : c0;
     }
     DVQ_STAMP(2);
+    if constexpr (SEL == 2) {
+        // the copies scored zeros (prologue): they take the triple of the lane that owns their cell -- the cell's first position,
+        // `y % rep` rows up and `x % rep` columns left, always in this workgroup (rows of 32 positions, four whole rows from a
+        // multiple of four, rep in {1, 2, 4}: staged_select_ok) -- through the waves' permutation scratch, idle since the prologue.
+        // A column's scores depend on its B values, the A fragments and the seeds, and the merge on the lane-group order, not on
+        // which column it is: the owner's triple is bit for bit what the copy computed from the same vector.
+        // Row, column and rep are re-derived here (wave = row, lane = column): nothing new lives in a VGPR through the loop.
+        const int lane_e = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+        const int c_e = lane_e & 31;
+        float am = __builtin_fabsf(sel_mask);
+        asm volatile("" : "+v"(am));                         // (opaque: nothing derived from it is computed ahead of the loop)
+        const int rm1 = (am == 1.0f) ? 0 : ((am == 0.25f) ? 1 : 3);             // rep - 1
+        char *hand = lds + NBUF * IMG_BYTES + NBUF * NW * 64 * 4;               // [wave][2 KiB]: 32 columns x 16 B in use
+        if (lane_e < 32) {
+            const f32x4 mine = {best, second, __int_as_float(code), 0.0f};
+            *(f32x4 *)(hand + wave * 2048 + c_e * 16) = mine;
+        }
+        __syncthreads();
+        const f32x4 own = *(const f32x4 *)(hand + (wave - (wave & rm1)) * 2048 + (c_e - (c_e & rm1)) * 16);
+        best = own[0];                                       // (a cell's first position reads back what it wrote)
+        second = own[1];
+        code = __float_as_int(own[2]);
+    }
     if constexpr (SPLIT) {
         // hand-off without fences (MI355X guide, inter-workgroup visibility: every payload store write-through (sc1) and drained by
         // its wave, the workgroup's barrier, ONE agent-scope add per workgroup; the workgroup whose add came last reads with sc1
@@ -820,7 +853,7 @@ __device__ __forceinline__ void pass1_body(
         if (zq != nullptr || partials != nullptr) {
             // (the lane half re-derived from the lane id: `8 * h` of the prologue does not live in a VGPR through the code loop)
             int h_e = h;                                     // (where it frees the register; elsewhere it costs some)
-            if constexpr (FOLD || (FLAT && SPLIT)) h_e = (int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >> 5);
+            if constexpr (FOLD || (FLAT && SPLIT) || SEL == 2) h_e =(int)(__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >> 5);
             const float *ep = E + (size_t)code * D + 8 * h_e;
             // gathers per batch: 2 k-steps (A/B on MI355X: 2 beats 1, 4, 8 and a 3-deep pipeline) where other workgroups hide the
             // latency; the split form's merging workgroup is alone on its CU and takes 8 (two round trips instead of eight)
