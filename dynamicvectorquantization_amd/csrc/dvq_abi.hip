@@ -7,7 +7,7 @@
 #include "../../include/dvq.h"
 #include "launchers.h"
 
-#define DVQ_VERSION 1700   // 0.17.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1701   // 0.17.1 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -636,6 +636,9 @@ int dvq_ema_update_f32(const float *stats_sum, const float *stats_count, float d
 size_t dvq_router_gate_workspace_bytes(int num_branches, int B, int C, int hc, int wc, int num_groups, int hidden)
 {
     if (num_branches < 2 || num_branches > 3 || B <= 0 || C <= 0 || hc <= 0 || wc <= 0 || num_groups < 0 || hidden < 0) return 0;
+    // a shape whose feature tile and output-layer rows the direct form cannot hold (dvq_router_gate_f32 refuses it in words)
+    if ((num_groups == 0 || C % num_groups == 0) &&
+        dvq_router_gate_lds_bytes(num_branches, C, hc, wc, num_groups, hidden > 0 ? hidden : 32, hidden > 0) > DVQ_GATE_LDS_MAX) return 0;
     return dvq_router_gate_ws_bytes(num_branches, B, C, hc, wc, num_groups, hidden > 0 ? hidden : 32);
 }
 
@@ -693,7 +696,13 @@ int dvq_router_gate_f32(int nb, const float *h_coarse, const float *h_median, co
     }
     if (C % 8 != 0 || nb * C > 1280) { dvq_set_error("%s: C=%d unsupported (C %% 8 == 0, num_branches*C <= 1280)", fn, C); return DVQ_EUNSUPPORTED; }
     if (num_groups > 0 && ((size_t)(C / num_groups) * hc * wc) % 4 != 0) { dvq_set_error("%s: group size not a multiple of 4 floats", fn); return DVQ_EUNSUPPORTED; }
-    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_router_gate_workspace_bytes(nb, B, C, hc, wc, num_groups, hidden))) return rc;
+    const int hid = activation == DVQ_ACT_NONE ? 32 : hidden;
+    if (const size_t lds = dvq_router_gate_lds_bytes(nb, C, hc, wc, num_groups, hid, activation); lds > DVQ_GATE_LDS_MAX) {
+        dvq_set_error("%s: num_branches=%d C=%d hidden=%d needs %zu bytes of LDS, %d available (128 * (num_branches*C rounded up to 16) + 4 * (1 + num_branches) * hidden)",
+                      fn, nb, C, hid, lds, DVQ_GATE_LDS_MAX);
+        return DVQ_EUNSUPPORTED;
+    }
+    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_router_gate_ws_bytes(nb, B, C, hc, wc, num_groups, hidden > 0 ? hidden : 32))) return rc;
     const float *h[3], *gw[3], *gb[3];
     if (nb == 2) {
         h[0] = h_coarse; h[1] = h_fine; h[2] = nullptr;
@@ -705,8 +714,7 @@ int dvq_router_gate_f32(int nb, const float *h_coarse, const float *h_median, co
         gb[0] = gn_b_coarse; gb[1] = gn_b_median; gb[2] = gn_b_fine;
     }
     return hip_rc(dvq_launch_router_gate(nb, h, gw, gb, B, C, hc, wc, num_groups, eps, w1, b1, w2, b2,
-                                         activation == DVQ_ACT_NONE ? 32 : hidden, activation, w1_prep, gate, ws,
-                                         (hipStream_t)stream), "router_gate");
+                                         hid, activation, w1_prep, gate, ws, (hipStream_t)stream), "router_gate");
 }
 
 // shared argument checks of the training-mode routing tail; fills the branch / parameter slots of *a

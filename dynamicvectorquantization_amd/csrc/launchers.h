@@ -80,6 +80,8 @@ int dvq_launch_code_stats_grain(const long long *codes, const long long *grain, 
 int dvq_launch_entropy_map(const float *img, int B, int H, int W, float *out, hipStream_t st);
 size_t dvq_router_gate_ws_bytes(int nb, int B, int C, int hc, int wc, int groups, int Hid);
 size_t dvq_router_gate_prep_bytes_impl(int nb, int C, int Hid);
+#define DVQ_GATE_LDS_MAX (160 * 1024 - 256)   // dynamic LDS the direct form of the gate opts in to (its static LDS takes the rest)
+size_t dvq_router_gate_lds_bytes(int nb, int C, int hc, int wc, int groups, int Hid, int act);
 int dvq_launch_router_gate_prepare(const float *W1, int nb, int C, int Hid, void *prep, hipStream_t st);
 int dvq_launch_restart_pick(unsigned long long seed, long long n, int k, long long *out, hipStream_t st);
 int dvq_launch_ema_update(const float *stats_sum, const float *stats_count, float decay, float eps, int K, int D,

@@ -907,6 +907,23 @@ static size_t gate_part_bytes(int nb, int B, int hc, int wc, int Hid)
 {
     return align256r((size_t)((Hid + 127) / 128) * 4 * B * hc * wc * nb * sizeof(float));       // one slice per row tile
 }
+// the GEMM form (gate_gemm_kernel): a hidden layer with GroupNorm'd inputs whose groups are whole octets of channels that fit the
+// pooling workgroup's LDS, F a multiple of 16 with a number of k-steps instantiated for this number of branches
+static bool gate_gemm_form(int nb, int C, int hc, int wc, int groups, int act)
+{
+    const int F = nb * C, S16 = F / 16;
+    const int cpg = groups > 0 ? C / groups : 0;
+    const bool steps = nb == 2 ? (S16 == 8 || S16 == 16 || S16 == 24 || S16 == 32) : (S16 == 12 || S16 == 24 || S16 == 48);
+    return act != 0 && groups > 0 && cpg % 8 == 0 && cpg <= 64 && (size_t)nb * cpg * hc * wc * 4 <= 48 * 1024 && F % 16 == 0 && steps;
+}
+// dynamic LDS of the direct form (router_gate_kernel) at one block of 32 cells: the split feature tile and the hidden bias +
+// output-layer rows; 0 for a shape that takes the GEMM form, whose LDS does not grow with the shape.  Hid = 32 without a hidden layer.
+size_t dvq_router_gate_lds_bytes(int nb, int C, int hc, int wc, int groups, int Hid, int act)
+{
+    if (gate_gemm_form(nb, C, hc, wc, groups, act)) return 0;
+    const size_t Fp = ((size_t)nb * C + 15) / 16 * 16;
+    return ((size_t)32 * Fp + (size_t)(1 + nb) * Hid) * sizeof(float);
+}
 size_t dvq_router_gate_ws_bytes(int nb, int B, int C, int hc, int wc, int groups, int Hid)
 {
     (void)groups;
@@ -1007,12 +1024,9 @@ int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn
     }
     const _Float16 *imgL = imgH ? imgH + (size_t)((Hid + 31) / 32) * 32 * Fp : nullptr;
     const float *wtail = imgH ? (const float *)((const char *)imgH + gate_img_bytes(nb, C, Hid)) : nullptr;   // act == 0: unused
-    // the GEMM form (gate_gemm_kernel): a hidden layer with GroupNorm'd inputs whose groups are whole octets of channels that fit the
-    // pooling workgroup's LDS, F a multiple of 16 with an instantiated number of k-steps
     const int cpg = groups > 0 ? C / groups : 0;
     const int S16 = F / 16;
-    const bool gemm_form = act != 0 && groups > 0 && cpg % 8 == 0 && cpg <= 64 && (size_t)nb * cpg * hc * wc * 4 <= 48 * 1024 &&
-                           F % 16 == 0 && (S16 == 8 || S16 == 12 || S16 == 16 || S16 == 24 || S16 == 32 || S16 == 48);
+    const bool gemm_form = gate_gemm_form(nb, C, hc, wc, groups, act);
     if (gemm_form) {
         // (prepared images carry the GroupNorm maxima in their tail when dvq_router_gate_prepare_norm_f32 ran; images rebuilt inside
         // this call do not)
@@ -1085,13 +1099,13 @@ int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn
         if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
         ncu = n > 0 ? n : 256;
     }
-    const bool cb2 = act != 0 && shmem2 <= 160 * 1024 - 512 && ncell >= 64L * ncu;
+    const bool cb2 = act != 0 && shmem2 <= DVQ_GATE_LDS_MAX - 256 && ncell >= 64L * ncu;
     const int CBv = cb2 ? 2 : 1;
     const unsigned grid = (unsigned)((ncell + 32 * CBv - 1) / (32 * CBv));
     const size_t shmem = cb2 ? shmem2 : ((size_t)32 * Fp + (size_t)(1 + nb) * Hid) * sizeof(float);
     // opted in to the LDS of the largest tile (not this launch's shmem), once per kernel and device
 #define DVQ_GATE_LAUNCH(GG, CC)                                                                                        \
-    dvq_launch_lds<router_gate_kernel<GG, CC>, 160 * 1024 - 256>(dim3(grid), dim3(GATE_NW * 64), shmem, st, a, stats,  \
+    dvq_launch_lds<router_gate_kernel<GG, CC>, DVQ_GATE_LDS_MAX>(dim3(grid), dim3(GATE_NW * 64), shmem, st, a, stats,  \
                                                                  pool, imgH, imgL, b1, W2, b2, Hid, act, gate, wtail)
     const int rc = nb == 2 ? (cb2 ? DVQ_GATE_LAUNCH(2, 2) : DVQ_GATE_LAUNCH(2, 1))
                            : (cb2 ? DVQ_GATE_LAUNCH(3, 2) : DVQ_GATE_LAUNCH(3, 1));

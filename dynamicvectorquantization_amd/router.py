@@ -298,7 +298,9 @@ def fused_router_gate(gate, gate_type, norms, branches, weight_prep=None):
     out = torch.empty((B, hc, wc, nb), dtype=torch.float32, device=dev)
     ws_bytes = checked.dvq_router_gate_workspace_bytes(nb, B, C, hc, wc, groups, hidden)
     if ws_bytes == 0:
-        raise _lib.DvqError("unsupported router shape")
+        raise _lib.DvqError("unsupported router shape: num_branches=%d C=%d hidden=%d (the 32-cell feature tile and the output-layer "
+                            "rows must fit the LDS: 128 * (num_branches*C rounded up to 16) + 4 * (1 + num_branches) * hidden <= 163584, "
+                            "hidden = 32 for 1layer-fc)" % (nb, C, hidden))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     ptr = lambda t: None if t is None else t.data_ptr()
     med = hs[1] if nb == 3 else None

@@ -30,6 +30,10 @@
  *     dvq_vq_assign_narrow_*_f32 below; every other entry point refuses them as before.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.17.1 dvq_router_gate_f32 refuses (DVQ_EUNSUPPORTED, naming the bytes) a shape whose 32-cell feature tile and output-layer rows do not
+ *          fit one workgroup's LDS -- until now it failed in the launch with a bare HIP status -- and dvq_router_gate_workspace_bytes
+ *          returns 0 for it; a dual router of C = 96 or 384 behind GroupNorm groups of whole octets of channels, until now a launch
+ *          failure as well, is served.  Nothing else changed.
  *   0.17.0 DVQ_DTYPE_F16 / DVQ_DTYPE_BF16, dvq_vq_assign_nchw_x16, dvq_vq_backward_nchw_x16, dvq_ema_accumulate_nchw_x16 (new): the dense
  *          assign, its backward and the EMA statistics on fp16 / bf16 latents (an encoder run under autocast), everything else float32.
  *          Nothing else changed.
@@ -461,7 +465,13 @@ DVQ_API int dvq_code_stats_grain_f32(const int64_t *codes, const int64_t *grain,
  * num_branches nb = 2 (h_median must be NULL; h_fine is 2x the coarse grid) or 3 (median 2x, fine 4x).
  * h_* are [B, C, rows, cols] f32 NCHW; num_groups == 0 means normalization_type "none" (gn_* ignored),
  * otherwise gn_w_* / gn_b_* are the [C] affine parameters of each branch's GroupNorm(num_groups, C, eps).
- * gate [B, hc, wc, nb] f32 logits.  C % 8 == 0, nb*C <= 1280.  The hidden layer runs on the fp16 matrix
+ * gate [B, hc, wc, nb] f32 logits.  C % 8 == 0, nb*C <= 1280 and, with Fp = nb*C rounded up to 16 and
+ * H = hidden (32 for DVQ_ACT_NONE), 128 * Fp + 4 * (1 + nb) * H <= 163584: the feature tile of 32 cells and
+ * the output-layer rows share one workgroup's LDS.  (Exempt: a hidden layer behind GroupNorms whose groups
+ * are 8, 16, ... 64 channels with nb * (C / num_groups) * hc * wc * 4 <= 49152 and nb*C one of 128, 256, 384,
+ * 512 (nb = 2) or 192, 384, 768 (nb = 3) -- that form keeps the weights in registers, any hidden width.)
+ * DVQ_EUNSUPPORTED names the bytes needed otherwise, and dvq_router_gate_workspace_bytes returns 0.
+ * The hidden layer runs on the fp16 matrix
  * cores with both operands split hi + lo (hi*hi + hi*lo + lo*hi, fp32 accumulation: 2^-22 products);
  * summation order differs from ATen/MKL: logits equal the reference within 1e-4, not bit for bit.
  */

@@ -16,13 +16,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = os.path.join(ROOT, "tests", "golden", "abi_rejections.json")
 TOOL = os.path.join(ROOT, "tools", "gen_golden_abi_rejections.py")
 # one row per distinct check at the least: assign (f32, x16, flat), backward and EMA pairs, qconv, fold, a dual and a triple routed
-# entry, soft, score, both apply_codes, both gumbel, both narrow entries, the two prepares
+# entry, soft, score, both apply_codes, both gumbel, both narrow entries, the two prepares, the router gate
 _PER_CHECK = {"dvq_vq_assign_nchw_f32": 8, "dvq_vq_assign_nchw_x16": 11, "dvq_vq_assign_flat_f32": 2, "dvq_vq_backward_nchw_f32": 5,
               "dvq_vq_backward_nchw_x16": 7, "dvq_ema_accumulate_nchw_f32": 2, "dvq_ema_accumulate_nchw_x16": 4, "dvq_vq_assign_qconv_f32": 11,
               "dvq_vq_assign_fold_f32": 10, "dvq_vq_assign_routed_dual_f32": 10, "dvq_vq_assign_routed_triple_f32": 11,
               "dvq_vq_soft_assign_flat_f32": 8, "dvq_vq_score_assign_f32": 8, "dvq_vq_apply_codes_nchw_f32": 8, "dvq_vq_apply_codes_flat_f32": 1,
               "dvq_gumbel_prepare_f32": 4, "dvq_vq_gumbel_assign_f32": 9, "dvq_vq_assign_narrow_nchw_f32": 8, "dvq_vq_assign_narrow_flat_f32": 9,
-              "dvq_codebook_prepare_f32": 4, "dvq_fold_prepare_f32": 4}
+              "dvq_codebook_prepare_f32": 4, "dvq_fold_prepare_f32": 4, "dvq_router_gate_f32": 13}
 
 
 def test_the_abi_refuses_what_it_refused_with_the_same_words():

@@ -213,6 +213,17 @@ ladder("dvq_ortho_loss_backward_f32", d(_ortho[0], grad=8), *_ortho[1:], d(t=P),
 ladder("dvq_lucid_update_f32", d(kind=2, counts=0, embed_avg=0, K=0, cluster_size_out=P, decay=2.0, embed=512, x=0), d(kind=0), d(counts=P), d(embed_avg=512),
        d(kind=1, sums=0), d(sums=P), d(K=8), d(cluster_size_out=1024), d(embed=1024), d(decay=0.5, threshold=-1.0), d(threshold=0.0))
 
+# the direct form of the router gate keeps a 32-cell feature tile and the output-layer rows in LDS: what does not fit is refused in
+# words (a triple router of C = 384 with the default hidden width, a dual single-layer router of C = 640, a small router with a very
+# wide hidden layer), behind the group-size check and before the workspace's; the second ladder walks the checks of a dual router
+_fits = d(num_groups=0, hc=4, wc=4, ws_bytes=BIG)
+ladder("dvq_router_gate_f32", d(_fits, num_branches=3, C=384, activation=1, hidden=1152))
+ladder("dvq_router_gate_f32", d(_fits, num_branches=2, h_median=0, C=640, activation=0, hidden=0))
+ladder("dvq_router_gate_f32", d(_fits, num_branches=2, h_median=0, C=8, activation=1, hidden=16384))
+ladder("dvq_router_gate_f32", d(num_branches=2, gate=0, h_median=P, wc=0, activation=-1, b1=0, hidden=16384, num_groups=-1, gn_b_coarse=0, C=12,
+                                ws=0, ws_bytes=BIG), d(gate=P), d(h_median=0), d(wc=1), d(activation=2), d(b1=P), d(num_groups=3), d(gn_b_coarse=P),
+       d(C=24, num_groups=12), d(num_groups=3), d(hidden=64), d(ws=16))
+
 
 def rows(protos):
     out = []
