@@ -3,6 +3,7 @@
 // by one translation unit per (D, resident seed table) -- vq_pass1_d<D>[_res].hip, each a call of launch_pass1_res<D, RES> --
 // so no kernel handle crosses an object boundary; the wide form (vq_pass1_wide.hip) and the resolver (vq_resolve.hip) are
 // units of their own and take the host-side types from here.
+// The code loop's text is pass1_loop.h, included by pass1_body once per form (long / the short form of SEL == 2).
 #pragma once
 #include "dvq_filter.h"
 #include <type_traits>
@@ -530,6 +531,27 @@ __device__ __forceinline__ void pass1_body(
     }
     f16x8 zb[2][S32];                                        // B operands of the 16x16x32 loop, [token half][k-step of 32]
     float xn, thr2W;
+    // SEL == 2, the order of a wave's columns: the real ones first (in column order), the copies of a coarser cell behind them.  A
+    // column's scores depend on its B values and not on where it sits, so the order is free; with at most 16 real columns the
+    // second column group (t2 = 1) holds copies only, whose results nobody reads, and the wave runs the code loop without it
+    // (the short form, below).  copymask: bit c = column c is a copy (wave-uniform, in scalar registers through the loop).
+    unsigned copymask = 0u;
+    unsigned perm_off[2] = {0u, 0u};                         // scratch byte offset of the column at sorted position 16 t2 + (lane & 15)
+    if constexpr (SEL == 2) {
+        copymask = (unsigned)__builtin_amdgcn_ballot_w64(sel_mask < 0.0f && h == 0);
+        // column c sits at pos(c): a real column at its rank among the real ones, a copy at nreal + its rank among the copies.
+        // The inverse (position -> column), 32 bytes, goes through the wave's scratch (idle until the first k-step pair; a wave's
+        // LDS operations execute in order).  No copies: pos(c) = c, and the offsets are the ones the dense form computes.
+        const int below = __builtin_popcount(copymask & ((1u << c) - 1u));
+        const int p = (sel_mask < 0.0f) ? 32 - __builtin_popcount(copymask) + below : c - below;
+        unsigned char *tab = (unsigned char *)scr;
+        if (h == 0) tab[p] = (unsigned char)c;
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+            const unsigned col = tab[16 * t2 + (lane & 15)];
+            perm_off[t2] = (unsigned)(lane >> 5) * 1024u + (col + 32u * ((unsigned)(lane >> 4) & 1u)) * 16u;
+        }
+    }
     {
         float pa[2][8];
         float amax = 0.0f, zeta2 = 0.0f;
@@ -590,8 +612,12 @@ __device__ __forceinline__ void pass1_body(
                 *(f16x8 *)(scr + 1024 + lane * 16) = zcur;
 #pragma unroll
                 for (int t2 = 0; t2 < 2; ++t2) {
+                    if constexpr (SEL == 2) {
+                        zb[t2][sp] = *(const f16x8 *)(scr + perm_off[t2]);
+                    } else {
                     const int srcl = 16 * t2 + (lane & 15) + 32 * ((lane >> 4) & 1);
                     zb[t2][sp] = *(const f16x8 *)(scr + (lane >> 5) * 1024 + srcl * 16);
+                    }
                 }
             }
             zprev = zcur;
@@ -638,81 +664,25 @@ __device__ __forceinline__ void pass1_body(
         // r03_pass1_loop_ablation.json).  Moving the top-2 update into the shadow of the MFMAs (one code half behind them, no
         // second accumulator set) changed nothing, as that model predicts: 42.7k vs 42.6k cycles per loop
         // (profiles/archive/r03_pass1_half_tile_pipelining.json; git history has the code).
-        f32x4 acc16[2][2];
-        auto top2 = [&](int tt) {
-#pragma unroll
-            for (int t2 = 0; t2 < 2; ++t2) {
-                const float om = b1[t2];
-#pragma unroll
-                for (int r = 0; r < 8; r += 2) {             // r = 4 c2 + i
-                    // running top-2 over the pair (g0, g1): with b2 <= b1 the new second-best is max(b2, med3(b1, g0, g1))
-                    // and the new best max3(b1, g0, g1): 2.5 VALU ops per score; the register index rides in 4 mantissa bits
-                    const float v0 = acc16[r >> 2][t2][r & 3], v1 = acc16[(r + 1) >> 2][t2][(r + 1) & 3];
-                    float g0 = __uint_as_float((__float_as_uint(v0) & 0xFFFFFFF0u) | (unsigned)r);
-                    float g1 = __uint_as_float((__float_as_uint(v1) & 0xFFFFFFF0u) | (unsigned)(r + 1));
-                    float md = __builtin_amdgcn_fmed3f(b1[t2], g0, g1);
-                    b1[t2] = vmax3_raw(b1[t2], g0, g1);
-                    b2[t2] = vmax_raw(b2[t2], md);
-                }
-                bt[t2] = (b1[t2] != om) ? tt : bt[t2];
-            }
-        };
-    for (int t = 0; t < T; ++t) {
-            asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_TILE) : "memory");   // all but the youngest tile's DMA: tiles <= t + 1 landed
-            __builtin_amdgcn_s_barrier();                    // tile t (everybody's DMA) landed; t-1 consumed
-            asm volatile("" ::: "memory");
-            if (S16 != 16) issue(t + 3);                     // D = 256: pieces ride between the MFMAs below
-            // A fragments: hand-placed LDS reads, four k-steps ahead of the MFMA that consumes them
-            // (ds_read returns in order: lgkmcnt(3) = "the oldest of my four reads has landed")
-            const unsigned tile_a = (unsigned)(size_t)(const __attribute__((address_space(3))) char *)(
-                                        lds + (t & (NBUF - 1)) * IMG_BYTES + lane * 16);
-            f16x8 a0, a1, a2, a3;
-#define DVQ_RD(dst, S) asm volatile("ds_read_b128 %0, %1 offset:%c2" : "=v"(dst) : "v"(tile_a), "i"((S) * 1024))
-            DVQ_RD(a0, 0); DVQ_RD(a1, 1); DVQ_RD(a2, 2); DVQ_RD(a3, 3);
-            __builtin_amdgcn_sched_barrier(0);
-            if (t > 0) top2(t - 1);
-            __builtin_amdgcn_sched_barrier(0);
-            {
-                // accumulator seeds of tile t, read behind the fragments: from the resident table (landed before tile 0's barrier),
-                // or from this wave's own DMA copy (landed by the wait above)
-                const unsigned seed_a = (unsigned)(size_t)(const __attribute__((address_space(3))) char *)(
-                                            RES ? enraw + t * 32 + 4 * q16 : enraw + ((t & (NBUF - 1)) * NW + wave) * 64 + 4 * q16);
-                f32x4 e0, e1;
-                asm volatile("ds_read_b128 %0, %1" : "=v"(e0) : "v"(seed_a));
-                asm volatile("ds_read_b128 %0, %1 offset:64" : "=v"(e1) : "v"(seed_a));
-                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(e0), "+v"(e1), "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) :: "memory");
-                acc16[0][0] = e0; acc16[0][1] = e0; acc16[1][0] = e1; acc16[1][1] = e1;
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#define DVQ_PIECE(Q) if constexpr ((Q) < PER_TILE) { issue_piece(t + 3, Q); }
-#define DVQ_MM(src, F, WAIT, NEXT)                                                                             \
-            asm volatile("s_waitcnt lgkmcnt(" #WAIT ")" ::: "memory");                                            \
-            __builtin_amdgcn_sched_barrier(0);                                                                    \
-            acc16[(F) / S32][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(src, zb[0][(F) % S32], acc16[(F) / S32][0], 0, 0, 0); \
-            acc16[(F) / S32][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(src, zb[1][(F) % S32], acc16[(F) / S32][1], 0, 0, 0); \
-            __builtin_amdgcn_sched_barrier(0);                                                                    \
-            if ((F) + 4 < S16) { DVQ_RD(src, ((F) + 4 < S16 ? (F) + 4 : 0)); }                                  \
-            NEXT
-            __builtin_amdgcn_s_setprio(1);
-            if (S16 == 16) {
-                // the next ring tile's DMA pieces are issued between MFMAs: each ~100-cycle issue stall
-                // then overlaps the MFMA already in the pipe instead of preceding the whole chain
-                DVQ_MM(a0, 0, 0, ) DVQ_MM(a1, 1, 1, DVQ_PIECE(0)) DVQ_MM(a2, 2, 2, ) DVQ_MM(a3, 3, 3, )
-                DVQ_MM(a0, 4, 3, DVQ_PIECE(1)) DVQ_MM(a1, 5, 3, ) DVQ_MM(a2, 6, 3, ) DVQ_MM(a3, 7, 3, DVQ_PIECE(2))
-                DVQ_MM(a0, 8, 3, ) DVQ_MM(a1, 9, 3, ) DVQ_MM(a2, 10, 3, DVQ_PIECE(3)) DVQ_MM(a3, 11, 3, )
-                DVQ_MM(a0, 12, 3, ) DVQ_MM(a1, 13, 2, DVQ_PIECE(4)) DVQ_MM(a2, 14, 1, ) DVQ_MM(a3, 15, 0, )
-            } else if (S16 == 8) {
-                DVQ_MM(a0, 0, 0, ) DVQ_MM(a1, 1, 1, ) DVQ_MM(a2, 2, 2, ) DVQ_MM(a3, 3, 3, )
-                DVQ_MM(a0, 4, 3, ) DVQ_MM(a1, 5, 2, ) DVQ_MM(a2, 6, 1, ) DVQ_MM(a3, 7, 0, )
+        // SEL == 2: a wave with at most 16 real columns runs the SHORT form of the loop: column group t2 = 0 alone -- half the MFMAs,
+        // half the top-2 update, half the re-seed -- and everything the workgroup shares as in the long form: the counted vmcnt wait,
+        // the tile barrier, the DMA pieces of tile t + 3 at the same fragments, all 16 A-fragment reads and their counted waits.
+        // One scalar branch around the loop picks the form; no wave leaves the ring's protocol.
+        if constexpr (SEL == 2) {
+            if (__builtin_popcount(copymask) >= 16) {        // short wave: nreal <= 16 (wave-uniform, decided before the loop)
+#define DVQ_NG 1
+#include "pass1_loop.h"
+#undef DVQ_NG
             } else {
-                DVQ_MM(a0, 0, 0, ) DVQ_MM(a1, 1, 0, ) DVQ_MM(a2, 2, 0, ) DVQ_MM(a3, 3, 0, )
+#define DVQ_NG 2
+#include "pass1_loop.h"
+#undef DVQ_NG
             }
-#undef DVQ_MM
-#undef DVQ_RD
-#undef DVQ_PIECE
-            __builtin_amdgcn_s_setprio(0);
+        } else {
+#define DVQ_NG 2
+#include "pass1_loop.h"
+#undef DVQ_NG
         }
-        top2(T - 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // surplus ring DMA
         // merge the four lane groups of a token column (lower lane wins ties), then hand the results to the lanes
         // that own the token in the (c, h) layout of the prologue / epilogue
@@ -737,6 +707,23 @@ __device__ __forceinline__ void pass1_body(
             rs[t2] = ms;
             rc[t2] = (mt + t_lo) * 32 + 16 * (r >> 2) + 4 * mq + (r & 3);
         }
+        if constexpr (SEL == 2) {
+            // the column's sorted position pos(c) again, from the mask and the lane id (nothing of the prologue's lives in a VGPR
+            // through the loop).  A short wave's positions >= 16 are copies: what they pick from the unscored group is replaced by
+            // their owner's triple below.
+            unsigned cm = copymask;
+            asm volatile("" : "+s"(cm));                     // (opaque: derived behind the loop, not kept from the prologue)
+            const int c_p = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & 31;
+            const int below = __builtin_popcount(cm & ((1u << c_p) - 1u));
+            const int pc = ((cm >> c_p) & 1u) ? 32 - __builtin_popcount(cm) + below : c_p - below;
+            const int srcl = pc & 15;
+            const float x0 = __shfl(rb[0], srcl), x1 = __shfl(rb[1], srcl);
+            const float y0 = __shfl(rs[0], srcl), y1 = __shfl(rs[1], srcl);
+            const int c0 = __shfl(rc[0], srcl), c1 = __shfl(rc[1], srcl);
+            best = (pc >> 4) ? x1 : x0;
+            second = (pc >> 4) ? y1 : y0;
+            code = (pc >> 4) ? c1 : c0;
+        } else {
         const int srcl = c & 15;
         const float x0 = __shfl(rb[0], srcl), x1 = __shfl(rb[1], srcl);
         const float y0 = __shfl(rs[0], srcl), y1 = __shfl(rs[1], srcl);
@@ -744,6 +731,7 @@ __device__ __forceinline__ void pass1_body(
         best = (c >> 4) ? x1 : x0;
         second = (c >> 4) ? y1 : y0;
         code = (c >> 4) ? c1 : c0;
+        }
     }
     DVQ_STAMP(2);
     if constexpr (SEL == 2) {
