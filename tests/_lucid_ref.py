@@ -12,6 +12,7 @@ top-2 gap of the perturbed scores is below
 float64| and max |-sqrt(oracle d) - float64| over the fixture, measured by the generator and stored in the .npz), its noise within
 G_ERR (tests/_maskvq_ref.py), plus one fp32 ulp of the best perturbed score for the roundings of the add.  At most SKIP_CAP of a
 fixture's tokens may be in that set."""
+import collections
 import os
 
 import numpy as np
@@ -85,6 +86,35 @@ def ortho64(t):
     loss = (m ** 2).sum() / n ** 2
     g = (4.0 / n ** 2) * (m @ c)
     return loss, (g - c * (c * g).sum(-1, keepdims=True)) / nrm
+
+
+def ortho64_heads(t):
+    """orthogonal_loss_fn of t [h, n, d] in float64: the mean of the heads' losses, each head's gradient divided by h"""
+    parts = [ortho64(th) for th in t]
+    return float(np.mean([p[0] for p in parts])), np.stack([p[1] for p in parts]) / len(parts)
+
+
+OrthoGeom = collections.namedtuple("OrthoGeom", "T gx gy idle s0 S tper last")
+
+
+def ortho_geometry(h, n):
+    """dvq_ortho_grid and dvq_ortho_backward_slices (csrc/ortho_loss.hip) restated.  T: 32-row tiles; forward grid gx x gy x h
+    (four column tiles per workgroup, OL_ROWCHUNK = 8 row tiles per chunk), idle: waves of the last forward workgroup without a
+    column tile; s0: the first estimate of the backward slice count (about 1024 waves, at most 8, at most T), S: the count after
+    rounding the tiles per slice (tper) up, last: the column tiles of the last slice"""
+    T = (n + 31) // 32
+    gx, gy = (T + 3) // 4, (T + 7) // 8
+    s0 = min(max(1024 // max(T * h, 1), 1), 8, T)
+    tper = (T + s0 - 1) // s0
+    S = (T + tper - 1) // tper
+    return OrthoGeom(T, gx, gy, 4 * gx - T, s0, S, tper, T - (S - 1) * tper)
+
+
+def ortho_workspace_bytes(h, n, d):
+    """dvq_ortho_loss_workspace_bytes restated: the larger of the forward partials (one double per workgroup) and the backward
+    slices' partial gradients (S x [h, n, d] floats), rounded up to 256 bytes"""
+    g = ortho_geometry(h, n)
+    return (max(g.gx * g.gy * h * 8, g.S * h * n * d * 4) + 255) // 256 * 256
 
 
 def train_step(kind, rows, codes, embed, embed_avg, cluster_size, decay, eps, threshold, picks):
