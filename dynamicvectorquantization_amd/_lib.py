@@ -179,6 +179,23 @@ def on_device(device):
     return torch.cuda.device(device)
 
 
+def is_channels_last(t):
+    """a 4-D [B, C, H, W] tensor in torch.channels_last memory format and NOT also contiguous (C = 1 or H = W = 1 satisfy both and
+    stay NCHW): byte for byte the row-major matrix [B H W, C], which `channels_last_rows` views it as"""
+    return t.dim() == 4 and not t.is_contiguous() and t.is_contiguous(memory_format=torch.channels_last)
+
+
+def channels_last_rows(t):
+    """the [B H W, C] view of a channels_last tensor (no copy: the permuted tensor is contiguous)"""
+    return t.permute(0, 2, 3, 1).reshape(-1, t.shape[1])
+
+
+def rows_channels_last(rows, shape):
+    """the inverse: rows [B H W, C] seen as the channels_last tensor of `shape` = (B, C, H, W)"""
+    B, C, H, W = shape
+    return rows.view(B, H, W, C).permute(0, 3, 1, 2)
+
+
 def require_cuda_f32(t, name):
     if not isinstance(t, torch.Tensor):
         raise TypeError("%s must be a torch.Tensor" % name)
@@ -189,9 +206,14 @@ def require_cuda_f32(t, name):
     return t if t.is_contiguous() else t.contiguous()
 
 
-def require_cuda_latents(t, name):
+def require_cuda_latents(t, name, keep_channels_last=False):
     """require_cuda_f32 for LATENTS: float32, or float16 / bfloat16 (the *_x16 entry points of the dense assign, its backward
-    and the EMA statistics); everything that is not a latent-shaped tensor stays with require_cuda_f32"""
+    and the EMA statistics); everything that is not a latent-shaped tensor stays with require_cuda_f32.
+    keep_channels_last: a channels_last tensor (is_channels_last) comes back as it is, for the caller to serve as rows; every
+    other layout that is not contiguous is copied as before."""
+    if isinstance(t, torch.Tensor) and t.is_cuda and (t.dtype in X16 or t.dtype == torch.float32) and keep_channels_last \
+            and is_channels_last(t):
+        return t
     if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype in X16:
         return t if t.is_contiguous() else t.contiguous()
     if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype != torch.float32:

@@ -7,7 +7,7 @@
 #include "../../include/dvq.h"
 #include "launchers.h"
 
-#define DVQ_VERSION 1701   // 0.17.1 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1800   // 0.18.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -469,6 +469,10 @@ static int backward_nchw(const char *fn, int dtype, const void *z, const float *
     if (D % 16 != 0) { dvq_set_error("%s: D=%d must be a multiple of 16", fn, D); return DVQ_EUNSUPPORTED; }
     if ((((uintptr_t)codebook) & 15) != 0) { dvq_set_error("%s: codebook must be 16-byte aligned", fn); return DVQ_EINVAL; }
     if (dtype != 0 && (((uintptr_t)z | (uintptr_t)g_zq | (uintptr_t)g_z) & 1) != 0) { dvq_set_error("%s: z, g_zq and g_z must be 2-byte aligned", fn); return DVQ_EINVAL; }
+    // HW == 1 is a row-major matrix [B, D]: the kernel whose lanes own 16-byte pieces of a row (train_rows.hip), where its pieces are aligned
+    if (HW == 1 && (((uintptr_t)z | (uintptr_t)g_zq | (uintptr_t)g_z) & 15) == 0)
+        return hip_rc(dvq_launch_vq_backward_rows(z, dtype, codebook, (const long long *)codes, mask, g_zq, g_loss, coef_scale, D, K, (long)B,
+                                                  g_z, (hipStream_t)stream), fn);
     return hip_rc(dvq_launch_vq_backward_z(z, dtype, codebook, (const long long *)codes, mask, g_zq, g_loss, coef_scale, D, HW, K,
                                            (long)B * HW, g_z, (hipStream_t)stream), fn);
 }
@@ -497,6 +501,9 @@ int dvq_vq_backward_codebook_nchw_f32(const float *z, const float *codebook, con
     if (!z || !codebook || !codes || !g_loss || !g_weight) return null_pointer(fn);
     if (B <= 0 || HW <= 0 || K <= 0 || D <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     if (K > 8192) { dvq_set_error("%s: K=%d > 8192 (index_add the differences instead)", fn, K); return DVQ_EUNSUPPORTED; }
+    if (HW == 1)                                            // row-major [B, D]: lane = channel straight from the rows, no LDS transpose
+        return hip_rc(dvq_launch_codebook_grad_rows(z, codebook, (const long long *)codes, mask, g_loss, coef_scale, D, (long)B, K, g_weight,
+                                                    (hipStream_t)stream), fn);
     return hip_rc(dvq_launch_codebook_grad(z, codebook, (const long long *)codes, mask, g_loss, coef_scale, D, HW, (long)B * HW, K,
                                            g_weight, (hipStream_t)stream), fn);
 }
@@ -567,6 +574,9 @@ static int ema_accumulate_nchw(const char *fn, int dtype, const void *z, const i
     if (!z || !codes || !cluster_size || !vectors_sum) return null_pointer(fn);
     if (dtype != 0 && ((uintptr_t)z & 1) != 0) { dvq_set_error("%s: z must be 2-byte aligned", fn); return DVQ_EINVAL; }
     if (B <= 0 || D <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
+    if (HW == 1)                                            // row-major [B, D] (train_rows.hip; any K)
+        return hip_rc(dvq_launch_ema_accumulate_rows(z, dtype, (const long long *)codes, D, (long)B, K, cluster_size, vectors_sum,
+                                                     (hipStream_t)stream), dtype != 0 ? fn : "ema_accumulate");
     return hip_rc(dvq_launch_ema_accumulate(z, dtype, (const long long *)codes, D, HW, (long)B * HW, K, cluster_size, vectors_sum,
                                             (hipStream_t)stream), dtype != 0 ? fn : "ema_accumulate");
 }

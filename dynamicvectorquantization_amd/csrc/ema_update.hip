@@ -177,6 +177,16 @@ __global__ __launch_bounds__(256) void ema_zero_kernel(float *__restrict__ a, si
     for (size_t i = i0; i < nb; i += stride) b[i] = 0.0f;
 }
 
+// a [na] and b [nb] (na <= nb) zeroed by a kernel, not hipMemsetAsync: memset nodes misbehave under hipGraph replay on ROCm 7.2
+int dvq_launch_ema_zero(float *a, size_t na, float *b, size_t nb, hipStream_t st)
+{
+    int blocks = (int)((nb / 4 + 255) / 256);
+    if (blocks > 2048) blocks = 2048;
+    if (blocks < 1) blocks = 1;
+    hipLaunchKernelGGL(ema_zero_kernel, dim3(blocks), dim3(256), 0, st, a, na, b, nb);
+    return (int)hipGetLastError();
+}
+
 // ---------------------------------------------------------------------------------------------
 // The same statistics with a BIG tile whose tokens are SORTED by code (N >= 65 536 tokens, K <= 4096, HW % 4 == 0, D % 16 == 0).
 // The kernel above is bound by the L2 float-atomic rate (67 M adds at B = 256 = 308 us) and a 64-token tile has nothing to combine
@@ -197,9 +207,13 @@ __global__ __launch_bounds__(256) void ema_zero_kernel(float *__restrict__ a, si
 #define EMS_STR (EMS_BT + 4)
 static_assert(EMS_BC == 16 && EMS_BT % 256 == 0 && EMS_BT * EMS_BC == 32768, "the walk's lane mapping (four 16-channel groups per wave) and the 128 load pieces assume this tile");
 #define EMS_LONG 128             // a code with more tokens than this in a tile is summed by ALL lane groups, 32 tokens each
-__global__ __launch_bounds__(1024) void ema_accumulate_sorted_kernel(const float *__restrict__ z, const long long *__restrict__ codes,
-                                                                    int D, int HW, long N, int K, float *__restrict__ cluster_size,
-                                                                    float *__restrict__ vectors_sum)
+// ROWS: the latents are row-major [N, D] (HW unused; D % 16 == 0, 16-byte aligned z, any N): a piece is four channels of one token,
+// a token's 16 channels of the slice are 64 contiguous bytes, and the piece is transposed into the [channel][token] tile as it is
+// stored to LDS; sorting and walk are the same.
+template <bool ROWS>
+__device__ __forceinline__ void ema_accumulate_sorted_body(const float *__restrict__ z, const long long *__restrict__ codes,
+                                                           int D, int HW, long N, int K, float *__restrict__ cluster_size,
+                                                           float *__restrict__ vectors_sum)
 {
     constexpr int NT = 1024, NWV = NT / 64, PPW = 128 / NWV, PPC = EMS_BT / 256, CPI = 64 / EMS_BC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -227,6 +241,14 @@ __global__ __launch_bounds__(1024) void ema_accumulate_sorted_kernel(const float
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
             const int q = wave * PPW + i;                                // piece: channel q / PPC, tokens (q % PPC) * 256 + 4 lane ..
+            if constexpr (ROWS) {                                        // piece: token (64 q + lane) / 4, channels 4 ((64 q + lane) % 4) ..
+                const int L = q * 64 + lane;
+                long n = tok0 + (L >> 2);
+                n = n < N ? n : N - 1;
+                // (a plain load: the other half of this 128-byte line belongs to the next slice, which a workgroup nearby reads soon)
+                v[i] = *(const f32x4 *)(z + (size_t)n * D + c0 + 4 * (L & 3));
+                continue;
+            }
             const int ch = q / PPC, t4 = (q % PPC) * 256 + 4 * lane;
             long n = tok0 + t4;
             n = n < N ? n : (N - 4 > 0 ? N - 4 : 0);                     // (HW % 4 == 0: N is a multiple of 4)
@@ -284,6 +306,12 @@ __global__ __launch_bounds__(1024) void ema_accumulate_sorted_kernel(const float
 #pragma unroll
         for (int i = 0; i < PPW; ++i) {
             const int q = wave * PPW + i;
+            if constexpr (ROWS) {
+                const int L = q * 64 + lane;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) tile[(4 * (L & 3) + j) * EMS_STR + (L >> 2)] = v[i][j];
+                continue;
+            }
             const int ch = q / PPC, t4 = (q % PPC) * 256 + 4 * lane;
             *(f32x4 *)(tile + ch * EMS_STR + t4) = v[i];
         }
@@ -367,20 +395,48 @@ __global__ __launch_bounds__(1024) void ema_accumulate_sorted_kernel(const float
     }
 }
 
+__global__ __launch_bounds__(1024) void ema_accumulate_sorted_kernel(const float *__restrict__ z, const long long *__restrict__ codes,
+                                                                    int D, int HW, long N, int K, float *__restrict__ cluster_size,
+                                                                    float *__restrict__ vectors_sum)
+{
+    ema_accumulate_sorted_body<false>(z, codes, D, HW, N, K, cluster_size, vectors_sum);
+}
+
+__global__ __launch_bounds__(1024) void ema_accumulate_sorted_rows_kernel(const float *__restrict__ z, const long long *__restrict__ codes,
+                                                                         int D, long N, int K, float *__restrict__ cluster_size,
+                                                                         float *__restrict__ vectors_sum)
+{
+    ema_accumulate_sorted_body<true>(z, codes, D, 1, N, K, cluster_size, vectors_sum);
+}
+
+// dynamic LDS (tile + order / rank / code_s + the K + 1 offsets) and grid (one workgroup per CU at most) of the two sorted kernels
+static unsigned ems_launch_shape(int D, long N, int K, size_t *shm)
+{
+    *shm = (size_t)EMS_BC * EMS_STR * 4 + (size_t)EMS_BT * 6 + ((size_t)K + 1) * 4;
+    int ncu = 256, dev = 0;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+    const long nitems = ((N + EMS_BT - 1) / EMS_BT) * (D / EMS_BC);
+    return (unsigned)(nitems < ncu ? nitems : (ncu > 0 ? ncu : 256));
+}
+
+// The sorted kernel on row-major float32 latents [N, D] (outputs already zeroed), where its conditions hold: as many tokens and as
+// few codes as the NCHW dispatch below asks for, D % 16 == 0, z 16-byte aligned.  -1: they do not hold, nothing was launched.
+int dvq_launch_ema_accumulate_sorted_rows(const float *z, const long long *codes, int D, long N, int K, float *cluster_size,
+                                          float *vectors_sum, hipStream_t st)
+{
+    if (!(K <= 4096 && (D & 15) == 0 && N >= 32 * EMS_BT && ((uintptr_t)z & 15) == 0)) return -1;
+    size_t shm;
+    const unsigned grid = ems_launch_shape(D, N, K, &shm);
+    return dvq_launch_lds<ema_accumulate_sorted_rows_kernel>(dim3(grid), dim3(1024), shm, st, z, codes, D, N, K, cluster_size, vectors_sum);
+}
+
 // xt = 0: float32 latents, the sorted kernel where its shape conditions hold, else the tile-transpose kernel.  16-bit latents
 // (xt = DVQ_DTYPE_F16 / DVQ_DTYPE_BF16): always the tile-transpose kernel.  Equal codes of a tile are combined up to K = 8192.
 int dvq_launch_ema_accumulate(const void *zv, int xt, const long long *codes, int D, int HW, long N, int K,
                               float *cluster_size, float *vectors_sum, hipStream_t st)
 {
     if (xt < 0 || xt > 2) return -1000;
-    // zeroed by a kernel, not hipMemsetAsync: memset nodes misbehave under hipGraph replay on ROCm 7.2
-    {
-        size_t n = (size_t)K * D;
-        int blocks = (int)((n / 4 + 255) / 256);
-        if (blocks > 2048) blocks = 2048;
-        if (blocks < 1) blocks = 1;
-        hipLaunchKernelGGL(ema_zero_kernel, dim3(blocks), dim3(256), 0, st, cluster_size, (size_t)K, vectors_sum, n);
-    }
+    if (int rc = dvq_launch_ema_zero(cluster_size, (size_t)K, vectors_sum, (size_t)K * D, st)) return rc;
     if (xt != 0) {
         const dim3 grid((unsigned)((N + 63) / 64));
         const bool combine = K <= 8192;
@@ -396,11 +452,8 @@ int dvq_launch_ema_accumulate(const void *zv, int xt, const long long *codes, in
     }
     const float *z = (const float *)zv;
     if (K <= 4096 && (HW & 3) == 0 && (D & 15) == 0 && N >= 32 * EMS_BT) {
-        const size_t shm = (size_t)EMS_BC * EMS_STR * 4 + (size_t)EMS_BT * 6 + ((size_t)K + 1) * 4;
-        int ncu = 256, dev = 0;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-        const long nitems = ((N + EMS_BT - 1) / EMS_BT) * (D / EMS_BC);
-        const unsigned grid = (unsigned)(nitems < ncu ? nitems : (ncu > 0 ? ncu : 256));
+        size_t shm;
+        const unsigned grid = ems_launch_shape(D, N, K, &shm);
         return dvq_launch_lds<ema_accumulate_sorted_kernel>(dim3(grid), dim3(1024), shm, st, z, codes, D, HW, N, K, cluster_size,
                                                             vectors_sum);
     }

@@ -47,6 +47,18 @@ int dvq_launch_ema_accumulate(const void *z, int xt, const long long *codes, int
                               float *cluster_size, float *vectors_sum, hipStream_t st);
 int dvq_launch_codebook_grad(const float *z, const float *E, const long long *codes, const float *mask, const float *g_loss,
                              float coef_scale, int D, int HW, long N, int K, float *gw, hipStream_t st);
+// the same three for row-major latents [N, D] (train_rows.hip; a channels_last image map is such a matrix): the backward reads
+// 16-byte pieces of a row (D % 16 == 0, 16-byte aligned z, g_zq, gz, E), the two sums read per element and have no limit on K;
+// the C ABI picks them for HW == 1
+int dvq_launch_vq_backward_rows(const void *z, int xt, const float *E, const long long *codes, const float *mask, const void *g_zq,
+                                const float *g_loss, float coef_scale, int D, int K, long N, void *gz, hipStream_t st);
+int dvq_launch_ema_accumulate_rows(const void *z, int xt, const long long *codes, int D, long N, int K, float *cluster_size,
+                                   float *vectors_sum, hipStream_t st);
+int dvq_launch_codebook_grad_rows(const float *z, const float *E, const long long *codes, const float *mask, const float *g_loss,
+                                  float coef_scale, int D, long N, int K, float *gw, hipStream_t st);
+int dvq_launch_ema_zero(float *a, size_t na, float *b, size_t nb, hipStream_t st);
+int dvq_launch_ema_accumulate_sorted_rows(const float *z, const long long *codes, int D, long N, int K, float *cluster_size,
+                                          float *vectors_sum, hipStream_t st);   // -1: not its shape, nothing launched
 int dvq_launch_embed_gather(const float *E, int K, int D, const long long *idx, long n, float *out,
                             hipStream_t st);
 

@@ -302,6 +302,23 @@ def _vq_assign_padded(z, codebook, prep, mask, beta, want_zq, want_loss, mode, o
     return zq, codes, loss
 
 
+def _vq_assign_channels_last(z, codebook, prep, mask, beta, want_zq, want_loss, mode, out):
+    """vq_assign for a channels_last [B, C, H, W] tensor: its bytes are the row-major matrix [B H W, C], so the row entry points
+    (`dvq_vq_assign_flat_f32`, `dvq_vq_assign_nchw_x16` with HW = 1, `dvq_vq_assign_narrow_flat_f32`) serve it in place -- no transposing copy in, and
+    z_q comes back channels_last for the convolution behind it.  codes [B, H, W]; a mask [B, 1, H, W] is [N] in memory already."""
+    B, C, H, W = z.shape
+    out_rows = None
+    if out is not None:
+        zq, codes, loss = out
+        if zq is not None and not (zq.shape == z.shape and _lib.is_channels_last(zq)):
+            raise ValueError("out: z_q of a channels_last z must be a channels_last tensor of its shape")
+        out_rows = (None if zq is None else _lib.channels_last_rows(zq), None if codes is None else codes.view(-1), loss)
+    zq, codes, loss = vq_assign(_lib.channels_last_rows(z), codebook, prep, mask, beta, want_zq, want_loss, mode, out_rows)
+    if out is not None:
+        return out
+    return (None if zq is None else _lib.rows_channels_last(zq, z.shape)), codes.view(B, H, W), loss
+
+
 def vq_assign(z, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=True,
               mode=_lib.MODE_FILTER, out=None, conv=None, h_buf=None, fold=False):
     """z [B, D, *spatial] f32 cuda, codebook [K, D] -> (zq or None, codes [B, *spatial] i64, loss[2] or None).
@@ -320,8 +337,12 @@ def vq_assign(z, codebook, prep, mask=None, beta=0.25, want_zq=True, want_loss=T
     float16 / bfloat16 z (an encoder run under autocast; `dvq_vq_assign_nchw_x16`): codes and loss are those of the op on
     z.float(), z_q that op's rounded once to z.dtype (what `.to(z.dtype)` gives) -- no cast pass on either side.  The codebook,
     mask and loss stay float32.  Kernel widths and the zero-padded ones only: the narrow widths, conv= and fold= raise TypeError
-    (they take float32)."""
-    z = _lib.require_cuda_latents(z, "z") if (conv is None and not fold) else _lib.require_cuda_f32(z, "z")
+    (they take float32).
+    A channels_last [B, C, H, W] z (`_lib.is_channels_last`) is served in place as the rows [B H W, C]: z_q comes back channels_last,
+    codes [B, H, W]; with conv= / fold= it is copied to NCHW as before."""
+    z = _lib.require_cuda_latents(z, "z", keep_channels_last=True) if (conv is None and not fold) else _lib.require_cuda_f32(z, "z")
+    if _lib.is_channels_last(z):
+        return _vq_assign_channels_last(z, codebook, prep, mask, beta, want_zq, want_loss, mode, out)
     codebook = _lib.require_cuda_f32(codebook, "codebook")
     B, D = z.shape[0], z.shape[1]
     x16 = _lib.X16.get(z.dtype, 0)
@@ -733,7 +754,10 @@ class _VQStraightThrough(torch.autograd.Function):
     d/dz runs as ONE kernel (`dvq_vq_backward_nchw_f32`: read z and g_zq, gather e from the snapshot, write g_z) in the same fp32
     operation order as the torch expression below, which remains the path for CPU tensors / odd channel counts.
     float16 / bfloat16 z: `dvq_vq_backward_nchw_x16` (g_zq of z's dtype or None; g_z comes back in it).  The CODEBOOK gradient of
-    16-bit latents (`dvq_vq_backward_codebook_nchw_f32` is float32-only) takes the torch expression on z.float()."""
+    16-bit latents (`dvq_vq_backward_codebook_nchw_f32` is float32-only) takes the torch expression on z.float().
+    Row-major z -- 2-D [N, D], HW == 1 by shape, or a channels_last [B, C, H, W] tensor, which is [B H W, C] in memory -- is passed
+    as B = N, HW = 1, for which the same entry points run kernels whose accesses follow the rows (csrc/train_rows.hip): the same
+    arithmetic.  g_z has z's shape, strides and dtype."""
 
     @staticmethod
     def forward(ctx, z, weight, mask, prep, K, coef_z, coef_e, mode):
@@ -765,34 +789,41 @@ class _VQStraightThrough(torch.autograd.Function):
         scale = 2.0 / z.numel()
         gz, gw = None, None
         x16 = _lib.X16.get(z.dtype, 0) if z.is_cuda else 0
-        fused = (need_z and z.is_cuda and (z.dtype == torch.float32 or x16) and D % 16 == 0 and z.is_contiguous()
+        # the layout of the saved z: channels_last [B, C, H, W] is the row-major matrix [B H W, C] and is read as it lies
+        nhwc = z.is_cuda and _lib.is_channels_last(z)
+        dense = z.is_contiguous() or nhwc
+        n_tok = z.numel() // D if D else 0
+        HW = 1 if nhwc else (n_tok // B if B else 1)
+        fused = (need_z and z.is_cuda and (z.dtype == torch.float32 or x16) and D % 16 == 0 and dense
                  and (g_zq is None or (g_zq.dtype == z.dtype and g_zq.device == z.device)))
         if need_z and g_loss is None:
             gz = g_zq
         elif fused:
-            HW = z[0, 0].numel()
-            gq = None if g_zq is None else g_zq.contiguous()
+            if g_zq is None:
+                gq = None
+            else:
+                gq = g_zq.contiguous(memory_format=torch.channels_last) if nhwc else g_zq.contiguous()
             gl = g_loss.reshape(1).to(torch.float32).contiguous()
             m = None if mask is None else _lib.require_cuda_f32(mask, "codebook_mask")
-            gz = torch.empty_like(z)
+            gz = torch.empty_like(z)                      # z's strides: channels_last stays channels_last
             with _lib.on_device(z.device):
+                # row-major z (HW == 1: B = the number of tokens): the entry points run the kernel whose lanes own pieces of a row
                 if x16:
                     checked.dvq_vq_backward_nchw_x16(
                         z.data_ptr(), x16, snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), _lib.ptr(gq), gl.data_ptr(),
-                        float(ctx.coef_z * scale), B, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device))
+                        float(ctx.coef_z * scale), n_tok // HW, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device))
                 else:
                     checked.dvq_vq_backward_nchw_f32(
                         z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), _lib.ptr(gq), gl.data_ptr(),
-                        float(ctx.coef_z * scale), B, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device))
-        if need_w and g_loss is not None and z.is_cuda and z.dtype == torch.float32 and z.is_contiguous() and snap.shape[0] <= 8192:
-            HW = z[0, 0].numel()
+                        float(ctx.coef_z * scale), n_tok // HW, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device))
+        if need_w and g_loss is not None and z.is_cuda and z.dtype == torch.float32 and dense and snap.shape[0] <= 8192:
             gw = torch.zeros(ctx.wshape, dtype=z.dtype, device=z.device)
             gl = g_loss.reshape(1).to(torch.float32).contiguous()
             m = None if mask is None else _lib.require_cuda_f32(mask, "codebook_mask")
             with _lib.on_device(z.device):
                 checked.dvq_vq_backward_codebook_nchw_f32(
                     z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), gl.data_ptr(), float(ctx.coef_e * scale),
-                    B, D, HW, snap.shape[0], gw.data_ptr(), _lib.stream_ptr(z.device))
+                    n_tok // HW, D, HW, snap.shape[0], gw.data_ptr(), _lib.stream_ptr(z.device))
             need_w = False                                # done
         diff = None
         if (need_z and gz is None) or (need_w and g_loss is not None):
@@ -802,6 +833,8 @@ class _VQStraightThrough(torch.autograd.Function):
                 diff = diff * mask.reshape(B, 1, *z.shape[2:])
         if need_z and gz is None:
             gz = ((g_zq if g_zq is not None else 0) + g_loss * (ctx.coef_z * scale) * diff).to(z.dtype)
+            if nhwc:
+                gz = gz.contiguous(memory_format=torch.channels_last)
         if need_w or (gw is None and ctx.needs_input_grad[1]):
             gw = torch.zeros(ctx.wshape, dtype=snap.dtype, device=z.device)
             if g_loss is not None and need_w:
@@ -910,43 +943,59 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
         tiled = x.repeat(-(-target_n // n), 1)
         return tiled + torch.rand_like(tiled) * (0.01 / math.sqrt(dim))
 
+    def _kernel_latents(self, vectors, nchw):
+        """(z, B, HW) -- the GPU tensor the statistics and update kernels read in place -- or None (CPU tensors, other dtypes, an
+        empty batch): the NCHW latents `nchw` [B, D, *spatial], or without them the token rows `vectors` [..., D] as the row-major
+        matrix [N, D] (B = N, HW = 1; a channels_last image map is passed as such rows)"""
+        t = vectors if nchw is None else nchw
+        if not (t.is_cuda and (t.dtype == torch.float32 or t.dtype in _lib.X16)) or t.numel() == 0:
+            return None
+        if nchw is None:
+            z = vectors.reshape(-1, self.weight.shape[-1]).contiguous()
+            return z, z.shape[0], 1
+        z = nchw.contiguous()
+        return z, z.shape[0], z[0, 0].numel()
+
     @torch.no_grad()
     def _cluster_sums(self, vectors, idxs, nchw=None):
         """cluster_size [K] and vectors_sum_per_cluster [K, D] (quantize2_mask.py:74-84), returned as
         views of ONE flat [K*D + K] buffer so the data-parallel reduction is a single collective.
-        The reference builds a dense one-hot [K, N] matrix and multiplies.  With the NCHW latents at
-        hand (`nchw` = z [B, D, *spatial], the layout the quantizer receives) one HIP kernel
-        (`dvq_ema_accumulate_nchw_f32`) produces both; otherwise a bincount and an index_add.
-        Either way the summation order differs from the reference: tolerance-level parity."""
+        The reference builds a dense one-hot [K, N] matrix and multiplies.  On the GPU one HIP kernel produces both, reading
+        the latents where they lie (`dvq_ema_accumulate_nchw_f32` / `_x16`): NCHW latents (`nchw` = z [B, D, *spatial], the
+        layout the quantizer receives), or token rows (`vectors` [..., D] alone) as B = N, HW = 1, the row-major form; CPU
+        tensors take a bincount and an index_add.  Either way the summation order differs from the reference: tolerance-level parity."""
         n_embed, embed_dim = self.weight.shape[0] - 1, self.weight.shape[-1]
         flat = torch.empty(n_embed * embed_dim + n_embed, dtype=torch.float32, device=vectors.device)
         vsum = flat[:n_embed * embed_dim].view(n_embed, embed_dim)
         cluster_size = flat[n_embed * embed_dim:]
-        if nchw is not None and nchw.is_cuda and (nchw.dtype == torch.float32 or nchw.dtype in _lib.X16):
-            z = nchw.contiguous()
-            B, HW = z.shape[0], z[0, 0].numel()
+        lat = self._kernel_latents(vectors, nchw)
+        if lat is not None:
+            z, B, HW = lat
             codes = idxs.reshape(B, HW).contiguous()
+            x16 = _lib.X16.get(z.dtype, 0)               # 16-bit latents: summed in float32 from the exact widened values
+            out = (cluster_size.data_ptr(), vsum.data_ptr(), _lib.stream_ptr(z.device))
             with _lib.on_device(z.device):
-                if z.dtype in _lib.X16:                  # 16-bit latents: summed in float32 from the exact widened values
-                    checked.dvq_ema_accumulate_nchw_x16(
-                        z.data_ptr(), _lib.X16[z.dtype], codes.data_ptr(), B, embed_dim, HW, n_embed, cluster_size.data_ptr(),
-                        vsum.data_ptr(), _lib.stream_ptr(z.device))
+                if x16:
+                    checked.dvq_ema_accumulate_nchw_x16(z.data_ptr(), x16, codes.data_ptr(), B, embed_dim, HW, n_embed, *out)
                 else:
-                    checked.dvq_ema_accumulate_nchw_f32(
-                        z.data_ptr(), codes.data_ptr(), B, embed_dim, HW, n_embed, cluster_size.data_ptr(),
-                        vsum.data_ptr(), _lib.stream_ptr(z.device))
+                    checked.dvq_ema_accumulate_nchw_f32(z.data_ptr(), codes.data_ptr(), B, embed_dim, HW, n_embed, *out)
         else:
             cluster_size.copy_(torch.bincount(idxs, minlength=n_embed))
             vsum.zero_().index_add_(0, idxs, vectors.to(torch.float32))
         return cluster_size, vsum, flat
 
     @torch.no_grad()
-    def _update_buffers(self, vectors, idxs, nchw=None):
+    def _update_buffers(self, vectors, idxs, nchw=None, fused=False):
         """Training-mode EMA statistics + dead-code restart (quantize2_mask.py:66-105).  Data-parallel:
         the reference's two all_reduce calls (:87-88) are one all_reduce over the flat [K*D + K]
-        statistics buffer; the restart vectors are broadcast from rank 0 as in :100."""
+        statistics buffer; the restart vectors are broadcast from rank 0 as in :100.
+        fused=True (`_ema_step`): where the latents allow it, the whole step INCLUDING `_update_embedding` as the statistics
+        kernel plus `dvq_ema_update_f32`; returns True when it did that -- the weight is written, nothing is left to do --
+        and otherwise runs as without the flag and returns False."""
         n_embed, embed_dim = self.weight.shape[0] - 1, self.weight.shape[-1]
         idxs = idxs.reshape(-1)
+        if fused and self._fused_step(vectors, idxs, nchw):
+            return True
         if nchw is None or not (nchw.is_cuda and (nchw.dtype == torch.float32 or nchw.dtype in _lib.X16)):
             vectors = vectors.reshape(-1, embed_dim)      # token rows (with NCHW latents on the GPU they are never materialised:
             nchw = None                                   # `vectors` stays the permuted VIEW [B, HW, D], rows are picked by index)
@@ -957,38 +1006,47 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
         self.embed_ema.mul_(self.decay).add_(vectors_sum_per_cluster, alpha=1 - self.decay)
         if self.restart_unused_codes:
             self._restart_dead_codes(vectors, self._draw_restart_vectors(vectors))
+        return False
 
     @torch.no_grad()
     def _ema_step(self, vectors, idxs, nchw=None):
-        """`_update_buffers` + `_update_embedding` (quantize2_mask.py:66-115) for NCHW latents on the GPU: the statistics kernel,
-        the (single) all-reduce, the restart pick, then ONE kernel for the two EMA updates, the dead-code restart and the
-        normalised weight (`dvq_ema_update_f32`; as torch ops ~20 launches of 4-5 us per step).  Anything else -- CPU tensors,
-        fewer input vectors than codes (the reference tiles them with noise), a replaced torch.randperm with too few vectors for
-        the pick kernel -- takes the two methods one after the other."""
-        n_embed, embed_dim = self.weight.shape[0] - 1, self.weight.shape[-1]
-        x16 = nchw is not None and nchw.is_cuda and nchw.dtype in _lib.X16
-        ok = (nchw is not None and nchw.is_cuda and (nchw.dtype == torch.float32 or x16) and self.weight.is_cuda
-              and self.weight.dtype == torch.float32 and self.weight.is_contiguous()
-              and self.embed_ema.is_contiguous() and self.embed_ema.dtype == torch.float32)
-        n_vectors = idxs.numel()
-        if not ok or (self.restart_unused_codes and n_vectors < n_embed):
-            self._update_buffers(vectors, idxs, nchw=nchw)
+        """`_update_buffers` + `_update_embedding` (quantize2_mask.py:66-115) for latents on the GPU -- NCHW (`nchw`) or token
+        rows (`vectors` [..., D] alone: channel-last callers, the items of VectorQuantize2List, every depth of RQBottleneck, a
+        channels_last image map) -- float32 / float16 / bfloat16: the statistics kernel, the (single) all-reduce, the restart pick,
+        then ONE kernel for the two EMA updates, the dead-code restart and the normalised weight (`dvq_ema_update_f32`; as torch
+        ops ~20 launches of 4-5 us per step).  Anything else -- CPU tensors, fewer input vectors than codes (the reference tiles
+        them with noise) -- takes the two methods one after the other."""
+        if not self._update_buffers(vectors, idxs, nchw=nchw, fused=True):
             self._update_embedding()
-            return
-        idxs = idxs.reshape(-1)
-        cluster_size, vectors_sum, flat = self._cluster_sums(vectors, idxs, nchw)
+
+    def _fused_step(self, vectors, idxs, nchw):
+        """the fused form of `_ema_step`; False (nothing done) where it does not apply"""
+        n_embed, embed_dim = self.weight.shape[0] - 1, self.weight.shape[-1]
+        n_vectors = idxs.numel()
+        if not (self.weight.is_cuda and self.weight.dtype == torch.float32 and self.weight.is_contiguous()
+                and self.embed_ema.is_contiguous() and self.embed_ema.dtype == torch.float32):
+            return False
+        if self.restart_unused_codes and n_vectors < n_embed:
+            return False
+        lat = self._kernel_latents(vectors, nchw)
+        if lat is None:
+            return False
+        z, B, HW = lat
+        x16 = z.dtype in _lib.X16
+        cluster_size, vectors_sum, flat = self._cluster_sums(z if nchw is None else vectors, idxs, nchw)
         ddp = dist.is_available() and dist.is_initialized()
         if ddp:
             dist.all_reduce(flat, op=dist.ReduceOp.SUM)
-        z = nchw.contiguous()
-        B, HW = z.shape[0], z[0, 0].numel()
         restart, rows, pick = 0, None, None
         if self.restart_unused_codes:
             pick = _restart_pick(n_vectors, n_embed, z.device).contiguous()
             restart = 2
             if ddp or x16:                                   # every rank restarts from rank 0's vectors (quantize2_mask.py:100);
                 # 16-bit latents: dvq_ema_update_f32 reads float32 rows, so the K picked rows are gathered and widened here
-                rows = vectors[torch.div(pick, HW, rounding_mode="floor"), pick % HW].to(torch.float32).contiguous()
+                if HW == 1:
+                    rows = z.reshape(B, embed_dim)[pick].to(torch.float32).contiguous()
+                else:
+                    rows = vectors[torch.div(pick, HW, rounding_mode="floor"), pick % HW].to(torch.float32).contiguous()
                 if ddp:
                     dist.broadcast(rows, 0)
                 restart = 1
@@ -1000,6 +1058,7 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
                 restart, _lib.ptr(rows), 0 if x16 else z.data_ptr(), B, HW, _lib.ptr(pick), _lib.stream_ptr(z.device))
         self.cluster_size_ema.copy_(cs_new)
         self._prep.invalidate()
+        return True
 
     @torch.no_grad()
     def _draw_restart_vectors(self, vectors):
@@ -1039,11 +1098,9 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
     def forward(self, inputs):
         """inputs [..., D] -> (embeds [..., D], idxs [...]) (quantize2_mask.py:117-128)."""
         embed_idxs = self.find_nearest_embedding(inputs)
+        embeds = self.embed(embed_idxs)                  # from the weight the search used: the step below rewrites it
         if self.training and self.ema:
-            self._update_buffers(inputs, embed_idxs)
-        embeds = self.embed(embed_idxs)
-        if self.ema and self.training:
-            self._update_embedding()
+            self._ema_step(inputs.detach(), embed_idxs)
         return embeds, embed_idxs
 
     def embed(self, idxs):
@@ -1126,12 +1183,13 @@ class VectorQuantize2(_CodebookOps, nn.Module):
                                                    float(self.beta), 1.0, self.assign_mode)
         if self.training and self.codebook.ema:
             with torch.no_grad():
-                if self.accept_image_fmap or need_transpose:     # channel-major -> token rows (a view)
+                if z.is_cuda and _lib.is_channels_last(z):      # NHWC bytes are token rows already
+                    self.codebook._ema_step(_lib.channels_last_rows(z.detach()), codes.reshape(-1))
+                elif self.accept_image_fmap or need_transpose:  # channel-major -> token rows (a view)
                     ztok = z.reshape(z.shape[0], z.shape[1], -1).permute(0, 2, 1)
                     self.codebook._ema_step(ztok, codes.reshape(-1), nchw=z.detach())
                 else:
-                    self.codebook._update_buffers(z, codes.reshape(-1))
-                    self.codebook._update_embedding()
+                    self.codebook._ema_step(z.detach(), codes.reshape(-1))
         if self.accept_image_fmap or need_transpose:
             x_q = zq
             x_code = codes                               # [B, H, W] / [B, N]
@@ -1195,8 +1253,7 @@ class VectorQuantize2List(_CodebookOps, nn.Module):
                                                       float(self.beta), 1.0, self.assign_mode)
             if self.training and self.codebook.ema:
                 with torch.no_grad():
-                    self.codebook._update_buffers(z, codes.reshape(-1))
-                    self.codebook._update_embedding()
+                    self.codebook._ema_step(z.detach(), codes.reshape(-1))
             loss = loss + l_i
             xq_list.append(zq.reshape(x.shape))
             code_list.append(codes.reshape(x.shape[:-1]))

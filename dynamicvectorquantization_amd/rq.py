@@ -8,7 +8,8 @@ runs, in order:
      reference's argmin bit for bit;
   2. `dvq_rq_step_f32`: agg / residual / loss partial / gradient sum / codes[:, i] (and on the last depth the straight-through
      output in latent layout) in one streaming pass;
-  3. in training only, that codebook's EMA update on (r_i, c_i) (`_update_buffers` + `_update_embedding`), so with
+  3. in training only, that codebook's EMA update on (r_i, c_i) (`VQEmbedding._ema_step` on the residual rows: the row-major
+     statistics kernel and `dvq_ema_update_f32`), so with
      `shared_codebook=True` depth i + 1 searches the codebook depth i has just updated, as in the reference.
 then `dvq_rq_loss_f32`.  Codes and `out` equal the reference bit for bit, the loss to 1e-5 relative.  The backward is one kernel
 (`dvq_rq_backward_f32`); the codebooks, EMA buffers, get no gradient, as in the reference.
@@ -112,8 +113,7 @@ def _rq_forward(mod, x, want_grad, want_loss, training, assign=None):
                 codes.data_ptr(), out.data_ptr(), ws.data_ptr(), ws.numel(), stream)
             if training and cb.ema:
                 with torch.no_grad():
-                    cb._update_buffers(r, c)
-                    cb._update_embedding()
+                    cb._ema_step(r, c)
             if i + 1 < depth:
                 off = checked.dvq_rq_residual_offset(N, D, depth, i + 1)
                 r = ws[off:off + N * D * 4].view(torch.float32).view(N, D)

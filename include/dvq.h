@@ -30,6 +30,10 @@
  *     dvq_vq_assign_narrow_*_f32 below; every other entry point refuses them as before.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.18.0 Row-major latents [N, D] -- token rows, or a channels_last (NHWC) image map, which is the same bytes -- on the training side:
+ *          dvq_vq_backward_nchw_f32 / _x16, dvq_vq_backward_codebook_nchw_f32 and dvq_ema_accumulate_nchw_f32 / _x16 called with B = N,
+ *          HW = 1 run kernels whose accesses follow the rows (the backward: where z, g_zq and g_z are 16-byte aligned; same bits as
+ *          before).  With HW = 1 dvq_ema_accumulate_nchw_* combines equal codes of a tile for every K.  No signature, status or message changed.
  *   0.17.1 dvq_router_gate_f32 refuses (DVQ_EUNSUPPORTED, naming the bytes) a shape whose 32-cell feature tile and output-layer rows do not
  *          fit one workgroup's LDS -- until now it failed in the launch with a bare HIP status -- and dvq_router_gate_workspace_bytes
  *          returns 0 for it; a dual router of C = 96 or 384 behind GroupNorm groups of whole octets of channels, until now a launch
@@ -358,7 +362,11 @@ DVQ_API int dvq_debug_fold_scores_f32(const float *tokens, int n, const void *fo
  *   callers keep a snapshot, the EMA update rewrites the weight between forward and backward), coef_scale = 2 c / numel.
  * One streaming pass (the reference: five or six element-wise passes and a transposed copy of e); same fp32 operation order
  * as that expression.  g_zq nullable (only the loss was used), g_loss nullable (only z_q was used; a device scalar otherwise),
- * mask nullable; D % 16 == 0.
+ * mask nullable; D % 16 == 0 (DVQ_EUNSUPPORTED otherwise); codebook 16-byte aligned (DVQ_EINVAL).
+ * HW == 1 is the ROW-MAJOR form, z / g_zq / g_z [N, D] with B = N (token rows, or a channels_last image map [B, C, H, W] with
+ * N = B H W): since 0.18.0 a lane then owns 16-byte pieces of a token's row instead of one token at a channel stride of HW, provided z,
+ * g_zq and g_z are 16-byte aligned (what torch allocates; a view at another offset is served by the strided kernel, an order of
+ * magnitude slower at HW == 1).  The same bits either way.
  */
 DVQ_API int dvq_vq_backward_nchw_f32(const float *z, const float *codebook, const int64_t *codes, const float *mask,
                              const float *g_zq, const float *g_loss, float coef_scale,
@@ -366,7 +374,9 @@ DVQ_API int dvq_vq_backward_nchw_f32(const float *z, const float *codebook, cons
 /* ... and with respect to a codebook trained by back-propagation (VectorQuantizer2, quantize_vqgan.py:290-298; no EMA):
  *   g_weight[j, :] += -(g_loss * coef_scale) * sum over tokens with code j of (z - codebook[j]) * mask
  * ACCUMULATES into g_weight [>= K rows, D] (zero it first); float atomics, one row per distinct code of a 64-token tile:
- * equal to the reference's index_add_ of the [N, D] differences up to summation order.  K <= 8192. */
+ * equal to the reference's index_add_ of the [N, D] differences up to summation order.  K <= 8192 (DVQ_EUNSUPPORTED above).
+ * HW == 1 (row-major z [N, D], B = N; since 0.18.0): a wave reads 64 consecutive channels of a token straight from its row, any D, any
+ * 4-byte aligned z; the K limit stays part of the contract although that kernel needs no table. */
 DVQ_API int dvq_vq_backward_codebook_nchw_f32(const float *z, const float *codebook, const int64_t *codes, const float *mask,
                                       const float *g_loss, float coef_scale, int B, int D, int HW, int K,
                                       float *g_weight, void *stream);
@@ -388,6 +398,10 @@ DVQ_API size_t dvq_vq_assign_routed_fallback_count_offset(int num_branches, int 
  *   cluster_size[j] = #tokens with code j, vectors_sum[j, :] = sum of those tokens' vectors.
  * z [B, D, HW] f32 (NCHW), codes [B, HW] int64; both outputs are overwritten.  Codes outside
  * [0, K) are ignored.  Float atomics: equal to the reference within rounding (1e-5).
+ * Equal codes of a 64-token tile are summed before the atomics up to K = 8192; float32 latents with B * HW >= 65536, K <= 4096,
+ * D % 16 == 0 and HW % 4 == 0 take a 2048-token tile sorted by code.  HW == 1 (row-major z [N, D], B = N; since 0.18.0): rows are read
+ * where they lie (any D, z aligned to its element), equal codes are summed at every K, and the sorted tile applies to float32 rows
+ * with N >= 65536, K <= 4096, D % 16 == 0 and a 16-byte aligned z.  dvq_ema_accumulate_nchw_x16 follows the same rules, without the sorted tile.
  */
 DVQ_API int dvq_ema_accumulate_nchw_f32(const float *z, const int64_t *codes, int B, int D, int HW, int K,
                                 float *cluster_size, float *vectors_sum, void *stream);
