@@ -47,6 +47,12 @@ DTYPE_F16, DTYPE_BF16 = 1, 2   # DVQ_DTYPE_*: the 16-bit latents of the *_x16 en
 X16 = {torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
 
 
+def FEATURES(dtype):
+    """DVQ_FEATURES(dtype) of include/dvq.h for a torch dtype: the flag OR-ed into `gate_dtype` of the route selects and `activation`
+    of the router gate when the branch features are fp16 / bf16; 0 for float32"""
+    return X16.get(dtype, 0) << 8
+
+
 class DvqError(RuntimeError):
     pass
 

@@ -7,7 +7,7 @@
 #include "../../include/dvq.h"
 #include "launchers.h"
 
-#define DVQ_VERSION 1800   // 0.18.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 1900   // 0.19.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -526,23 +526,45 @@ int dvq_entropy_gate_f32(const float *entropy, int64_t n, float thr, int64_t *ga
     return hip_rc(dvq_launch_entropy_gate(entropy, (long)n, thr, (long long *)gate, (hipStream_t)stream), "entropy_gate");
 }
 
-static int route_args_ok(const char *fn, const void *gate, int gate_dtype, const float *a, const float *b,
-                         int B, int C, int hc, int wc, float *h_out, int64_t *indices, float *cmask)
+// DVQ_FEATURES(dtype) OR-ed into the one enumerated argument of the select / gate entry points: the enumerator is the low byte,
+// the feature dtype the bits above it (0 = float32).  A negative value carries no flag: it is an unknown enumerator as a whole.
+static int enum_of(int v) { return v < 0 ? v : (v & 0xFF); }
+static int features_of(int v) { return v < 0 ? 0 : (v >> 8); }
+
+static int check_features(const char *fn, int xt)
+{
+    if (xt == 0 || xt == DVQ_DTYPE_F16 || xt == DVQ_DTYPE_BF16) return DVQ_OK;
+    dvq_set_error("%s: DVQ_FEATURES dtype %d (0 = float32, DVQ_DTYPE_F16 = 1, DVQ_DTYPE_BF16 = 2)", fn, xt);
+    return DVQ_EINVAL;
+}
+
+// gate_dtype: DVQ_GATE_F32 / DVQ_GATE_I64, with DVQ_FEATURES(dtype) for 2-byte features (a, b, h_out then hold such elements)
+static int route_args_ok(const char *fn, const void *gate, int gate_dtype, const void *a, const void *b,
+                         int B, int C, int hc, int wc, void *h_out, int64_t *indices, float *cmask)
 {
     if (!gate || !a || !b || !h_out || !indices || !cmask) return null_pointer(fn);
-    if (gate_dtype != DVQ_GATE_F32 && gate_dtype != DVQ_GATE_I64) { dvq_set_error("%s: gate_dtype %d", fn, gate_dtype); return DVQ_EINVAL; }
+    const int gd = enum_of(gate_dtype);
+    if (gd != DVQ_GATE_F32 && gd != DVQ_GATE_I64) { dvq_set_error("%s: gate_dtype %d", fn, gd); return DVQ_EINVAL; }
+    if (int rc = check_features(fn, features_of(gate_dtype))) return rc;
     if (B <= 0 || C <= 0 || hc <= 0 || wc <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
+    if (features_of(gate_dtype) != 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)h_out) & 1) != 0) {
+        dvq_set_error("%s: 16-bit features must be 2-byte aligned", fn); return DVQ_EINVAL;
+    }
     return DVQ_OK;
 }
 
-int dvq_route_select_dual_f32(const void *gate, int gate_dtype, const float *h_coarse,
-                              const float *h_fine, int B, int C, int hc, int wc,
-                              float *h_out, int64_t *indices, float *cmask, void *stream)
+int dvq_route_select_dual_f32(const void *gate, int gate_dtype, const void *h_coarse,
+                              const void *h_fine, int B, int C, int hc, int wc,
+                              void *h_out, int64_t *indices, float *cmask, void *stream)
 {
     int rc = route_args_ok("dvq_route_select_dual_f32", gate, gate_dtype, h_coarse, h_fine, B, C, hc, wc, h_out, indices, cmask);
     if (rc) return rc;
-    return hip_rc(dvq_launch_route_select(2, gate_dtype == DVQ_GATE_I64, gate, h_coarse, nullptr, h_fine, B, C, hc, wc,
-                                          h_out, (long long *)indices, cmask, 0.0f, nullptr, (hipStream_t)stream), "route_select_dual");
+    const int gate_mode = enum_of(gate_dtype) == DVQ_GATE_I64;
+    if (features_of(gate_dtype) != 0)
+        return hip_rc(dvq_launch_route_select_x16(2, gate_mode, gate, h_coarse, nullptr, h_fine, B, C, hc, wc, h_out,
+                                                  (long long *)indices, cmask, (hipStream_t)stream), "route_select_dual");
+    return hip_rc(dvq_launch_route_select(2, gate_mode, gate, (const float *)h_coarse, nullptr, (const float *)h_fine, B, C, hc, wc,
+                                          (float *)h_out, (long long *)indices, cmask, 0.0f, nullptr, (hipStream_t)stream), "route_select_dual");
 }
 
 int dvq_route_select_dual_entropy_f32(const float *entropy, float threshold, const float *h_coarse,
@@ -557,15 +579,22 @@ int dvq_route_select_dual_entropy_f32(const float *entropy, float threshold, con
                                           (hipStream_t)stream), "route_select_dual_entropy");
 }
 
-int dvq_route_select_triple_f32(const void *gate, int gate_dtype, const float *h_coarse,
-                                const float *h_median, const float *h_fine, int B, int C, int hc,
-                                int wc, float *h_out, int64_t *indices, float *cmask, void *stream)
+int dvq_route_select_triple_f32(const void *gate, int gate_dtype, const void *h_coarse,
+                                const void *h_median, const void *h_fine, int B, int C, int hc,
+                                int wc, void *h_out, int64_t *indices, float *cmask, void *stream)
 {
     int rc = route_args_ok("dvq_route_select_triple_f32", gate, gate_dtype, h_coarse, h_fine, B, C, hc, wc, h_out, indices, cmask);
     if (rc) return rc;
     if (!h_median) { dvq_set_error("dvq_route_select_triple_f32: null h_median"); return DVQ_EINVAL; }
-    return hip_rc(dvq_launch_route_select(3, gate_dtype == DVQ_GATE_I64, gate, h_coarse, h_median, h_fine, B, C, hc, wc,
-                                          h_out, (long long *)indices, cmask, 0.0f, nullptr, (hipStream_t)stream), "route_select_triple");
+    const int gate_mode = enum_of(gate_dtype) == DVQ_GATE_I64;
+    if (features_of(gate_dtype) != 0) {
+        if (((uintptr_t)h_median & 1) != 0) { dvq_set_error("dvq_route_select_triple_f32: 16-bit features must be 2-byte aligned"); return DVQ_EINVAL; }
+        return hip_rc(dvq_launch_route_select_x16(3, gate_mode, gate, h_coarse, h_median, h_fine, B, C, hc, wc, h_out,
+                                                  (long long *)indices, cmask, (hipStream_t)stream), "route_select_triple");
+    }
+    return hip_rc(dvq_launch_route_select(3, gate_mode, gate, (const float *)h_coarse, (const float *)h_median, (const float *)h_fine,
+                                          B, C, hc, wc, (float *)h_out, (long long *)indices, cmask, 0.0f, nullptr, (hipStream_t)stream),
+                  "route_select_triple");
 }
 
 static int ema_accumulate_nchw(const char *fn, int dtype, const void *z, const int64_t *codes, int B, int D, int HW, int K,
@@ -684,21 +713,25 @@ int dvq_router_gate_prepare_norm_f32(int nb, int C, int hidden, const float *gn_
     return hip_rc(dvq_launch_router_gate_prepare_norm(w, b, nb, C, hidden, w1_prep, (hipStream_t)stream), fn);
 }
 
-int dvq_router_gate_f32(int nb, const float *h_coarse, const float *h_median, const float *h_fine,
+int dvq_router_gate_f32(int nb, const void *h_coarse, const void *h_median, const void *h_fine,
                         int B, int C, int hc, int wc, int num_groups, float eps,
                         const float *gn_w_coarse, const float *gn_b_coarse,
                         const float *gn_w_median, const float *gn_b_median,
                         const float *gn_w_fine, const float *gn_b_fine,
                         const float *w1, const float *b1, const float *w2, const float *b2,
-                        int hidden, int activation, const void *w1_prep, float *gate, void *ws, size_t ws_bytes,
+                        int hidden, int activation_arg, const void *w1_prep, float *gate, void *ws, size_t ws_bytes,
                         void *stream)
 {
     const char *fn = "dvq_router_gate_f32";
+    const int activation = enum_of(activation_arg), xt = features_of(activation_arg);    // DVQ_FEATURES(dtype): 16-bit branches
     if (nb != 2 && nb != 3) { dvq_set_error("%s: num_branches=%d (2 or 3)", fn, nb); return DVQ_EINVAL; }
     if (!h_coarse || !h_fine || !w2 || !b2 || !gate) return null_pointer(fn);
     if ((nb == 3) != (h_median != nullptr)) { dvq_set_error("%s: h_median must be given exactly when num_branches == 3", fn); return DVQ_EINVAL; }
     if (B <= 0 || C <= 0 || hc <= 0 || wc <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     if (activation != DVQ_ACT_NONE && activation != DVQ_ACT_SILU && activation != DVQ_ACT_RELU) { dvq_set_error("%s: unknown activation %d", fn, activation); return DVQ_EINVAL; }
+    if (int rc = check_features(fn, xt)) return rc;
+    // the pooling pass reads four 2-byte elements with one 8-byte load
+    if (xt != 0 && (((uintptr_t)h_coarse | (uintptr_t)h_median | (uintptr_t)h_fine) & 7) != 0) { dvq_set_error("%s: 16-bit features must be 8-byte aligned", fn); return DVQ_EINVAL; }
     if (activation != DVQ_ACT_NONE && (!w1 || !b1 || hidden <= 0)) { dvq_set_error("%s: hidden layer requested without w1 / b1 / hidden", fn); return DVQ_EINVAL; }
     if (num_groups < 0 || (num_groups > 0 && C % num_groups != 0)) { dvq_set_error("%s: C=%d is not divisible by num_groups=%d", fn, C, num_groups); return DVQ_EINVAL; }
     if (num_groups > 0 && (!gn_w_coarse || !gn_b_coarse || !gn_w_fine || !gn_b_fine || (nb == 3 && (!gn_w_median || !gn_b_median)))) {
@@ -713,7 +746,8 @@ int dvq_router_gate_f32(int nb, const float *h_coarse, const float *h_median, co
         return DVQ_EUNSUPPORTED;
     }
     if (int rc = check_workspace(fn, ws, ws_bytes, dvq_router_gate_ws_bytes(nb, B, C, hc, wc, num_groups, hidden > 0 ? hidden : 32))) return rc;
-    const float *h[3], *gw[3], *gb[3];
+    const void *h[3];
+    const float *gw[3], *gb[3];
     if (nb == 2) {
         h[0] = h_coarse; h[1] = h_fine; h[2] = nullptr;
         gw[0] = gn_w_coarse; gw[1] = gn_w_fine; gw[2] = nullptr;
@@ -723,7 +757,7 @@ int dvq_router_gate_f32(int nb, const float *h_coarse, const float *h_median, co
         gw[0] = gn_w_coarse; gw[1] = gn_w_median; gw[2] = gn_w_fine;
         gb[0] = gn_b_coarse; gb[1] = gn_b_median; gb[2] = gn_b_fine;
     }
-    return hip_rc(dvq_launch_router_gate(nb, h, gw, gb, B, C, hc, wc, num_groups, eps, w1, b1, w2, b2,
+    return hip_rc(dvq_launch_router_gate(nb, h, xt, gw, gb, B, C, hc, wc, num_groups, eps, w1, b1, w2, b2,
                                          hid, activation, w1_prep, gate, ws, (hipStream_t)stream), "router_gate");
 }
 

@@ -38,6 +38,10 @@ int dvq_launch_route_select(int G, int gate_mode, const void *gate, const float 
                             const float *h_median, const float *h_fine, int B, int C, int hc, int wc,
                             float *h_out, long long *indices, float *cmask, float thr, long long *gate_out,
                             hipStream_t st);
+// the select on 2-byte features (fp16 or bf16: nothing is converted); gate_mode 0 / 1 only
+int dvq_launch_route_select_x16(int G, int gate_mode, const void *gate, const void *h_coarse, const void *h_median,
+                                const void *h_fine, int B, int C, int hc, int wc, void *h_out, long long *indices,
+                                float *cmask, hipStream_t st);
 int dvq_launch_entropy_gate(const float *ent, long n, float thr, long long *gate, hipStream_t st);
 // xt (here and below): the type of the latent-shaped tensors, 0 = float32, DVQ_DTYPE_F16 / DVQ_DTYPE_BF16 (dvq_common.h: DvqLat);
 // anything else returns -1000
@@ -101,7 +105,8 @@ int dvq_launch_ema_update(const float *stats_sum, const float *stats_count, floa
                           const float *z, int HW, const long long *pick, hipStream_t st);
 int dvq_launch_router_gate_prepare_norm(const float *const *gn_w, const float *const *gn_b, int nb, int C, int Hid, void *prep,
                                         hipStream_t st);
-int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn_w, const float *const *gn_b,
+// xt: the type of the branch features h (0 = float32, DVQ_DTYPE_F16 / DVQ_DTYPE_BF16: widened where the pooling pass loads them)
+int dvq_launch_router_gate(int nb, const void *const *h, int xt, const float *const *gn_w, const float *const *gn_b,
                            int B, int C, int hc, int wc, int groups, float eps,
                            const float *W1, const float *b1, const float *W2, const float *b2,
                            int Hid, int act, const void *w1_prep, float *gate, void *ws, hipStream_t st);

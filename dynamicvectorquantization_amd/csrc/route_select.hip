@@ -145,6 +145,112 @@ __global__ __launch_bounds__(256) void route_select_kernel(
     }
 }
 
+// ---- the same select on 2-byte elements (fp16 / bf16 branch features; DVQ_FEATURES in dvq.h).  Nothing is converted, so ONE
+// kernel serves both types: elements are unsigned shorts.  V = elements per thread and access, a power of two chosen by the
+// launcher: 8 (16 bytes) where the rows, the planes and the pointers allow, else 4, 2 or 1.  A piece starts at a column that
+// is a multiple of V, and V and SC are powers of two, so a piece of V >= SC elements covers exactly V / SC WHOLE coarse cells
+// (dual at V = 8: four; triple: two) and a shorter one lies inside one cell: the float kernel's cx0 / cx1 pair becomes the
+// compile-time array g[NC], and element j of a piece belongs to cell j / SC of it.  MODE 0 / 1 as above (no entropy form: the
+// fixed-entropy router runs as entropy_gate_kernel + the int64 gate).  indices and cmask are written as by the float kernel.
+template <int V> struct U16Of { typedef unsigned short type __attribute__((ext_vector_type(V))); };
+template <> struct U16Of<1> { struct type { unsigned short s; __device__ unsigned short &operator[](int) { return s; } }; };
+template <int V> __device__ __forceinline__ void store_mask(float *p, const float (&m)[V])
+{
+    if constexpr (V == 1) {
+        p[0] = m[0];
+    } else if constexpr (V == 2) {
+        *(f32x2 *)p = (f32x2){m[0], m[1]};
+    } else {
+#pragma unroll
+        for (int q = 0; q < V; q += 4) *(f32x4 *)(p + q) = (f32x4){m[q], m[q + 1], m[q + 2], m[q + 3]};
+    }
+}
+template <int G, int MODE, int V>
+__global__ __launch_bounds__(256) void route_select_x16_kernel(
+    const void *__restrict__ gate, const unsigned short *__restrict__ h_coarse,
+    const unsigned short *__restrict__ h_median, const unsigned short *__restrict__ h_fine,
+    int B, int C, int hc, int wc,
+    unsigned short *__restrict__ h_out, long long *__restrict__ indices, float *__restrict__ cmask)
+{
+    static_assert(MODE == 0 || MODE == 1, "float32 logits or the int64 gate");
+    constexpr int SC = (G == 2) ? 2 : 4;          // fine pixels per coarse cell edge
+    constexpr int NC = V >= SC ? V / SC : 1;      // coarse cells a piece covers
+    __shared__ unsigned char grain[MAX_CELLS];
+    typedef typename U16Of<V>::type vec_t;
+    const int H = SC * hc, W = SC * wc, WV = W / V;
+    const int per_plane = H * WV;
+    const int ncell = hc * wc;
+    for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int p0 = blockIdx.x * PLANES_PER_BLOCK;
+    const int p1 = (p0 + PLANES_PER_BLOCK < C + 1) ? p0 + PLANES_PER_BLOCK : C + 1;
+    const bool in_lds = ncell <= MAX_CELLS;
+    if (in_lds) {
+        for (int cell = threadIdx.x; cell < ncell; cell += 256)
+            grain[cell] = (unsigned char)gate_argmax<G, MODE>(gate, (size_t)b * ncell + cell, 0.0f);
+        __syncthreads();
+    }
+    auto grain_of = [&](int cell) -> int {
+        return in_lds ? (int)grain[cell] : gate_argmax<G, MODE>(gate, (size_t)b * ncell + cell, 0.0f);
+    };
+    // one loop over the pieces of all of the workgroup's planes: a 32 x 32 plane is only 128 16-byte pieces, half a workgroup
+    {
+        for (int idx = threadIdx.x; idx < (p1 - p0) * per_plane; idx += 256) {
+            const int p = p0 + idx / per_plane, i = idx - (p - p0) * per_plane;
+            const size_t plane = (size_t)b * C + p;
+            const int y = i / WV, x = (i - y * WV) * V;
+            const int cy = y / SC, cx0 = x / SC;
+            const int cell0 = cy * wc + cx0;      // the piece's first (V < SC: only) coarse cell
+            int g[NC];
+            bool all_fine = true, any_fine = false;
+#pragma unroll
+            for (int c = 0; c < NC; ++c) {
+                g[c] = grain_of(cell0 + c);
+                all_fine = all_fine && g[c] == G - 1;
+                any_fine = any_fine || g[c] == G - 1;
+            }
+            if (p == C) {
+                float m[V];
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const int gg = g[V >= SC ? j / SC : 0];
+                    m[j] = (G == 2) ? (gg == 0 ? 0.25f : 1.0f)
+                                    : (gg == 0 ? 0.0625f : (gg == 1 ? 0.25f : 1.0f));
+                }
+                store_mask<V>(cmask + ((size_t)b * H + y) * W + x, m);
+                if (y % SC == 0 && (V >= SC || x % SC == 0)) {
+#pragma unroll
+                    for (int c = 0; c < NC; ++c) indices[(size_t)b * ncell + cell0 + c] = g[c];
+                }
+                continue;
+            }
+            const size_t o = (plane * H + y) * W + x;
+            vec_t v;
+            if (all_fine) {
+                v = *(const vec_t *)(h_fine + o);
+            } else {
+                vec_t f = {};
+                if (any_fine) f = *(const vec_t *)(h_fine + o);
+#pragma unroll
+                for (int j = 0; j < V; ++j) {
+                    const int xx = x + j;
+                    const int gg = g[V >= SC ? j / SC : 0];
+                    unsigned short sv;
+                    if (gg == 0)
+                        sv = h_coarse[(plane * hc + cy) * wc + xx / SC];
+                    else if (G == 3 && gg == 1)
+                        sv = h_median[(plane * (2 * hc) + y / 2) * (2 * wc) + xx / 2];
+                    else
+                        sv = f[j];
+                    v[j] = sv;
+                }
+            }
+            *(vec_t *)(h_out + o) = v;
+        }
+    }
+    if (in_lds) __syncthreads();                  // the next image overwrites the grain map
+    }
+}
+
 __global__ __launch_bounds__(256) void entropy_gate_kernel(const float *__restrict__ ent, long n,
                                                            float thr, long long *__restrict__ gate)
 {
@@ -209,6 +315,31 @@ int dvq_launch_route_select(int G, int gate_mode, const void *gate, const float 
     else DVQ_SEL(3, 0);
 #undef DVQ_SEL
 #undef DVQ_SEL2
+    return (int)hipGetLastError();
+}
+
+// 2-byte features.  The piece width: the widest power of two up to 8 elements that divides the row length (and with it the
+// plane, H rows of it: plane bases are only 2 H W bytes aligned -- a C = 7, 2 x 2 fine map has 8-byte planes) AND fits the actual
+// alignment of h_fine, h_out (2 V bytes) and cmask (V floats, at most 16 bytes per store): a view that starts one element into
+// its storage moves 2-byte pieces.  h_coarse / h_median are read one element at a time (2-byte aligned: dvq_abi.hip).
+int dvq_launch_route_select_x16(int G, int gate_mode, const void *gate, const void *h_coarse, const void *h_median,
+                                const void *h_fine, int B, int C, int hc, int wc, void *h_out, long long *indices,
+                                float *cmask, hipStream_t st)
+{
+    const long W = (long)(G == 2 ? 2 : 4) * wc, H = (long)(G == 2 ? 2 : 4) * hc;
+    const uintptr_t a16 = (uintptr_t)h_fine | (uintptr_t)h_out, am = (uintptr_t)cmask;
+    int V = 8;
+    while (V > 1 && (W % V != 0 || (H * W) % V != 0 || a16 % (2 * V) != 0 || am % (4 * V < 16 ? 4 * V : 16) != 0)) V >>= 1;
+    dim3 grid((C + 1 + PLANES_PER_BLOCK - 1) / PLANES_PER_BLOCK, B < 65535 ? B : 65535), block(256);
+    typedef const unsigned short *cu16;
+#define DVQ_SEL16(GG, MM, VV) hipLaunchKernelGGL((route_select_x16_kernel<GG, MM, VV>), grid, block, 0, st, gate, (cu16)h_coarse, (cu16)h_median, (cu16)h_fine, B, C, hc, wc, (unsigned short *)h_out, indices, cmask)
+#define DVQ_SEL16V(GG, MM) do { if (V == 8) DVQ_SEL16(GG, MM, 8); else if (V == 4) DVQ_SEL16(GG, MM, 4); else if (V == 2) DVQ_SEL16(GG, MM, 2); else DVQ_SEL16(GG, MM, 1); } while (0)
+    if (G == 2 && gate_mode == 1) DVQ_SEL16V(2, 1);
+    else if (G == 2) DVQ_SEL16V(2, 0);
+    else if (gate_mode == 1) DVQ_SEL16V(3, 1);
+    else DVQ_SEL16V(3, 0);
+#undef DVQ_SEL16V
+#undef DVQ_SEL16
     return (int)hipGetLastError();
 }
 

@@ -30,7 +30,7 @@
 #include <type_traits>
 
 struct DvqGateArgs {
-    const float *h[3];        // branches, coarse -> fine
+    const void *h[3];         // branches, coarse -> fine: float32, or fp16 / bf16 (gate_pool_kernel's XT)
     const float *gn_w[3];     // GroupNorm affine per branch (nullptr with groups == 0)
     const float *gn_b[3];
     int scale[3];             // fine pixels per coarse cell edge of the branch (1, 2[, 4])
@@ -54,12 +54,43 @@ struct DvqGateArgs {
 // workgroup rebuilds a tile.  fp16 range: every workgroup derives the SAME power-of-two scale from the GroupNorm parameters
 // alone -- |normalised value| <= |w| sqrt(n) + |b| for every element of a group of n values, and an average of such values
 // obeys the same bound -- so no workgroup needs another's data; xs[0] = that scale's inverse for the matrix kernel.
+// XT (DVQ_DTYPE_F16 / DVQ_DTYPE_BF16; 0 = float32): the branches hold 2-byte elements, widened to fp32 where they are loaded
+// (dvq_widen_bits: exact, the bits of torch's .float()) -- a thread's 4 consecutive columns are then one 8-byte load, a pair one
+// 4-byte load.  Everything behind the load is the float32 kernel's expression, so the logits are those of the float32 op on the
+// widened features, bit for bit.
 #define GATE_LD(p) (NT ? __builtin_nontemporal_load(p) : *(p))    // NT: see DVQ_CACHED_MAX_BYTES (dvq_common.h)
+typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
+typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
+template <int XT> struct GateElem { typedef unsigned short T; };
+template <> struct GateElem<0> { typedef float T; };
+template <int XT, bool NT> __device__ __forceinline__ f32x4 gate_ld4(const typename GateElem<XT>::T *p)
+{
+    if constexpr (XT == 0) {
+        return GATE_LD((const f32x4 *)p);
+    } else {
+        const u16x4 r = GATE_LD((const u16x4 *)p);
+        return (f32x4){dvq_widen_bits<XT>(r[0]), dvq_widen_bits<XT>(r[1]), dvq_widen_bits<XT>(r[2]), dvq_widen_bits<XT>(r[3])};
+    }
+}
+template <int XT, bool NT> __device__ __forceinline__ f32x2 gate_ld2(const typename GateElem<XT>::T *p)
+{
+    if constexpr (XT == 0) {
+        return GATE_LD((const f32x2 *)p);
+    } else {
+        const u16x2 r = GATE_LD((const u16x2 *)p);
+        return (f32x2){dvq_widen_bits<XT>(r[0]), dvq_widen_bits<XT>(r[1])};
+    }
+}
+template <int XT, bool NT> __device__ __forceinline__ float gate_ld1(const typename GateElem<XT>::T *p)
+{
+    if constexpr (XT == 0) return GATE_LD(p);
+    else return dvq_widen_bits<XT>(GATE_LD(p));
+}
 #ifndef DVQ_POOL_WPE
 #define DVQ_POOL_WPE 8           // workgroups per CU the pooling pass is compiled for (a streaming pass lives on occupancy)
 #endif
 #define DVQ_GATE_NORM_MAGIC 0x44563531      // tail of the weight prep: [magic][max |gn_w|, max |gn_b| per branch] (dvq_router_gate_prepare_norm_f32)
-template <bool IMG, bool NT>
+template <bool IMG, bool NT, int XT = 0>
 __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArgs a, float2 *__restrict__ ab,
                                                         float *__restrict__ pool, char *__restrict__ ximg,
                                                         float *__restrict__ xs, const float *__restrict__ nbound)
@@ -112,7 +143,8 @@ __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArg
         const int sc = a.scale[br];
         const int Wb = a.wc * sc;
         const size_t plane = (size_t)(a.hc * sc) * Wb;
-        const float *p0 = a.h[br] + ((size_t)b * a.C + (size_t)g * cpg) * plane;
+        typedef typename GateElem<XT>::T elem_t;
+        const elem_t *p0 = (const elem_t *)a.h[br] + ((size_t)b * a.C + (size_t)g * cpg) * plane;
         float *o0 = IMG ? lp + (size_t)br * npair : pool + ((size_t)b * F + (size_t)br * a.C + (size_t)g * cpg) * ncell;
         double s = 0.0, ss = 0.0;
         if (a.vec && (Wb & 3) == 0) {
@@ -125,19 +157,19 @@ __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArg
             for (int u = tid; u < nunit; u += 256) {
                 const int ch = u / upc, r = u - ch * upc;
                 const int y = r / upr, xu = r - y * upr;
-                const float *p = p0 + (size_t)ch * plane + (size_t)sc * y * Wb + 4 * xu;
+                const elem_t *p = p0 + (size_t)ch * plane + (size_t)sc * y * Wb + 4 * xu;
                 float *o = o0 + (size_t)ch * ncell + y * a.wc + xu * cu;
                 auto acc4 = [&](const f32x4 &r) {
 #pragma unroll
                     for (int j = 0; j < 4; ++j) { s += r[j]; ss += (double)r[j] * r[j]; }
                 };
                 if (sc == 1) {
-                    const f32x4 r0 = GATE_LD((const f32x4 *)p);
+                    const f32x4 r0 = gate_ld4<XT, NT>(p);
                     acc4(r0);
                     *(f32x4 *)o = r0;
                 } else if (sc == 2) {
-                    const f32x4 r0 = GATE_LD((const f32x4 *)p);
-                    const f32x4 r1 = GATE_LD((const f32x4 *)(p + Wb));
+                    const f32x4 r0 = gate_ld4<XT, NT>(p);
+                    const f32x4 r1 = gate_ld4<XT, NT>(p + Wb);
                     acc4(r0); acc4(r1);
                     f32x2 v;
                     v[0] = ((r0[0] + r0[1]) + (r1[0] + r1[1])) * 0.25f;
@@ -146,7 +178,7 @@ __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArg
                 } else {
                     f32x4 rw[4];
 #pragma unroll
-                    for (int i = 0; i < 4; ++i) rw[i] = GATE_LD((const f32x4 *)(p + (size_t)i * Wb));
+                    for (int i = 0; i < 4; ++i) rw[i] = gate_ld4<XT, NT>(p + (size_t)i * Wb);
                     float s4 = 0.0f;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
@@ -160,22 +192,22 @@ __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArg
         for (int pr = tid; pr < npair; pr += 256) {
             const int ch = pr / ncell, cell = pr - ch * ncell;
             const int y = cell / a.wc, x = cell - y * a.wc;
-            const float *p = p0 + (size_t)ch * plane + (size_t)sc * y * Wb + sc * x;
+            const elem_t *p = p0 + (size_t)ch * plane + (size_t)sc * y * Wb + sc * x;
             float v;
             if (sc == 1) {
-                const float r = GATE_LD(p);
+                const float r = gate_ld1<XT, NT>(p);
                 s += r; ss += (double)r * r;
                 v = r;
             } else if (sc == 2) {
-                const f32x2 r0 = GATE_LD((const f32x2 *)p);
-                const f32x2 r1 = GATE_LD((const f32x2 *)(p + Wb));
+                const f32x2 r0 = gate_ld2<XT, NT>(p);
+                const f32x2 r1 = gate_ld2<XT, NT>(p + Wb);
 #pragma unroll
                 for (int j = 0; j < 2; ++j) { s += r0[j]; ss += (double)r0[j] * r0[j]; s += r1[j]; ss += (double)r1[j] * r1[j]; }
                 v = ((r0[0] + r0[1]) + (r1[0] + r1[1])) * 0.25f;
             } else {
                 f32x4 r[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) r[i] = GATE_LD((const f32x4 *)(p + (size_t)i * Wb));
+                for (int i = 0; i < 4; ++i) r[i] = gate_ld4<XT, NT>(p + (size_t)i * Wb);
                 float s4 = 0.0f;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -984,7 +1016,7 @@ int dvq_launch_router_gate_prepare(const float *W1, int nb, int C, int Hid, void
     return (int)hipGetLastError();
 }
 
-int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn_w, const float *const *gn_b,
+int dvq_launch_router_gate(int nb, const void *const *h, int xt, const float *const *gn_w, const float *const *gn_b,
                            int B, int C, int hc, int wc, int groups, float eps,
                            const float *W1, const float *b1, const float *W2, const float *b2,
                            int Hid, int act, const void *w1_prep, float *gate, void *ws, hipStream_t st)
@@ -1005,10 +1037,21 @@ int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn
     }
 #endif
     const int F = nb * C, Fp = (F + 15) & ~15;
-    // features that fit the memory-side cache are read with plain loads (pass 1 reads them again right after)
+    // features that fit the memory-side cache are read with plain loads (pass 1 reads them again right after).  16-bit features
+    // keep the rule as it is -- it counts elements x 4, so a shape takes the same form whatever its type; the threshold was
+    // measured for float32 only
     const int fs = 1 << (nb - 1);
     const bool cached = (size_t)B * C * hc * fs * wc * fs * sizeof(float) <= DVQ_CACHED_MAX_BYTES;
     float2 *stats = (float2 *)ws;                            // (scale, shift) per (image, feature)
+    if (xt != 0 && xt != 1 && xt != 2) return -1000;
+    // the pooling pass on fp16 (xt = 1 = DVQ_DTYPE_F16) / bf16 (2 = DVQ_DTYPE_BF16) features: GRID workgroups, LDS bytes of dynamic LDS
+#define DVQ_POOL_X16(IMG_, NT_, GRID, LDS, XIMG, XS, NBOUND)                                                            \
+    do {                                                                                                                \
+        if (xt == 1)                                                                                                    \
+            hipLaunchKernelGGL((gate_pool_kernel<IMG_, NT_, 1>), GRID, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND);  \
+        else                                                                                                            \
+            hipLaunchKernelGGL((gate_pool_kernel<IMG_, NT_, 2>), GRID, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND);  \
+    } while (0)
     float *pool = (float *)((char *)ws + align256r((size_t)B * F * sizeof(float2)));
     // ws: [folded GroupNorm affine][pooled averages (direct form) OR feature images (GEMM form)][W1 images, when the caller
     //      passes none][partial logits of the GEMM form][its scale word]
@@ -1038,6 +1081,11 @@ int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn
         const int nblocks = (int)((ncell + 31) / 32);
         if ((ncell & 31) != 0)                               // the last block's unused cell columns must hold finite values
             (void)hipMemsetAsync(ximg + (size_t)(nblocks - 1) * S16 * 2048, 0, (size_t)S16 * 2048, st);
+        const size_t pool_lds = (size_t)nb * cpg * hc * wc * sizeof(float);
+        if (xt != 0) {                                       // 16-bit features: the same two forms, loads widened
+            if (cached) DVQ_POOL_X16(true, false, dim3(B * groups), pool_lds, ximg, xs, nbound);
+            else DVQ_POOL_X16(true, true, dim3(B * groups), pool_lds, ximg, xs, nbound);
+        } else
         if (cached)
             hipLaunchKernelGGL((gate_pool_kernel<true, false>), dim3(B * groups), dim3(256), (size_t)nb * cpg * hc * wc * sizeof(float), st, a,
                                stats, pool, ximg, xs, nbound);
@@ -1084,6 +1132,10 @@ int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn
         hipLaunchKernelGGL(gate_finalize_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, part, HG * 4, nout, nb, b2, gate);
         return (int)hipGetLastError();
     }
+    if (xt != 0) {
+        if (cached) DVQ_POOL_X16(false, false, dim3(B * (groups > 0 ? groups : C / 8)), 0, nullptr, nullptr, nullptr);
+        else DVQ_POOL_X16(false, true, dim3(B * (groups > 0 ? groups : C / 8)), 0, nullptr, nullptr, nullptr);
+    } else
     if (cached)
         hipLaunchKernelGGL((gate_pool_kernel<false, false>), dim3(B * (groups > 0 ? groups : C / 8)), dim3(256), 0, st, a, stats, pool,
                            nullptr, nullptr, nullptr);
@@ -1110,5 +1162,6 @@ int dvq_launch_router_gate(int nb, const float *const *h, const float *const *gn
     const int rc = nb == 2 ? (cb2 ? DVQ_GATE_LAUNCH(2, 2) : DVQ_GATE_LAUNCH(2, 1))
                            : (cb2 ? DVQ_GATE_LAUNCH(3, 2) : DVQ_GATE_LAUNCH(3, 1));
 #undef DVQ_GATE_LAUNCH
+#undef DVQ_POOL_X16
     return rc;
 }

@@ -93,7 +93,12 @@ def encode_dual(router, quantize, h_fine, h_coarse, entropy=None, quant_conv=Non
       * no quant_conv: gate + routing tail + quantizer as ONE routed op (the select fused into the assign);
       * a 1x1 quant_conv on 256 channels: the same ONE op with the conv as its prologue (h_dual and the conv's output are
         never written); other channel counts: select + conv as one kernel, then the dense assign;
-    otherwise route select -> quant_conv -> dense assign as differentiable pieces."""
+    otherwise route select -> quant_conv -> dense assign as differentiable pieces.
+    float16 / bfloat16 branch features (an encoder under autocast; both branches one dtype, no autograd through the select) take
+    that last chain: every fused form above answers False for them, so the router gate and the select run on the 16-bit
+    features (DVQ_FEATURES of include/dvq.h), quant_conv runs as the torch module in the features' dtype, and the quantizer is
+    the dense 16-bit assign -- grain indices and gate as the float32 ops give them on the widened features, quant in the
+    features' dtype, emb_loss float32."""
     _refuse_narrow_fold(fold, h_coarse)
     fixed = isinstance(router, DualGrainFixedEntropyRouter) and entropy is not None and entropy.is_cuda
     if fold and _can_fold(quantize, quant_conv, h_coarse, h_fine):
@@ -149,7 +154,8 @@ def encode_dual(router, quantize, h_fine, h_coarse, entropy=None, quant_conv=Non
 
 def encode_triple(router, quantize, h_fine, h_median, h_coarse, quant_conv=None, temp=0.0, fold=False):
     """-> (quant, emb_loss, info, grain_indices, gate) as TripleGrainVQModel.encode (dqvae_triple_feat.py:68-77).
-    fold=True: see encode_dual (emb_loss = None)."""
+    fold=True: see encode_dual (emb_loss = None).  float16 / bfloat16 branch features (all three one dtype): the 16-bit gate and
+    select, quant_conv in torch, the dense 16-bit assign -- see encode_dual."""
     _refuse_narrow_fold(fold, h_coarse)
     gate = router(h_fine=h_fine, h_median=h_median, h_coarse=h_coarse, entropy=None)
     if fold and _can_fold(quantize, quant_conv, h_coarse, h_median, h_fine):

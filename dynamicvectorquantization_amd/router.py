@@ -50,21 +50,39 @@ def _gate_arg(gate, G):
     return gate.contiguous(), _lib.GATE_F32
 
 
+def _branch_features(named):
+    """the branch features of a routing op, coarse -> fine, as (name, tensor) pairs: float32, or ALL float16 / ALL bfloat16 as an
+    encoder under autocast produces them (DVQ_FEATURES of include/dvq.h: the select moves the 16-bit values as they are, the
+    gate widens them where it loads them) -> the contiguous tensors and the flag for the ABI's enumerated argument"""
+    hs = [_lib.require_cuda_latents(t, n) for n, t in named]
+    if len({h.dtype for h in hs}) != 1:
+        raise TypeError("the branch features must have one dtype, got %s"
+                        % ", ".join("%s %s" % (n, h.dtype) for (n, _), h in zip(named, hs)))
+    return hs, _lib.FEATURES(hs[0].dtype)
+
+
+def _check_out_dtype(h_out, h_fine):
+    if h_out.dtype != h_fine.dtype:
+        raise TypeError("out= holds %s, the features are %s: the select moves values, it converts nothing" % (h_out.dtype, h_fine.dtype))
+
+
 def _route_select_dual_raw(gate, h_coarse, h_fine, out=None):
     """gate [B, hc, wc, 2] (router output, f32 logits or int64), h_coarse [B, C, hc, wc],
     h_fine [B, C, 2hc, 2wc] -> dict(h_dual, indices, codebook_mask, gate) exactly as
     DualGrainEncoder.forward returns it in eval mode (EncoderDual.py:151-156):
     indices [B, hc, wc] int64 (0 coarse / 1 fine), codebook_mask [B, 1, 2hc, 2wc] f32 (0.25 / 1.0),
-    gate permuted to [B, 2, hc, wc]."""
+    gate permuted to [B, 2, hc, wc].
+    Features: float32, or both float16 / both bfloat16 -- h_dual then has that dtype and holds exactly the selected 16-bit
+    values; indices, codebook_mask and gate are what the float32 op gives on the widened features."""
     g, gdt = _gate_arg(gate, 2)
-    h_coarse = _lib.require_cuda_f32(h_coarse, "h_coarse")
-    h_fine = _lib.require_cuda_f32(h_fine, "h_fine")
+    (h_coarse, h_fine), flag = _branch_features([("h_coarse", h_coarse), ("h_fine", h_fine)])
     B, C, hc, wc = h_coarse.shape
     if tuple(h_fine.shape) != (B, C, 2 * hc, 2 * wc) or tuple(g.shape[:3]) != (B, hc, wc):
         raise ValueError("shape mismatch: gate %s h_coarse %s h_fine %s" %
                          (tuple(gate.shape), tuple(h_coarse.shape), tuple(h_fine.shape)))
     if out is not None:
         h_dual, indices, cmask = out
+        _check_out_dtype(h_dual, h_fine)
     else:
         h_dual = torch.empty_like(h_fine)
         indices = torch.empty((B, hc, wc), dtype=torch.int64, device=h_fine.device)
@@ -73,7 +91,7 @@ def _route_select_dual_raw(gate, h_coarse, h_fine, out=None):
         return {"h_dual": h_dual, "indices": indices, "codebook_mask": cmask, "gate": gate.permute(0, 3, 1, 2)}
     with _lib.on_device(h_fine.device):
         checked.dvq_route_select_dual_f32(
-            g.data_ptr(), gdt, h_coarse.data_ptr(), h_fine.data_ptr(), B, C, hc, wc,
+            g.data_ptr(), gdt | flag, h_coarse.data_ptr(), h_fine.data_ptr(), B, C, hc, wc,
             h_dual.data_ptr(), indices.data_ptr(), cmask.data_ptr(), _lib.stream_ptr(h_fine.device))
     return {"h_dual": h_dual, "indices": indices, "codebook_mask": cmask, "gate": gate.permute(0, 3, 1, 2)}
 
@@ -82,16 +100,28 @@ def _route_select_dual_entropy_raw(entropy, threshold, h_coarse, h_fine, out=Non
     """DualGrainFixedEntropyRouter.forward + the routing tail of DualGrainEncoder.forward in ONE kernel
     (RouterDual.py:53-57 + EncoderDual.py:134-156): entropy [B, hc, wc] f32 -> the same dict as
     route_select_dual, "gate" being the router's int64 gate permuted to [B, 2, hc, wc].
-    out = (h_dual, indices, codebook_mask, gate[B, hc, wc, 2] int64) to reuse buffers."""
+    out = (h_dual, indices, codebook_mask, gate[B, hc, wc, 2] int64) to reuse buffers.
+    float16 / bfloat16 features (entropy stays float32): TWO launches, `dvq_entropy_gate_f32` and the int64-gate select on
+    16-bit features -- the fused entry point has no argument that could carry a dtype; same outputs."""
     entropy = _lib.require_cuda_f32(entropy, "entropy")
-    h_coarse = _lib.require_cuda_f32(h_coarse, "h_coarse")
-    h_fine = _lib.require_cuda_f32(h_fine, "h_fine")
+    (h_coarse, h_fine), flag = _branch_features([("h_coarse", h_coarse), ("h_fine", h_fine)])
     B, C, hc, wc = h_coarse.shape
     if tuple(h_fine.shape) != (B, C, 2 * hc, 2 * wc) or tuple(entropy.shape) != (B, hc, wc):
         raise ValueError("shape mismatch: entropy %s h_coarse %s h_fine %s" %
                          (tuple(entropy.shape), tuple(h_coarse.shape), tuple(h_fine.shape)))
+    if flag:
+        if out is not None:
+            gate = out[3]
+            if gate.numel() > 0:
+                with _lib.on_device(entropy.device):
+                    checked.dvq_entropy_gate_f32(entropy.data_ptr(), entropy.numel(), float(threshold), gate.data_ptr(),
+                                                 _lib.stream_ptr(entropy.device))
+        else:
+            gate = entropy_gate(entropy, threshold)
+        return _route_select_dual_raw(gate, h_coarse, h_fine, None if out is None else out[:3])
     if out is not None:
         h_dual, indices, cmask, gate = out
+        _check_out_dtype(h_dual, h_fine)
     else:
         h_dual = torch.empty_like(h_fine)
         indices = torch.empty((B, hc, wc), dtype=torch.int64, device=h_fine.device)
@@ -109,11 +139,9 @@ def _route_select_dual_entropy_raw(entropy, threshold, h_coarse, h_fine, out=Non
 def _route_select_triple_raw(gate, h_coarse, h_median, h_fine, out=None):
     """gate [B, hc, wc, 3]; h_coarse [B,C,hc,wc], h_median [B,C,2hc,2wc], h_fine [B,C,4hc,4wc]
     -> dict(h_triple, indices, codebook_mask, gate) as TripleGrainEncoder.forward (EncoderTriple.py:178-183);
-    mask values 0.0625 / 0.25 / 1.0."""
+    mask values 0.0625 / 0.25 / 1.0.  Features: float32, or all three float16 / bfloat16 (see _route_select_dual_raw)."""
     g, gdt = _gate_arg(gate, 3)
-    h_coarse = _lib.require_cuda_f32(h_coarse, "h_coarse")
-    h_median = _lib.require_cuda_f32(h_median, "h_median")
-    h_fine = _lib.require_cuda_f32(h_fine, "h_fine")
+    (h_coarse, h_median, h_fine), flag = _branch_features([("h_coarse", h_coarse), ("h_median", h_median), ("h_fine", h_fine)])
     B, C, hc, wc = h_coarse.shape
     if (tuple(h_median.shape) != (B, C, 2 * hc, 2 * wc) or tuple(h_fine.shape) != (B, C, 4 * hc, 4 * wc)
             or tuple(g.shape[:3]) != (B, hc, wc)):
@@ -121,6 +149,7 @@ def _route_select_triple_raw(gate, h_coarse, h_median, h_fine, out=None):
                          (tuple(gate.shape), tuple(h_coarse.shape), tuple(h_median.shape), tuple(h_fine.shape)))
     if out is not None:
         h_triple, indices, cmask = out
+        _check_out_dtype(h_triple, h_fine)
     else:
         h_triple = torch.empty_like(h_fine)
         indices = torch.empty((B, hc, wc), dtype=torch.int64, device=h_fine.device)
@@ -129,7 +158,7 @@ def _route_select_triple_raw(gate, h_coarse, h_median, h_fine, out=None):
         return {"h_triple": h_triple, "indices": indices, "codebook_mask": cmask, "gate": gate.permute(0, 3, 1, 2)}
     with _lib.on_device(h_fine.device):
         checked.dvq_route_select_triple_f32(
-            g.data_ptr(), gdt, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), B, C, hc, wc,
+            g.data_ptr(), gdt | flag, h_coarse.data_ptr(), h_median.data_ptr(), h_fine.data_ptr(), B, C, hc, wc,
             h_triple.data_ptr(), indices.data_ptr(), cmask.data_ptr(), _lib.stream_ptr(h_fine.device))
     return {"h_triple": h_triple, "indices": indices, "codebook_mask": cmask, "gate": gate.permute(0, 3, 1, 2)}
 
@@ -170,6 +199,11 @@ class _RouteSelectGrad(torch.autograd.Function):
 def _select(run, key, h_coarse, h_median, h_fine):
     feats = [t for t in (h_coarse, h_median, h_fine) if t is not None]
     if torch.is_grad_enabled() and any(t.requires_grad for t in feats):
+        for t in feats:
+            if isinstance(t, torch.Tensor) and t.dtype in _lib.X16:
+                raise TypeError("route_select: features that require grad must be float32, got %s (float16 / bfloat16 features "
+                                "are selected without autograd only: detach them, or cast to float32 to train through the select)"
+                                % t.dtype)
         h_out, indices, cmask = _RouteSelectGrad.apply(run, h_coarse, h_median, h_fine)
         sel = run.last
         return {key: h_out, "indices": indices, "codebook_mask": cmask, "gate": sel["gate"]}
@@ -273,9 +307,13 @@ def fused_router_gate(gate, gate_type, norms, branches, weight_prep=None):
     GroupNorm (or Identity) modules and of the [B, C, rows, cols] feature maps.
     -> logits [B, hc, wc, len(branches)] f32 (RouterDual.py:35-43, RouterTriple.py:46-56): one pass over the features
     (statistics + per-cell averages), then the gate MLP on the averages.  weight_prep: a _GateWeightPrep kept by the
-    module (None: the weight images are rebuilt inside the call)."""
+    module (None: the weight images are rebuilt inside the call).
+    branches: float32, or all float16 / all bfloat16 -- widened where the pooling pass loads them, everything behind the load is
+    the float32 op: the logits (float32 either way) are those of this function on `h.float()`, bit for bit."""
     nb = len(branches)
-    hs = [_lib.require_cuda_f32(h, "router input") for h in branches]
+    hs, flag = _branch_features([("router input %d" % i, h) for i, h in enumerate(branches)])
+    # the pooling pass reads four 16-bit elements with one 8-byte load (a view that starts inside its storage is copied)
+    hs = [h.clone() if flag and h.data_ptr() % 8 != 0 else h for h in hs]
     B, C, hc, wc = hs[0].shape
     for i, h in enumerate(hs):
         if tuple(h.shape) != (B, C, hc << i, wc << i):
@@ -313,7 +351,7 @@ def fused_router_gate(gate, gate_type, norms, branches, weight_prep=None):
         checked.dvq_router_gate_f32(
             nb, hs[0].data_ptr(), ptr(med), hs[-1].data_ptr(), B, C, hc, wc, groups, float(eps),
             ptr(gw[0]), ptr(gb[0]), ptr(gw[1]) if nb == 3 else None, ptr(gb[1]) if nb == 3 else None,
-            ptr(gw[-1]), ptr(gb[-1]), ptr(w1), ptr(b1), ptr(w2), ptr(b2), hidden, act, ptr(prep),
+            ptr(gw[-1]), ptr(gb[-1]), ptr(w1), ptr(b1), ptr(w2), ptr(b2), hidden, act | flag, ptr(prep),
             out.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
     return out
 

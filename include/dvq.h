@@ -30,6 +30,10 @@
  *     dvq_vq_assign_narrow_*_f32 below; every other entry point refuses them as before.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.19.0 DVQ_FEATURES(dtype): dvq_route_select_dual_f32, dvq_route_select_triple_f32 and dvq_router_gate_f32 take fp16 / bf16 branch
+ *          features when DVQ_FEATURES(DVQ_DTYPE_F16 / DVQ_DTYPE_BF16) is OR-ed into their enumerated argument (gate_dtype, activation);
+ *          the h_* / h_out parameters of the three are declared `const void *` / `void *` for that (binary- and source-compatible
+ *          for C callers).  Without the flag nothing changed; no new entry point.
  *   0.18.0 Row-major latents [N, D] -- token rows, or a channels_last (NHWC) image map, which is the same bytes -- on the training side:
  *          dvq_vq_backward_nchw_f32 / _x16, dvq_vq_backward_codebook_nchw_f32 and dvq_ema_accumulate_nchw_f32 / _x16 called with B = N,
  *          HW = 1 run kernels whose accesses follow the rows (the backward: where z, g_zq and g_z are 16-byte aligned; same bits as
@@ -128,6 +132,16 @@ extern "C" {
 #define DVQ_GATE_ENTROPY 2  /* routed assign only: float32 entropy map [B, hc, wc] + threshold  */
                             /* (the fixed-entropy router fused in)                              */
 
+/* Flag, OR-ed into the one enumerated argument of dvq_route_select_dual_f32 / dvq_route_select_triple_f32 (`gate_dtype`) and of
+ * dvq_router_gate_f32 (`activation`), the way DVQ_MODE_WS_CLEAN rides on `mode`: the BRANCH FEATURES (h_coarse, h_median, h_fine,
+ * and h_out of the selects) are fp16 or bf16 -- DVQ_FEATURES(DVQ_DTYPE_F16) / DVQ_FEATURES(DVQ_DTYPE_BF16), defined with the *_x16
+ * entry points below -- as an encoder under autocast produces them.  The contract is that of the *_x16 assign, carried through the
+ * routing tail: every integer output (indices, the argmax behind them) is what the float32 op gives on the widened features; the
+ * gate logits and cmask stay float32; h_out holds exactly the selected 16-bit values (a select moves bytes and rounds nothing).
+ * The enumerator is the low byte and is checked where and with the words it always was; dtype bits other than 0 (float32), 1, 2
+ * are DVQ_EINVAL.  Every other entry point refuses the flag by its own enumerator check. */
+#define DVQ_FEATURES(dtype) ((dtype) << 8)
+
 DVQ_API int dvq_version(void);
 DVQ_API const char *dvq_last_error_string(void);
 
@@ -199,11 +213,14 @@ DVQ_API int dvq_entropy_gate_f32(const float *entropy, int64_t n, float thr, int
  *   gate [B, hc, wc, 2] (DVQ_GATE_F32 logits or DVQ_GATE_I64)
  *   h_coarse [B, C, hc, wc], h_fine [B, C, 2hc, 2wc]
  *   h_out [B, C, 2hc, 2wc], indices [B, hc, wc] int64, cmask [B, 1, 2hc, 2wc] (0.25 / 1.0)
+ * h_coarse, h_fine and h_out hold float32; with gate_dtype | DVQ_FEATURES(DVQ_DTYPE_F16 / DVQ_DTYPE_BF16) they hold 2-byte elements
+ * of that type (2-byte aligned, DVQ_EINVAL otherwise; h_out = the selected elements, bit for bit; any hc, wc, C).  This and the
+ * triple select move the widest pieces the row length and the alignment of h_fine / h_out / cmask allow, 16 bytes at the best.
  */
 DVQ_API int dvq_route_select_dual_f32(const void *gate, int gate_dtype,
-                              const float *h_coarse, const float *h_fine,
+                              const void *h_coarse, const void *h_fine,
                               int B, int C, int hc, int wc,
-                              float *h_out, int64_t *indices, float *cmask, void *stream);
+                              void *h_out, int64_t *indices, float *cmask, void *stream);
 
 /* The fixed-entropy router (RouterDual.py:46-57) fused into the dual select: entropy [B, hc, wc] f32,
  * gate = [(entropy <= threshold), (entropy > threshold)]; outputs as dvq_route_select_dual_f32 plus,
@@ -217,11 +234,12 @@ DVQ_API int dvq_route_select_dual_entropy_f32(const float *entropy, float thresh
  * Routing tail of TripleGrainEncoder.forward in eval mode (EncoderTriple.py:148-176).
  *   gate [B, hc, wc, 3]; h_coarse [B,C,hc,wc], h_median [B,C,2hc,2wc], h_fine [B,C,4hc,4wc]
  *   cmask values 0.0625 / 0.25 / 1.0
+ * h_* and h_out: float32, or 2-byte elements with gate_dtype | DVQ_FEATURES(dtype), as for dvq_route_select_dual_f32.
  */
 DVQ_API int dvq_route_select_triple_f32(const void *gate, int gate_dtype,
-                                const float *h_coarse, const float *h_median,
-                                const float *h_fine, int B, int C, int hc, int wc,
-                                float *h_out, int64_t *indices, float *cmask, void *stream);
+                                const void *h_coarse, const void *h_median,
+                                const void *h_fine, int B, int C, int hc, int wc,
+                                void *h_out, int64_t *indices, float *cmask, void *stream);
 
 /*
  * Routed assignment: routing tail + VectorQuantize2.forward as ONE op straight from the encoder
@@ -509,7 +527,10 @@ DVQ_API int dvq_router_gate_prepare_norm_f32(int num_branches, int C, int hidden
                                      const float *gn_w_median, const float *gn_b_median,
                                      const float *gn_w_fine, const float *gn_b_fine,
                                      void *w1_prep, size_t w1_prep_bytes, void *stream);
-DVQ_API int dvq_router_gate_f32(int num_branches, const float *h_coarse, const float *h_median, const float *h_fine,
+/* h_*: float32; with activation | DVQ_FEATURES(DVQ_DTYPE_F16 / DVQ_DTYPE_BF16) 2-byte elements of that type (8-byte aligned, DVQ_EINVAL
+ * otherwise), widened to float32 where the pooling pass loads them: the logits are those of this op on the widened features, bit for
+ * bit.  Workspace, prep and every other argument are the same (dvq_router_gate_workspace_bytes takes no dtype). */
+DVQ_API int dvq_router_gate_f32(int num_branches, const void *h_coarse, const void *h_median, const void *h_fine,
                         int B, int C, int hc, int wc, int num_groups, float eps,
                         const float *gn_w_coarse, const float *gn_b_coarse,
                         const float *gn_w_median, const float *gn_b_median,
