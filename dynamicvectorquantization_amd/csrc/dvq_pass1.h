@@ -3,7 +3,7 @@
 // by one translation unit per (D, resident seed table) -- vq_pass1_d<D>[_res].hip, each a call of launch_pass1_res<D, RES> --
 // so no kernel handle crosses an object boundary; the wide form (vq_pass1_wide.hip) and the resolver (vq_resolve.hip) are
 // units of their own and take the host-side types from here.
-// The code loop's text is pass1_loop.h, included by pass1_body once per form (long / the short form of SEL == 2).
+// The code loop's text is pass1_loop.h, included by pass1_body once per form (two, one or no column group; the latter two: SEL == 2).
 #pragma once
 #include "dvq_filter.h"
 #include <type_traits>
@@ -203,7 +203,23 @@ __device__ __forceinline__ void pass1_body(
     const int tile_id = SPLIT ? (int)(blockIdx.x / (unsigned)ksplit) : xcd_swizzle(blockIdx.x, gridDim.x);
     // SEL == 2 parks the coarser branches in the ring slots from `pre` on: 2 slots = D x 128 B for the 2x-coarser
     // branch (dual: slots 2, 3; triple: slots 1, 2), slot 3 for the triple's 4x-coarser branch (D x 32 B)
+    // WGC (SEL == 2 at D = 256): the workgroup's real columns are packed over its four waves (below), and the B operands cross
+    // waves through two 8-KiB exchange buffers: the four permutation scratches, and the first 8 KiB of the 2x-coarser branch's
+    // image -- its channels 0 .. 63, which every wave has consumed once it has written the second k-step pair.  (Taking a ring slot
+    // for the second buffer instead -- one code tile in flight through the dual's prologue, not two -- exposed that tile's DMA
+    // latency in front of the loop: the kernel alone ran 2.7 us LONGER than the per-wave rule's, section 8.)
+    constexpr bool WGC = (SEL == 2 && D == 256);
     const int pre = (SEL == 2) ? ((rv.G == 2) ? 2 : 1) : 3;  // code tiles in flight before the prologue
+    char *const xbuf_a = lds + NBUF * IMG_BYTES + NBUF * NW * 64 * 4;
+    char *xbuf_b = nullptr;
+    if constexpr (WGC) xbuf_b = lds + pre * IMG_BYTES;       // (SEL == 2: the image sits in the slots from `pre` on)
+    static_assert(!WGC || (64 * 128 == 8192 && S32 >= 4), "channels 0 .. 63 of the [D][32 floats] image are the second buffer");
+    unsigned wgm0 = 0u, wgm1 = 0u, wgm2 = 0u, wgm3 = 0u;     // WGC: the four waves' copy masks (scalar registers through the loop)
+    unsigned *wg_masks = nullptr;                            // ... and where they are exchanged: 16 bytes of static LDS
+    if constexpr (WGC) {
+        __shared__ unsigned s_wg_masks[4];
+        wg_masks = s_wg_masks;
+    }
 
     const int n_raw = (tile_id * NW + wave) * 32 + c;
     const int n = (n_raw < N) ? n_raw : -1;
@@ -469,11 +485,26 @@ __device__ __forceinline__ void pass1_body(
 #pragma unroll
                 for (int j = 0; j < 8; ++j) zf[s][j] = DVQ_BUF_LOAD(zr, zo, (16 * s + j) * HW * 4, NT ? 2 : 0);
             __builtin_amdgcn_s_setprio(0);
+            if constexpr (WGC) {
+                // the wave's copy mask (bit c = column c is a copy: not its cell's first position) goes to the other waves through
+                // LDS; the barrier behind the branch images publishes it
+                sel_g = dvq_gate_reduce(graw, rv.gate_mode, rv.G, rv.thr);
+                const int rep_g = rv.rep[sel_g];
+                const unsigned cm = (unsigned)__builtin_amdgcn_ballot_w64(!(y % rep_g == 0 && x % rep_g == 0) && h == 0);
+                if (lane == 0) wg_masks[wave] = cm;
+                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            } else
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the branch images (and its loads) landed;
             __builtin_amdgcn_s_barrier();                      // the barrier makes that true for the other waves' pieces
             asm volatile("" ::: "memory");
-            sel_g = dvq_gate_reduce(graw, rv.gate_mode, rv.G, rv.thr);
+            if constexpr (!WGC) sel_g = dvq_gate_reduce(graw, rv.gate_mode, rv.G, rv.thr);
             by_products(sel_g);
+            if constexpr (WGC) {
+                wgm0 = (unsigned)__builtin_amdgcn_readfirstlane((int)wg_masks[0]);
+                wgm1 = (unsigned)__builtin_amdgcn_readfirstlane((int)wg_masks[1]);
+                wgm2 = (unsigned)__builtin_amdgcn_readfirstlane((int)wg_masks[2]);
+                wgm3 = (unsigned)__builtin_amdgcn_readfirstlane((int)wg_masks[3]);
+            }
         }
     } else if constexpr (CONV) {
         conv_prologue(z + token_base(HW, h), (size_t)HW);
@@ -537,6 +568,38 @@ __device__ __forceinline__ void pass1_body(
     // (the short form, below).  copymask: bit c = column c is a copy (wave-uniform, in scalar registers through the loop).
     unsigned copymask = 0u;
     unsigned perm_off[2] = {0u, 0u};                         // scratch byte offset of the column at sorted position 16 t2 + (lane & 15)
+    // WGC: the order is the WORKGROUP's: its real columns wave by wave, in column order; sorted position p is scored by wave p / 32
+    // in column group (p / 16) & 1, and positions from nreal_wg on read a copy's (zero) operands.  The argument above carries over
+    // from the wave to the workgroup, and wave w scores ng = clamp(ceil((nreal_wg - 32 w) / 16), 0, 2) groups: the long form of
+    // the loop, the short one, or (ng = 0) the ring's protocol alone.
+    int ng = 2;
+    if constexpr (WGC) {
+        const int nr0 = 32 - __builtin_popcount(wgm0), nr1 = 32 - __builtin_popcount(wgm1), nr2 = 32 - __builtin_popcount(wgm2);
+        const int pf1 = nr0, pf2 = pf1 + nr1, pf3 = pf2 + nr2, nreal_wg = pf3 + 32 - __builtin_popcount(wgm3);
+        const int left = nreal_wg - 32 * wave + 15;
+        ng = __builtin_amdgcn_readfirstlane(left < 16 ? 0 : (left < 32 ? 1 : 2));
+        // the first copy of the workgroup: its operands are zeros (no copy at all: nreal_wg = 128, and no position refers to it)
+        const int wz = wgm0 ? 0 : (wgm1 ? 1 : (wgm2 ? 2 : 3));
+        const unsigned mz = wgm0 ? wgm0 : (wgm1 ? wgm1 : (wgm2 ? wgm2 : wgm3));
+        const int cz = mz ? __builtin_ctz(mz) : 0;
+#pragma unroll
+        for (int t2 = 0; t2 < 2; ++t2) {
+            const int P = 32 * wave + 16 * t2 + (lane & 15);
+            // the wave that holds the P-th real column, and the column: the k-th set bit of its real mask
+            const int ws = (P >= pf3) ? 3 : ((P >= pf2) ? 2 : ((P >= pf1) ? 1 : 0));
+            int k = P - ((P >= pf3) ? pf3 : ((P >= pf2) ? pf2 : ((P >= pf1) ? pf1 : 0)));
+            const unsigned real = ~((ws == 3) ? wgm3 : ((ws == 2) ? wgm2 : ((ws == 1) ? wgm1 : wgm0)));
+            int col = 0;
+#pragma unroll
+            for (int sh = 16; sh >= 1; sh >>= 1) {
+                const int cnt = __builtin_popcount((real >> col) & ((1u << sh) - 1u));
+                if (k >= cnt) { k -= cnt; col += sh; }
+            }
+            const bool past = P >= nreal_wg;
+            const unsigned wsrc = past ? (unsigned)wz : (unsigned)ws, csrc = past ? (unsigned)cz : (unsigned)col;
+            perm_off[t2] = wsrc * 2048u + (unsigned)(lane >> 5) * 1024u + (csrc + 32u * ((unsigned)(lane >> 4) & 1u)) * 16u;
+        }
+    } else
     if constexpr (SEL == 2) {
         copymask = (unsigned)__builtin_amdgcn_ballot_w64(sel_mask < 0.0f && h == 0);
         // column c sits at pos(c): a real column at its rank among the real ones, a copy at nreal + its rank among the copies.
@@ -608,6 +671,26 @@ __device__ __forceinline__ void pass1_body(
                 // k-step 2 s' + (lane >> 5) of the load layout: through the per-wave LDS scratch (a wave's LDS
                 // operations execute in order, so no barrier; 128 ds_bpermutes instead spilled 54 VGPRs)
                 const int sp = s >> 1;
+                if constexpr (WGC) {
+                    // the same through the workgroup's exchange buffers, [wave][2 KiB]: the barrier publishes pair sp, and the wait
+                    // in front of it has retired this wave's reads of pair sp - 1, so the buffer of pair sp - 1 may be written
+                    // again behind it.  Pairs 0 and 1 both take the scratches (one more barrier between them: the image's head is
+                    // still in use), from pair 2 on the image's head and the scratches alternate.  Every wave executes every one
+                    // of these barriers.
+                    char *xb = (sp >= 2 && !(sp & 1)) ? xbuf_b : xbuf_a;
+                    if (sp == 1) {
+                        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                        __builtin_amdgcn_s_barrier();
+                        asm volatile("" ::: "memory");
+                    }
+                    *(f16x8 *)(xb + wave * 2048 + lane * 16) = zprev;
+                    *(f16x8 *)(xb + wave * 2048 + 1024 + lane * 16) = zcur;
+                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                    __builtin_amdgcn_s_barrier();
+                    asm volatile("" ::: "memory");
+#pragma unroll
+                    for (int t2 = 0; t2 < 2; ++t2) zb[t2][sp] = *(const f16x8 *)(xb + perm_off[t2]);
+                } else {
                 *(f16x8 *)(scr + lane * 16) = zprev;
                 *(f16x8 *)(scr + 1024 + lane * 16) = zcur;
 #pragma unroll
@@ -618,6 +701,7 @@ __device__ __forceinline__ void pass1_body(
                     const int srcl = 16 * t2 + (lane & 15) + 32 * ((lane >> 4) & 1);
                     zb[t2][sp] = *(const f16x8 *)(scr + (lane >> 5) * 1024 + srcl * 16);
                     }
+                }
                 }
             }
             zprev = zcur;
@@ -643,6 +727,7 @@ __device__ __forceinline__ void pass1_body(
                      : dvq_filter_threshold(xn, amax, zeta2, sB, meta);
     }
     if (SEL == 2) {
+        if constexpr (WGC) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // ... and its operands of the last pair (slot buffer)
         __builtin_amdgcn_s_barrier();                        // every wave has read the branch images: the slots join the ring
         asm volatile("" ::: "memory");
     }
@@ -668,6 +753,23 @@ __device__ __forceinline__ void pass1_body(
         // half the top-2 update, half the re-seed -- and everything the workgroup shares as in the long form: the counted vmcnt wait,
         // the tile barrier, the DMA pieces of tile t + 3 at the same fragments, all 16 A-fragment reads and their counted waits.
         // One scalar branch around the loop picks the form; no wave leaves the ring's protocol.
+        // WGC: the form follows the wave's share of the workgroup's packed columns; a wave with none (ng = 0) performs the tile's
+        // counted wait, the barrier and its DMA pieces, and nothing else.
+        if constexpr (WGC) {
+            if (ng == 0) {
+#define DVQ_NG 0
+#include "pass1_loop.h"
+#undef DVQ_NG
+            } else if (ng == 1) {
+#define DVQ_NG 1
+#include "pass1_loop.h"
+#undef DVQ_NG
+            } else {
+#define DVQ_NG 2
+#include "pass1_loop.h"
+#undef DVQ_NG
+            }
+        } else
         if constexpr (SEL == 2) {
             if (__builtin_popcount(copymask) >= 16) {        // short wave: nreal <= 16 (wave-uniform, decided before the loop)
 #define DVQ_NG 1
@@ -707,6 +809,19 @@ __device__ __forceinline__ void pass1_body(
             rs[t2] = ms;
             rc[t2] = (mt + t_lo) * 32 + 16 * (r >> 2) + 4 * mq + (r & 3);
         }
+        if constexpr (WGC) {
+            // the triples go to a workgroup-wide table indexed by sorted position (the permutation scratches, idle since the
+            // prologue; the surplus DMA has landed): groups the wave did not score leave entries nobody reads
+            const int lane_t = (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
+            if (lane_t < 16) {
+#pragma unroll
+                for (int t2 = 0; t2 < 2; ++t2) {
+                    const f32x4 mine = {rb[t2], rs[t2], __int_as_float(rc[t2]), 0.0f};
+                    *(f32x4 *)(xbuf_a + (32 * wave + 16 * t2 + lane_t) * 16) = mine;
+                }
+            }
+            best = 0.0f; second = 0.0f; code = 0;            // (taken from the table below)
+        } else
         if constexpr (SEL == 2) {
             // the column's sorted position pos(c) again, from the mask and the lane id (nothing of the prologue's lives in a VGPR
             // through the loop).  A short wave's positions >= 16 are copies: what they pick from the unscored group is replaced by
@@ -747,6 +862,22 @@ __device__ __forceinline__ void pass1_body(
         asm volatile("" : "+v"(am));                         // (opaque: nothing derived from it is computed ahead of the loop)
         const int rm1 = (am == 1.0f) ? 0 : ((am == 0.25f) ? 1 : 3);             // rep - 1
         char *hand = lds + NBUF * IMG_BYTES + NBUF * NW * 64 * 4;               // [wave][2 KiB]: 32 columns x 16 B in use
+        if constexpr (WGC) {
+            // the owner (a real column: row wave_o, column c_o) sits at sorted position prefix(wave_o) + its rank among that wave's
+            // real columns, re-derived from the four masks (scalar) and the lane id
+            unsigned m0 = wgm0, m1 = wgm1, m2 = wgm2, m3 = wgm3;
+            asm volatile("" : "+s"(m0), "+s"(m1), "+s"(m2), "+s"(m3));          // (opaque: derived behind the loop)
+            const int wave_o = wave - (wave & rm1), c_o = c_e - (c_e & rm1);
+            const int q1 = 32 - __builtin_popcount(m0), q2 = q1 + 32 - __builtin_popcount(m1), q3 = q2 + 32 - __builtin_popcount(m2);
+            const unsigned m_o = (wave_o == 0) ? m0 : ((wave_o == 1) ? m1 : ((wave_o == 2) ? m2 : m3));
+            const int pf_o = (wave_o == 0) ? 0 : ((wave_o == 1) ? q1 : ((wave_o == 2) ? q2 : q3));
+            const int p_o = pf_o + __builtin_popcount(~m_o & ((1u << c_o) - 1u));
+            __syncthreads();
+            const f32x4 own = *(const f32x4 *)(hand + p_o * 16);
+            best = own[0];
+            second = own[1];
+            code = __float_as_int(own[2]);
+        } else {
         if (lane_e < 32) {
             const f32x4 mine = {best, second, __int_as_float(code), 0.0f};
             *(f32x4 *)(hand + wave * 2048 + c_e * 16) = mine;
@@ -756,6 +887,7 @@ __device__ __forceinline__ void pass1_body(
         best = own[0];                                       // (a cell's first position reads back what it wrote)
         second = own[1];
         code = __float_as_int(own[2]);
+        }
     }
     if constexpr (SPLIT) {
         // hand-off without fences (MI355X guide, inter-workgroup visibility: every payload store write-through (sc1) and drained by

@@ -2,7 +2,9 @@
 // DVQ_NG = 2 scores both column groups of the wave (t2 = 0, 1), DVQ_NG = 1 the first one alone (the short form of SEL == 2: a wave
 // whose second group holds only copies of coarser cells).  Everything the workgroup shares -- the counted vmcnt wait, the tile
 // barrier, the DMA pieces of tile t + 3 at the same fragments, all 16 A-fragment reads and their counted waits -- is the same in
-// both.  Uses pass1_body's locals (b1, b2, bt, zb, lds, enraw, issue, issue_piece, T, q16, lane, wave) and no include guard.
+// both.  DVQ_NG = 0 (a wave of the workgroup-packed form, SEL == 2 at D = 256, with no column group to score) keeps the counted wait,
+// the barrier and its DMA pieces, and nothing else.  Uses pass1_body's locals (b1, b2, bt, zb, lds, enraw, issue, issue_piece, T, q16, lane, wave) and no include guard.
+#if DVQ_NG != 0
         f32x4 acc16[2][2];
         auto top2 = [&](int tt) {
 #pragma unroll
@@ -22,11 +24,16 @@
                 bt[t2] = (b1[t2] != om) ? tt : bt[t2];
             }
         };
+#endif
     for (int t = 0; t < T; ++t) {
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER_TILE) : "memory");   // all but the youngest tile's DMA: tiles <= t + 1 landed
             __builtin_amdgcn_s_barrier();                    // tile t (everybody's DMA) landed; t-1 consumed
             asm volatile("" ::: "memory");
             if (S16 != 16) issue(t + 3);                     // D = 256: pieces ride between the MFMAs below
+#if DVQ_NG == 0
+            if (S16 == 16) issue(t + 3);                     // no column group: this wave's pieces of tile t + 3, at once
+        }
+#else
             // A fragments: hand-placed LDS reads, four k-steps ahead of the MFMA that consumes them
             // (ds_read returns in order: lgkmcnt(3) = "the oldest of my four reads has landed")
             const unsigned tile_a = (unsigned)(size_t)(const __attribute__((address_space(3))) char *)(
@@ -80,3 +87,4 @@
             __builtin_amdgcn_s_setprio(0);
         }
         top2(T - 1);
+#endif
