@@ -45,6 +45,7 @@ TRANSFER_SOS_NONE, TRANSFER_SOS_CONST, TRANSFER_SOS_COPY = 0, 1, 2
 METRIC_L2, METRIC_DOT = 0, 1   # dvq_vq_score_assign_f32: s = -distance / s = dot product
 DTYPE_F16, DTYPE_BF16 = 1, 2   # DVQ_DTYPE_*: the 16-bit latents of the *_x16 entry points
 X16 = {torch.float16: DTYPE_F16, torch.bfloat16: DTYPE_BF16}
+NHWC = 0x1000                  # DVQ_NHWC: channels_last branch features, OR-ed into the same argument as FEATURES(dtype)
 
 
 def FEATURES(dtype):

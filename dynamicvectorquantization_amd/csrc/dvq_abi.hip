@@ -7,7 +7,7 @@
 #include "../../include/dvq.h"
 #include "launchers.h"
 
-#define DVQ_VERSION 1900   // 0.19.0 (include/dvq.h lists what each version changed)
+#define DVQ_VERSION 2000   // 0.20.0 (include/dvq.h lists what each version changed)
 #define DVQ_ROUTE_MAX_CELLS_ABI 1024   // = DVQ_ROUTE_MAX_CELLS (dvq_filter.h)
 
 static thread_local char g_err[512] = "";
@@ -526,15 +526,25 @@ int dvq_entropy_gate_f32(const float *entropy, int64_t n, float thr, int64_t *ga
     return hip_rc(dvq_launch_entropy_gate(entropy, (long)n, thr, (long long *)gate, (hipStream_t)stream), "entropy_gate");
 }
 
-// DVQ_FEATURES(dtype) OR-ed into the one enumerated argument of the select / gate entry points: the enumerator is the low byte,
-// the feature dtype the bits above it (0 = float32).  A negative value carries no flag: it is an unknown enumerator as a whole.
+// DVQ_FEATURES(dtype) and DVQ_NHWC OR-ed into the one enumerated argument of the select / gate entry points: the enumerator is the
+// low byte, the feature dtype bits 8 - 11 (0 = float32), the layout bit 12 (DVQ_NHWC: channels_last branches); nothing above it.
+// A negative value carries no flag: it is an unknown enumerator as a whole.
 static int enum_of(int v) { return v < 0 ? v : (v & 0xFF); }
-static int features_of(int v) { return v < 0 ? 0 : (v >> 8); }
+static int features_of(int v) { return v < 0 ? 0 : ((v >> 8) & 0xF); }
+static int layout_of(int v) { return v < 0 ? 0 : ((v >> 12) & 1); }
 
 static int check_features(const char *fn, int xt)
 {
     if (xt == 0 || xt == DVQ_DTYPE_F16 || xt == DVQ_DTYPE_BF16) return DVQ_OK;
     dvq_set_error("%s: DVQ_FEATURES dtype %d (0 = float32, DVQ_DTYPE_F16 = 1, DVQ_DTYPE_BF16 = 2)", fn, xt);
+    return DVQ_EINVAL;
+}
+
+// the bits of the argument that no flag owns (checked after the enumerator, before the dtype)
+static int check_flag_bits(const char *fn, int v)
+{
+    if (v < 0 || (v >> 13) == 0) return DVQ_OK;
+    dvq_set_error("%s: flag bits 0x%x above DVQ_NHWC (the argument carries an enumerator, DVQ_FEATURES(dtype) and DVQ_NHWC)", fn, v & ~0x1FFF);
     return DVQ_EINVAL;
 }
 
@@ -545,13 +555,21 @@ static int route_args_ok(const char *fn, const void *gate, int gate_dtype, const
     if (!gate || !a || !b || !h_out || !indices || !cmask) return null_pointer(fn);
     const int gd = enum_of(gate_dtype);
     if (gd != DVQ_GATE_F32 && gd != DVQ_GATE_I64) { dvq_set_error("%s: gate_dtype %d", fn, gd); return DVQ_EINVAL; }
+    if (int rc = check_flag_bits(fn, gate_dtype)) return rc;
     if (int rc = check_features(fn, features_of(gate_dtype))) return rc;
     if (B <= 0 || C <= 0 || hc <= 0 || wc <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     if (features_of(gate_dtype) != 0 && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)h_out) & 1) != 0) {
         dvq_set_error("%s: 16-bit features must be 2-byte aligned", fn); return DVQ_EINVAL;
     }
+    // DVQ_NHWC: a workgroup numbers the pieces (2 bytes at least) of one row of output pixels with 32 bits
+    if (layout_of(gate_dtype) && (double)wc * 4.0 * (double)C * 4.0 >= 2147483648.0) {
+        dvq_set_error("%s: DVQ_NHWC: a row of %d cells x C=%d is too long (16 * wc * C < 2^31)", fn, wc, C); return DVQ_EUNSUPPORTED;
+    }
     return DVQ_OK;
 }
+
+// bytes per feature element of a flagged argument
+static int feature_bytes(int v) { return features_of(v) != 0 ? 2 : 4; }
 
 int dvq_route_select_dual_f32(const void *gate, int gate_dtype, const void *h_coarse,
                               const void *h_fine, int B, int C, int hc, int wc,
@@ -560,6 +578,9 @@ int dvq_route_select_dual_f32(const void *gate, int gate_dtype, const void *h_co
     int rc = route_args_ok("dvq_route_select_dual_f32", gate, gate_dtype, h_coarse, h_fine, B, C, hc, wc, h_out, indices, cmask);
     if (rc) return rc;
     const int gate_mode = enum_of(gate_dtype) == DVQ_GATE_I64;
+    if (layout_of(gate_dtype))
+        return hip_rc(dvq_launch_route_select_rows(2, gate_mode, gate, h_coarse, nullptr, h_fine, feature_bytes(gate_dtype), B, C, hc, wc,
+                                                   h_out, (long long *)indices, cmask, (hipStream_t)stream), "route_select_dual");
     if (features_of(gate_dtype) != 0)
         return hip_rc(dvq_launch_route_select_x16(2, gate_mode, gate, h_coarse, nullptr, h_fine, B, C, hc, wc, h_out,
                                                   (long long *)indices, cmask, (hipStream_t)stream), "route_select_dual");
@@ -587,8 +608,13 @@ int dvq_route_select_triple_f32(const void *gate, int gate_dtype, const void *h_
     if (rc) return rc;
     if (!h_median) { dvq_set_error("dvq_route_select_triple_f32: null h_median"); return DVQ_EINVAL; }
     const int gate_mode = enum_of(gate_dtype) == DVQ_GATE_I64;
+    if (features_of(gate_dtype) != 0 && ((uintptr_t)h_median & 1) != 0) {
+        dvq_set_error("dvq_route_select_triple_f32: 16-bit features must be 2-byte aligned"); return DVQ_EINVAL;
+    }
+    if (layout_of(gate_dtype))
+        return hip_rc(dvq_launch_route_select_rows(3, gate_mode, gate, h_coarse, h_median, h_fine, feature_bytes(gate_dtype), B, C, hc, wc,
+                                                   h_out, (long long *)indices, cmask, (hipStream_t)stream), "route_select_triple");
     if (features_of(gate_dtype) != 0) {
-        if (((uintptr_t)h_median & 1) != 0) { dvq_set_error("dvq_route_select_triple_f32: 16-bit features must be 2-byte aligned"); return DVQ_EINVAL; }
         return hip_rc(dvq_launch_route_select_x16(3, gate_mode, gate, h_coarse, h_median, h_fine, B, C, hc, wc, h_out,
                                                   (long long *)indices, cmask, (hipStream_t)stream), "route_select_triple");
     }
@@ -724,14 +750,20 @@ int dvq_router_gate_f32(int nb, const void *h_coarse, const void *h_median, cons
 {
     const char *fn = "dvq_router_gate_f32";
     const int activation = enum_of(activation_arg), xt = features_of(activation_arg);    // DVQ_FEATURES(dtype): 16-bit branches
+    const int nhwc = layout_of(activation_arg);                                          // DVQ_NHWC: channels_last branches
     if (nb != 2 && nb != 3) { dvq_set_error("%s: num_branches=%d (2 or 3)", fn, nb); return DVQ_EINVAL; }
     if (!h_coarse || !h_fine || !w2 || !b2 || !gate) return null_pointer(fn);
     if ((nb == 3) != (h_median != nullptr)) { dvq_set_error("%s: h_median must be given exactly when num_branches == 3", fn); return DVQ_EINVAL; }
     if (B <= 0 || C <= 0 || hc <= 0 || wc <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
     if (activation != DVQ_ACT_NONE && activation != DVQ_ACT_SILU && activation != DVQ_ACT_RELU) { dvq_set_error("%s: unknown activation %d", fn, activation); return DVQ_EINVAL; }
+    if (int rc = check_flag_bits(fn, activation_arg)) return rc;
     if (int rc = check_features(fn, xt)) return rc;
+    // channels_last branches: the pooling pass takes the piece width the actual alignment allows, down to one element
+    if (nhwc && (((uintptr_t)h_coarse | (uintptr_t)h_median | (uintptr_t)h_fine) & (xt != 0 ? 1 : 3)) != 0) {
+        dvq_set_error("%s: DVQ_NHWC features must be aligned to their element size (%d bytes)", fn, xt != 0 ? 2 : 4); return DVQ_EINVAL;
+    }
     // the pooling pass reads four 2-byte elements with one 8-byte load
-    if (xt != 0 && (((uintptr_t)h_coarse | (uintptr_t)h_median | (uintptr_t)h_fine) & 7) != 0) { dvq_set_error("%s: 16-bit features must be 8-byte aligned", fn); return DVQ_EINVAL; }
+    if (!nhwc && xt != 0 && (((uintptr_t)h_coarse | (uintptr_t)h_median | (uintptr_t)h_fine) & 7) != 0) { dvq_set_error("%s: 16-bit features must be 8-byte aligned", fn); return DVQ_EINVAL; }
     if (activation != DVQ_ACT_NONE && (!w1 || !b1 || hidden <= 0)) { dvq_set_error("%s: hidden layer requested without w1 / b1 / hidden", fn); return DVQ_EINVAL; }
     if (num_groups < 0 || (num_groups > 0 && C % num_groups != 0)) { dvq_set_error("%s: C=%d is not divisible by num_groups=%d", fn, C, num_groups); return DVQ_EINVAL; }
     if (num_groups > 0 && (!gn_w_coarse || !gn_b_coarse || !gn_w_fine || !gn_b_fine || (nb == 3 && (!gn_w_median || !gn_b_median)))) {
@@ -757,7 +789,7 @@ int dvq_router_gate_f32(int nb, const void *h_coarse, const void *h_median, cons
         gw[0] = gn_w_coarse; gw[1] = gn_w_median; gw[2] = gn_w_fine;
         gb[0] = gn_b_coarse; gb[1] = gn_b_median; gb[2] = gn_b_fine;
     }
-    return hip_rc(dvq_launch_router_gate(nb, h, xt, gw, gb, B, C, hc, wc, num_groups, eps, w1, b1, w2, b2,
+    return hip_rc(dvq_launch_router_gate(nb, h, xt, nhwc, gw, gb, B, C, hc, wc, num_groups, eps, w1, b1, w2, b2,
                                          hid, activation, w1_prep, gate, ws, (hipStream_t)stream), "router_gate");
 }
 

@@ -42,6 +42,10 @@ int dvq_launch_route_select(int G, int gate_mode, const void *gate, const float 
 int dvq_launch_route_select_x16(int G, int gate_mode, const void *gate, const void *h_coarse, const void *h_median,
                                 const void *h_fine, int B, int C, int hc, int wc, void *h_out, long long *indices,
                                 float *cmask, hipStream_t st);
+// the select on channels_last features (DVQ_NHWC: [B, rows, cols, C]) of es-byte elements, moved as bytes; gate_mode 0 / 1 only
+int dvq_launch_route_select_rows(int G, int gate_mode, const void *gate, const void *h_coarse, const void *h_median,
+                                 const void *h_fine, int es, int B, int C, int hc, int wc, void *h_out, long long *indices,
+                                 float *cmask, hipStream_t st);
 int dvq_launch_entropy_gate(const float *ent, long n, float thr, long long *gate, hipStream_t st);
 // xt (here and below): the type of the latent-shaped tensors, 0 = float32, DVQ_DTYPE_F16 / DVQ_DTYPE_BF16 (dvq_common.h: DvqLat);
 // anything else returns -1000
@@ -106,7 +110,8 @@ int dvq_launch_ema_update(const float *stats_sum, const float *stats_count, floa
 int dvq_launch_router_gate_prepare_norm(const float *const *gn_w, const float *const *gn_b, int nb, int C, int Hid, void *prep,
                                         hipStream_t st);
 // xt: the type of the branch features h (0 = float32, DVQ_DTYPE_F16 / DVQ_DTYPE_BF16: widened where the pooling pass loads them)
-int dvq_launch_router_gate(int nb, const void *const *h, int xt, const float *const *gn_w, const float *const *gn_b,
+// nhwc: the branches are channels_last, [B, rows, cols, C] (DVQ_NHWC: the pooling pass reads them in place)
+int dvq_launch_router_gate(int nb, const void *const *h, int xt, int nhwc, const float *const *gn_w, const float *const *gn_b,
                            int B, int C, int hc, int wc, int groups, float eps,
                            const float *W1, const float *b1, const float *W2, const float *b2,
                            int Hid, int act, const void *w1_prep, float *gate, void *ws, hipStream_t st);

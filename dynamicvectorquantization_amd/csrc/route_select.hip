@@ -251,6 +251,67 @@ __global__ __launch_bounds__(256) void route_select_x16_kernel(
     }
 }
 
+// ---- the same select on channels_last branches (DVQ_NHWC in dvq.h): every branch and h_out are [B, rows, cols, C] row-major, a
+// pixel is ONE run of C elements.  Nothing is converted and nothing depends on the element type, so one kernel serves float32,
+// fp16 and bf16: a pixel's run is moved as raw bytes in pieces of V bytes, V the widest of 16, 8, 4, 2 that divides the run
+// (row_bytes = C x element size) and fits the actual alignment of the four tensors (the launcher's choice: a view that starts one
+// element into its storage moves narrower pieces).  Workgroup = one row y of one image's output: its W x ppr pieces (ppr =
+// row_bytes / V) are dealt to the threads in memory order, so a wave's accesses to h_out and to a fine source are one contiguous
+// run.  The grain of a piece's cell is evaluated where it is needed, by the rule of the kernels above (gate_argmax): the logits
+// of a cell are a few bytes that the SC x SC x ppr pieces of the cell share (a broadcast within a wave, an L1 / L2 hit across
+// waves) -- no grain map in LDS, hence no second regime at many cells.  A fine pixel that is not selected is never read; coarse
+// and median runs are read with plain loads (each is wanted 4 or 16 times), fine runs and h_out non-temporally when nt is set
+// (the launcher: the output exceeds DVQ_CACHED_MAX_BYTES).  The thread that moves a pixel's first piece writes its codebook_mask
+// value, and at a cell's first pixel the cell's index: the values of the NCHW kernels.  MODE 0 / 1 as above.
+template <int V> struct PieceOf;
+template <> struct PieceOf<16> { typedef unsigned type __attribute__((ext_vector_type(4))); };
+template <> struct PieceOf<8> { typedef unsigned type __attribute__((ext_vector_type(2))); };
+template <> struct PieceOf<4> { typedef unsigned type; };
+template <> struct PieceOf<2> { typedef unsigned short type; };
+template <int G, int MODE, int V>
+__global__ __launch_bounds__(256) void route_select_rows_kernel(
+    const void *__restrict__ gate, const char *__restrict__ h_coarse, const char *__restrict__ h_median,
+    const char *__restrict__ h_fine, int B, unsigned row_bytes, int hc, int wc, char *__restrict__ h_out,
+    long long *__restrict__ indices, float *__restrict__ cmask, unsigned ppr, int ppr_shift, int nt)
+{
+    static_assert(MODE == 0 || MODE == 1, "float32 logits or the int64 gate");
+    constexpr unsigned SC = (G == 2) ? 2 : 4;     // fine pixels per coarse cell edge
+    typedef typename PieceOf<V>::type piece_t;
+    const unsigned H = SC * (unsigned)hc, W = SC * (unsigned)wc;
+    const unsigned per_row = W * ppr;             // pieces of one row of pixels (< 2^31: dvq_abi.hip)
+    for (unsigned b = blockIdx.y; b < (unsigned)B; b += gridDim.y)
+    for (unsigned y = blockIdx.x; y < H; y += gridDim.x) {
+        const unsigned cy = y / SC;
+        const size_t orow = ((size_t)b * H + y) * W;                     // the row's first pixel in h_out / h_fine / cmask
+        const size_t crow = ((size_t)b * hc + cy) * wc;                  // its row of cells
+        const size_t mrow = ((size_t)b * (2 * hc) + y / 2) * (2 * wc);   // (triple) its row of median pixels
+        for (unsigned j = threadIdx.x; j < per_row; j += 256) {
+            unsigned x, q;
+            if (ppr_shift >= 0) { x = j >> ppr_shift; q = j & (ppr - 1); }
+            else { x = j / ppr; q = j - x * ppr; }
+            const size_t cell = crow + x / SC;
+            const int g = gate_argmax<G, MODE>(gate, cell, 0.0f);
+            const size_t off = (size_t)q * V;
+            piece_t v;
+            if (g == G - 1) {
+                const piece_t *s = (const piece_t *)(h_fine + (orow + x) * row_bytes + off);
+                v = nt ? __builtin_nontemporal_load(s) : *s;
+            } else if (G == 3 && g == 1) {
+                v = *(const piece_t *)(h_median + (mrow + x / 2) * row_bytes + off);
+            } else {
+                v = *(const piece_t *)(h_coarse + cell * row_bytes + off);
+            }
+            piece_t *d = (piece_t *)(h_out + (orow + x) * row_bytes + off);
+            if (nt) __builtin_nontemporal_store(v, d);
+            else *d = v;
+            if (q == 0) {
+                cmask[orow + x] = (G == 2) ? (g == 0 ? 0.25f : 1.0f) : (g == 0 ? 0.0625f : (g == 1 ? 0.25f : 1.0f));
+                if (y % SC == 0 && x % SC == 0) indices[cell] = g;
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void entropy_gate_kernel(const float *__restrict__ ent, long n,
                                                            float thr, long long *__restrict__ gate)
 {
@@ -340,6 +401,34 @@ int dvq_launch_route_select_x16(int G, int gate_mode, const void *gate, const vo
     else DVQ_SEL16V(3, 0);
 #undef DVQ_SEL16V
 #undef DVQ_SEL16
+    return (int)hipGetLastError();
+}
+
+// channels_last features of es-byte elements (see route_select_rows_kernel): the piece width from the run length and the actual
+// alignment of the four tensors; cached / non-temporal by the size of the output (DVQ_CACHED_MAX_BYTES, as the gate's pooling pass)
+int dvq_launch_route_select_rows(int G, int gate_mode, const void *gate, const void *h_coarse, const void *h_median,
+                                 const void *h_fine, int es, int B, int C, int hc, int wc, void *h_out, long long *indices,
+                                 float *cmask, hipStream_t st)
+{
+    const unsigned SC = G == 2 ? 2 : 4;
+    const unsigned row_bytes = (unsigned)C * (unsigned)es;
+    const uintptr_t al = (uintptr_t)h_coarse | (uintptr_t)h_median | (uintptr_t)h_fine | (uintptr_t)h_out;
+    unsigned V = 16;
+    while (V > 2 && (row_bytes % V != 0 || al % V != 0)) V >>= 1;
+    const unsigned ppr = row_bytes / V;
+    int ppr_shift = -1;
+    if ((ppr & (ppr - 1)) == 0) { ppr_shift = 0; while ((1u << ppr_shift) < ppr) ++ppr_shift; }
+    const int nt = (size_t)B * SC * hc * SC * wc * row_bytes > DVQ_CACHED_MAX_BYTES;
+    dim3 grid(SC * (unsigned)hc, B < 65535 ? B : 65535), block(256);
+    typedef const char *cch;
+#define DVQ_SELR(GG, MM, VV) hipLaunchKernelGGL((route_select_rows_kernel<GG, MM, VV>), grid, block, 0, st, gate, (cch)h_coarse, (cch)h_median, (cch)h_fine, B, row_bytes, hc, wc, (char *)h_out, indices, cmask, ppr, ppr_shift, nt)
+#define DVQ_SELRV(GG, MM) do { if (V == 16) DVQ_SELR(GG, MM, 16); else if (V == 8) DVQ_SELR(GG, MM, 8); else if (V == 4) DVQ_SELR(GG, MM, 4); else DVQ_SELR(GG, MM, 2); } while (0)
+    if (G == 2 && gate_mode == 1) DVQ_SELRV(2, 1);
+    else if (G == 2) DVQ_SELRV(2, 0);
+    else if (gate_mode == 1) DVQ_SELRV(3, 1);
+    else DVQ_SELRV(3, 0);
+#undef DVQ_SELRV
+#undef DVQ_SELR
     return (int)hipGetLastError();
 }
 

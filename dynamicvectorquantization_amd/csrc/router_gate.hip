@@ -270,6 +270,197 @@ __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArg
     }
 }
 
+// ---- 1b. the same pass on channels_last branches (DVQ_NHWC in dvq.h): h[br] is [B, rows, cols, C] row-major, a pixel one run of
+// C elements.  The decomposition is gate_pool_kernel's -- workgroup = (image b, channel group g) -- and so is everything it
+// writes: ab, and the raw averages pool[...] or (IMG) the normalised split operand images with the same power-of-two scale; the
+// kernels behind it, the workspace and the prep do not know the layout.  Only the walk over the features differs: a thread owns
+// (cell, piece) pairs, a piece being E consecutive channels of the group's cpg-channel slice of a pixel (a.vec = E: 16 bytes
+// where cpg and the branches' alignment allow -- 4 floats, 8 halves widened where loaded --, else 8, 4, 2 or 1 elements; the
+// launcher's choice), and loads that piece of the cell's sc x sc pixels.  Per channel the average is the NCHW pass's expression
+// on the same pixels, ((a + b) + (c + d)) * 0.25f and four such row sums * 0.0625f, hence the same bits; the GroupNorm sums are
+// doubles added in a fixed order (thread, wave, workgroup), another order than the NCHW pass's.  Pieces are the fast index, so
+// neighbouring lanes read a pixel's slice (cpg elements: 32 B at cpg = 8 float32) and then the next cell's: short runs out of
+// C-element rows, whose remaining bytes the workgroups of the neighbouring groups read.  Those workgroups are therefore dealt to
+// ONE XCD, one after the other (workgroups go round-robin over the 8 XCDs: workgroup i takes the logical index
+// (i % 8) * chunk + i / 8, the grid is rounded up to 8 * chunk and the surplus exits), so that a line fetched for one of them is
+// an L2 hit for the others.  Arithmetic behind the load, LDS staging and the IMG epilogue: gate_pool_kernel's, restated here so
+// that its instantiations keep their machine code.
+template <int XT, bool NT, int E> __device__ __forceinline__ void gate_ld_piece(const typename GateElem<XT>::T *p, float (&r)[E])
+{
+    static_assert(XT != 0 || E <= 4, "a piece is at most 16 bytes");
+    if constexpr (E == 1) {
+        r[0] = gate_ld1<XT, NT>(p);
+    } else {
+        typedef typename GateElem<XT>::T vec_t __attribute__((ext_vector_type(E)));
+        const vec_t v = GATE_LD((const vec_t *)p);
+#pragma unroll
+        for (int j = 0; j < E; ++j) {
+            if constexpr (XT == 0) r[j] = v[j];
+            else r[j] = dvq_widen_bits<XT>(v[j]);
+        }
+    }
+}
+// one branch of one workgroup: p0 = the group's slice of the image's first pixel, o0[channel of the group][cell] the averages
+template <int XT, bool NT, int E>
+__device__ __forceinline__ void gate_pool_rows_branch(const typename GateElem<XT>::T *p0, int C, int sc, int wc, int cpg, int ncell,
+                                                      float *o0, double &s, double &ss)
+{
+    typedef typename GateElem<XT>::T elem_t;
+    const int npc = cpg / E;                                 // pieces of a pixel's slice
+    const size_t rowp = (size_t)wc * sc * C;                 // elements from a pixel to the one below it
+    auto stats = [&](const float (&r)[E]) {
+#pragma unroll
+        for (int j = 0; j < E; ++j) { s += r[j]; ss += (double)r[j] * r[j]; }
+    };
+    for (int u = threadIdx.x; u < ncell * npc; u += 256) {
+        const int cell = u / npc, pc = u - cell * npc;
+        const int y = cell / wc, x = cell - y * wc;
+        const elem_t *p = p0 + (size_t)sc * y * rowp + (size_t)sc * x * C + pc * E;
+        float v[E];
+        if (sc == 1) {
+            gate_ld_piece<XT, NT, E>(p, v);
+            stats(v);
+        } else if (sc == 2) {
+            float r00[E], r01[E], r10[E], r11[E];
+            gate_ld_piece<XT, NT, E>(p, r00);
+            gate_ld_piece<XT, NT, E>(p + C, r01);
+            gate_ld_piece<XT, NT, E>(p + rowp, r10);
+            gate_ld_piece<XT, NT, E>(p + rowp + C, r11);
+            stats(r00); stats(r01); stats(r10); stats(r11);
+#pragma unroll
+            for (int j = 0; j < E; ++j) v[j] = ((r00[j] + r01[j]) + (r10[j] + r11[j])) * 0.25f;
+        } else {
+            float s4[E];
+#pragma unroll
+            for (int j = 0; j < E; ++j) s4[j] = 0.0f;
+#pragma unroll 1                                             // a row of the cell at a time: 4 loads in flight, registers for 8 waves per SIMD
+            for (int i = 0; i < 4; ++i) {
+                float r0[E], r1[E], r2[E], r3[E];
+                gate_ld_piece<XT, NT, E>(p + i * rowp, r0);
+                gate_ld_piece<XT, NT, E>(p + i * rowp + C, r1);
+                gate_ld_piece<XT, NT, E>(p + i * rowp + 2 * (size_t)C, r2);
+                gate_ld_piece<XT, NT, E>(p + i * rowp + 3 * (size_t)C, r3);
+#pragma unroll
+                for (int j = 0; j < E; ++j) s4[j] += (r0[j] + r1[j]) + (r2[j] + r3[j]);
+                stats(r0); stats(r1); stats(r2); stats(r3);
+            }
+#pragma unroll
+            for (int j = 0; j < E; ++j) v[j] = s4[j] * 0.0625f;
+        }
+#pragma unroll
+        for (int j = 0; j < E; ++j) o0[(size_t)(pc * E + j) * ncell + cell] = v[j];
+    }
+}
+template <bool IMG, bool NT, int XT = 0>
+__global__ __launch_bounds__(256, 4) void gate_pool_rows_kernel(DvqGateArgs a, float2 *__restrict__ ab,
+                                                       float *__restrict__ pool, char *__restrict__ ximg,
+                                                       float *__restrict__ xs, const float *__restrict__ nbound,
+                                                       int nwg, int chunk)
+{
+    const int G = a.groups > 0 ? a.groups : a.C / 8;
+    const int cpg = a.C / G;
+    const int wg = (int)(blockIdx.x & 7) * chunk + (int)(blockIdx.x >> 3);   // neighbouring groups on one XCD, see above
+    if (wg >= nwg) return;
+    const int b = wg / G, g = wg - b * G;
+    const int ncell = a.hc * a.wc, F = a.nb * a.C;
+    const int npair = cpg * ncell;
+    __shared__ double red[3][2][4];                          // [branch (IMG; else 0)][sum | sum of squares][wave]
+    __shared__ float s_bound[4];
+    __shared__ float2 s_aff[3 * 64];                         // IMG: (scale, shift) of the group's channels, per branch
+    extern __shared__ float lp[];                            // IMG: [branch][cpg][ncell] pooled averages
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float xscale = 1.0f;
+    if (IMG) {                                               // the fp16 range bound and its power-of-two scale: gate_pool_kernel's
+        float bound = 0.0f;
+        if (nbound != nullptr && __builtin_bit_cast(int, nbound[0]) == DVQ_GATE_NORM_MAGIC) {
+            for (int br = 0; br < a.nb; ++br) {
+                const float n = (float)cpg * (float)(a.hc * a.scale[br]) * (float)(a.wc * a.scale[br]);
+                bound = fmaxf(bound, nbound[1 + 2 * br] * sqrtf(n) * 1.0001f + nbound[2 + 2 * br]);
+            }
+        } else {
+            for (int k = tid; k < F; k += 256) {
+                const int br = k / a.C, ch = k - br * a.C;
+                const float n = (float)cpg * (float)(a.hc * a.scale[br]) * (float)(a.wc * a.scale[br]);
+                bound = fmaxf(bound, fabsf(a.gn_w[br][ch]) * sqrtf(n) * 1.0001f + fabsf(a.gn_b[br][ch]));
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) bound = fmaxf(bound, __shfl_xor(bound, off));
+            if (lane == 0) s_bound[wave] = bound;
+            __syncthreads();
+            bound = fmaxf(fmaxf(s_bound[0], s_bound[1]), fmaxf(s_bound[2], s_bound[3]));
+        }
+        float inv = 1.0f;
+        if (bound > 0.0f && bound < __builtin_inff()) {
+            int e;
+            (void)frexpf(bound, &e);
+            const int sh = 13 - e < 100 ? 13 - e : 100;
+            xscale = ldexpf(1.0f, sh);
+            inv = ldexpf(1.0f, -sh);
+        }
+        if (wg == 0 && tid == 0) xs[0] = inv;
+    }
+    for (int br = 0; br < a.nb; ++br) {
+        const int sc = a.scale[br];
+        typedef typename GateElem<XT>::T elem_t;
+        const elem_t *p0 = (const elem_t *)a.h[br] + (size_t)b * (a.hc * sc) * (a.wc * sc) * a.C + (size_t)g * cpg;
+        float *o0 = IMG ? lp + (size_t)br * npair : pool + ((size_t)b * F + (size_t)br * a.C + (size_t)g * cpg) * ncell;
+        double s = 0.0, ss = 0.0;
+        if (XT != 0 && a.vec == 8) {
+            if constexpr (XT != 0) gate_pool_rows_branch<XT, NT, 8>(p0, a.C, sc, a.wc, cpg, ncell, o0, s, ss);
+        } else if (a.vec == 4) gate_pool_rows_branch<XT, NT, 4>(p0, a.C, sc, a.wc, cpg, ncell, o0, s, ss);
+        else if (a.vec == 2) gate_pool_rows_branch<XT, NT, 2>(p0, a.C, sc, a.wc, cpg, ncell, o0, s, ss);
+        else gate_pool_rows_branch<XT, NT, 1>(p0, a.C, sc, a.wc, cpg, ncell, o0, s, ss);
+        auto affine = [&](int brr, int chl) -> float2 {      // the group's statistics of branch brr folded with channel chl's affine
+            const double n = (double)cpg * (double)(a.hc * a.scale[brr]) * (double)(a.wc * a.scale[brr]);
+            const int rb = IMG ? brr : 0;
+            const double mean = ((red[rb][0][0] + red[rb][0][1]) + (red[rb][0][2] + red[rb][0][3])) / n;
+            double var = ((red[rb][1][0] + red[rb][1][1]) + (red[rb][1][2] + red[rb][1][3])) / n - mean * mean;   // biased, as GroupNorm
+            if (var < 0.0) var = 0.0;
+            const float mf = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)a.eps));
+            const int ch = g * cpg + chl;
+            const float sc_ = rstd * a.gn_w[brr][ch];
+            return make_float2(sc_, a.gn_b[brr][ch] - mf * sc_);
+        };
+        if (a.groups > 0) {
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off); ss += __shfl_xor(ss, off); }
+            if (IMG) {                                       // one barrier for all branches, after the loop
+                if (lane == 0) { red[br][0][wave] = s; red[br][1][wave] = ss; }
+            } else {
+                __syncthreads();                             // red[] of the previous branch consumed
+                if (lane == 0) { red[0][0][wave] = s; red[0][1][wave] = ss; }
+                __syncthreads();
+                if (tid < cpg) ab[(size_t)b * F + (size_t)br * a.C + g * cpg + tid] = affine(br, tid);
+            }
+        }
+        if (!IMG || br + 1 < a.nb) continue;
+        // IMG, after the last branch: every branch's pooled averages are in LDS and its sums in red[]
+        __syncthreads();
+        for (int i = tid; i < a.nb * cpg; i += 256) s_aff[(i / cpg) * 64 + (i % cpg)] = affine(i / cpg, i % cpg);
+        __syncthreads();
+        // one thread per (branch, cell, octet of channels): 8 LDS reads, normalise, scale, split, two 16-B stores
+        const int noct = cpg / 8;
+        for (int u = tid; u < a.nb * ncell * noct; u += 256) {
+            const int brr = u / (ncell * noct), r2 = u - brr * (ncell * noct);
+            const int o = r2 / ncell, cell = r2 - o * ncell;
+            f16x8 hi, lo;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const float2 af = s_aff[brr * 64 + 8 * o + j];
+                const float x = (lp[(size_t)brr * npair + (8 * o + j) * ncell + cell] * af.x + af.y) * xscale;
+                const _Float16 hh = (_Float16)x;
+                hi[j] = hh;
+                lo[j] = (_Float16)(x - (float)hh);
+            }
+            const int kk = brr * a.C + g * cpg + 8 * o;      // first feature of the octet
+            const long cg = (long)b * ncell + cell;
+            char *dst = ximg + ((size_t)(cg >> 5) * (F / 16) + (kk >> 4)) * 2048 + (((kk >> 3) & 1) * 32 + (int)(cg & 31)) * 16;
+            *(f16x8 *)dst = hi;
+            *(f16x8 *)(dst + 1024) = lo;
+        }
+    }
+}
+
 // ---- 2. hidden-layer weight W1 [Hid, F] -> split fp16 tile images (Fp = F rounded up to 16, S = Fp/16):
 //   imgH / imgL [t][s][lane = 32h + c][j < 8] = hi / lo of W1[32t + c][16s + 8h + j]   (zero padded)
 //   The images hold w * 2^sh with the power of two that brings max |W1| into [2^14, 2^15): fp16 keeps 11 bits below 2^-14 no
@@ -1016,7 +1207,7 @@ int dvq_launch_router_gate_prepare(const float *W1, int nb, int C, int Hid, void
     return (int)hipGetLastError();
 }
 
-int dvq_launch_router_gate(int nb, const void *const *h, int xt, const float *const *gn_w, const float *const *gn_b,
+int dvq_launch_router_gate(int nb, const void *const *h, int xt, int nhwc, const float *const *gn_w, const float *const *gn_b,
                            int B, int C, int hc, int wc, int groups, float eps,
                            const float *W1, const float *b1, const float *W2, const float *b2,
                            int Hid, int act, const void *w1_prep, float *gate, void *ws, hipStream_t st)
@@ -1053,6 +1244,33 @@ int dvq_launch_router_gate(int nb, const void *const *h, int xt, const float *co
             hipLaunchKernelGGL((gate_pool_kernel<IMG_, NT_, 2>), GRID, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND);  \
     } while (0)
     float *pool = (float *)((char *)ws + align256r((size_t)B * F * sizeof(float2)));
+    // channels_last branches (gate_pool_rows_kernel): the piece of E elements, 16 bytes where the group's slice and the branches'
+    // actual alignment allow, else narrower; workgroups renumbered in 8 chunks, one per XCD
+    if (nhwc) {
+        const int es = xt != 0 ? 2 : 4, cpg_r = groups > 0 ? C / groups : 8;
+        uintptr_t al = 0;
+        for (int i = 0; i < nb; ++i) al |= (uintptr_t)h[i];
+        int E = 16 / es;
+        while (E > 1 && (cpg_r % E != 0 || al % ((uintptr_t)E * es) != 0)) E >>= 1;
+        a.vec = E;
+    }
+    const int nwg_r = B * (groups > 0 ? groups : C / 8), chunk_r = (nwg_r + 7) / 8;
+#define DVQ_POOL_ROWS(IMG_, LDS, XIMG, XS, NBOUND)                                                                      \
+    do {                                                                                                                \
+        const dim3 grid_r(8 * chunk_r);                                                                                 \
+        if (xt == 0 && cached)                                                                                          \
+            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, false, 0>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
+        else if (xt == 0)                                                                                               \
+            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, true, 0>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
+        else if (xt == 1 && cached)                                                                                     \
+            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, false, 1>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
+        else if (xt == 1)                                                                                               \
+            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, true, 1>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
+        else if (cached)                                                                                                \
+            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, false, 2>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
+        else                                                                                                            \
+            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, true, 2>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
+    } while (0)
     // ws: [folded GroupNorm affine][pooled averages (direct form) OR feature images (GEMM form)][W1 images, when the caller
     //      passes none][partial logits of the GEMM form][its scale word]
     const long ncell = (long)B * hc * wc;
@@ -1082,6 +1300,9 @@ int dvq_launch_router_gate(int nb, const void *const *h, int xt, const float *co
         if ((ncell & 31) != 0)                               // the last block's unused cell columns must hold finite values
             (void)hipMemsetAsync(ximg + (size_t)(nblocks - 1) * S16 * 2048, 0, (size_t)S16 * 2048, st);
         const size_t pool_lds = (size_t)nb * cpg * hc * wc * sizeof(float);
+        if (nhwc) {
+            DVQ_POOL_ROWS(true, pool_lds, ximg, xs, nbound);
+        } else
         if (xt != 0) {                                       // 16-bit features: the same two forms, loads widened
             if (cached) DVQ_POOL_X16(true, false, dim3(B * groups), pool_lds, ximg, xs, nbound);
             else DVQ_POOL_X16(true, true, dim3(B * groups), pool_lds, ximg, xs, nbound);
@@ -1132,6 +1353,9 @@ int dvq_launch_router_gate(int nb, const void *const *h, int xt, const float *co
         hipLaunchKernelGGL(gate_finalize_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, part, HG * 4, nout, nb, b2, gate);
         return (int)hipGetLastError();
     }
+    if (nhwc) {
+        DVQ_POOL_ROWS(false, 0, nullptr, nullptr, nullptr);
+    } else
     if (xt != 0) {
         if (cached) DVQ_POOL_X16(false, false, dim3(B * (groups > 0 ? groups : C / 8)), 0, nullptr, nullptr, nullptr);
         else DVQ_POOL_X16(false, true, dim3(B * (groups > 0 ? groups : C / 8)), 0, nullptr, nullptr, nullptr);
@@ -1163,5 +1387,6 @@ int dvq_launch_router_gate(int nb, const void *const *h, int xt, const float *co
                            : (cb2 ? DVQ_GATE_LAUNCH(3, 2) : DVQ_GATE_LAUNCH(3, 1));
 #undef DVQ_GATE_LAUNCH
 #undef DVQ_POOL_X16
+#undef DVQ_POOL_ROWS
     return rc;
 }

@@ -83,6 +83,16 @@ def _can_route_conv(quantize, quant_conv, *feats):
             and _can_route(quantize, None, *feats) and quantize.assign_mode == _lib.MODE_FILTER)
 
 
+def _quant_conv(quant_conv, h):
+    """the last chain's quant_conv call.  A channels_last h (the select's output on channels_last features) stays channels_last
+    for the quantizer, which serves it in place: where the convolution backend answers an NCHW tensor for it, that (codebook_dim-
+    wide) result is converted back; where it answers channels_last, or h is NCHW, this is quant_conv(h)."""
+    out = quant_conv(h)
+    if h.is_cuda and _lib.is_channels_last(h) and out.dim() == 4 and not out.is_contiguous(memory_format=torch.channels_last):
+        out = out.contiguous(memory_format=torch.channels_last)
+    return out
+
+
 def encode_dual(router, quantize, h_fine, h_coarse, entropy=None, quant_conv=None, temp=0.0, fold=False):
     """-> (quant, emb_loss, info, grain_indices, gate) as DualGrainVQModel.encode
     (dqvae_dual_feat.py:59-68, dqvae_dual_entropy.py:124-134).
@@ -98,7 +108,11 @@ def encode_dual(router, quantize, h_fine, h_coarse, entropy=None, quant_conv=Non
     that last chain: every fused form above answers False for them, so the router gate and the select run on the 16-bit
     features (DVQ_FEATURES of include/dvq.h), quant_conv runs as the torch module in the features' dtype, and the quantizer is
     the dense 16-bit assign -- grain indices and gate as the float32 ops give them on the widened features, quant in the
-    features' dtype, emb_loss float32."""
+    features' dtype, emb_loss float32.
+    channels_last branch features (h_fine decides; an encoder run channels_last for MIOpen's convolutions): that last chain keeps
+    them channels_last end to end -- the router gate and the select read them in place (DVQ_NHWC), h_dual, the conv's output and
+    quant are channels_last, the quantizer serves the rows [B H W, C] in place.  float32 eval features that one of the fused ops
+    above serves still take it (it copies to NCHW inside and returns NCHW); only the feature router's gate reads them in place."""
     _refuse_narrow_fold(fold, h_coarse)
     fixed = isinstance(router, DualGrainFixedEntropyRouter) and entropy is not None and entropy.is_cuda
     if fold and _can_fold(quantize, quant_conv, h_coarse, h_fine):
@@ -147,7 +161,7 @@ def encode_dual(router, quantize, h_fine, h_coarse, entropy=None, quant_conv=Non
         sel = route_select_dual(gate, h_coarse, h_fine)
     h = sel["h_dual"]
     if quant_conv is not None:
-        h = quant_conv(h)
+        h = _quant_conv(quant_conv, h)
     quant, emb_loss, info = quantize(x=h, temp=temp, codebook_mask=sel["codebook_mask"])
     return quant, emb_loss, info, sel["indices"], sel["gate"]
 
@@ -180,7 +194,7 @@ def encode_triple(router, quantize, h_fine, h_median, h_coarse, quant_conv=None,
     sel = route_select_triple(gate, h_coarse, h_median, h_fine)
     h = sel["h_triple"]
     if quant_conv is not None:
-        h = quant_conv(h)
+        h = _quant_conv(quant_conv, h)
     quant, emb_loss, info = quantize(x=h, temp=temp, codebook_mask=sel["codebook_mask"])
     return quant, emb_loss, info, sel["indices"], sel["gate"]
 

@@ -53,17 +53,29 @@ def _gate_arg(gate, G):
 def _branch_features(named):
     """the branch features of a routing op, coarse -> fine, as (name, tensor) pairs: float32, or ALL float16 / ALL bfloat16 as an
     encoder under autocast produces them (DVQ_FEATURES of include/dvq.h: the select moves the 16-bit values as they are, the
-    gate widens them where it loads them) -> the contiguous tensors and the flag for the ABI's enumerated argument"""
-    hs = [_lib.require_cuda_latents(t, n) for n, t in named]
+    gate widens them where it loads them) -> the dense tensors and the flags for the ABI's enumerated argument.
+    The finest branch decides the layout: a channels_last h_fine (`_lib.is_channels_last`) is served as it lies (DVQ_NHWC), and the
+    coarser branches are brought to channels_last -- nothing to do for one that is, or whose bytes are the same in both layouts
+    (C = 1, or a 1 x 1 map), else one small copy.  Otherwise every branch is made NCHW-contiguous, as before."""
+    fine = named[-1][1]
+    nhwc = isinstance(fine, torch.Tensor) and fine.is_cuda and _lib.is_channels_last(fine)
+    hs = [_lib.require_cuda_latents(t, n, keep_channels_last=nhwc) for n, t in named]
     if len({h.dtype for h in hs}) != 1:
         raise TypeError("the branch features must have one dtype, got %s"
                         % ", ".join("%s %s" % (n, h.dtype) for (n, _), h in zip(named, hs)))
+    if nhwc:
+        cl = torch.channels_last
+        hs = [h if (h.dim() != 4 or h.is_contiguous(memory_format=cl)) else h.contiguous(memory_format=cl) for h in hs]
+        return hs, _lib.FEATURES(hs[0].dtype) | _lib.NHWC
     return hs, _lib.FEATURES(hs[0].dtype)
 
 
-def _check_out_dtype(h_out, h_fine):
+def _check_out_dtype(h_out, h_fine, flag=0):
     if h_out.dtype != h_fine.dtype:
         raise TypeError("out= holds %s, the features are %s: the select moves values, it converts nothing" % (h_out.dtype, h_fine.dtype))
+    if flag & _lib.NHWC and not (h_out.shape == h_fine.shape and h_out.is_contiguous(memory_format=torch.channels_last)):
+        raise ValueError("out= for channels_last features must be a channels_last tensor of h_fine's shape %s, got shape %s, strides %s"
+                         % (tuple(h_fine.shape), tuple(h_out.shape), tuple(h_out.stride())))
 
 
 def _route_select_dual_raw(gate, h_coarse, h_fine, out=None):
@@ -73,7 +85,9 @@ def _route_select_dual_raw(gate, h_coarse, h_fine, out=None):
     indices [B, hc, wc] int64 (0 coarse / 1 fine), codebook_mask [B, 1, 2hc, 2wc] f32 (0.25 / 1.0),
     gate permuted to [B, 2, hc, wc].
     Features: float32, or both float16 / both bfloat16 -- h_dual then has that dtype and holds exactly the selected 16-bit
-    values; indices, codebook_mask and gate are what the float32 op gives on the widened features."""
+    values; indices, codebook_mask and gate are what the float32 op gives on the widened features.
+    A channels_last h_fine (any of the three dtypes) is read in place and h_dual comes back channels_last, the same values; an out=
+    h_dual must then be channels_last too (ValueError)."""
     g, gdt = _gate_arg(gate, 2)
     (h_coarse, h_fine), flag = _branch_features([("h_coarse", h_coarse), ("h_fine", h_fine)])
     B, C, hc, wc = h_coarse.shape
@@ -82,7 +96,7 @@ def _route_select_dual_raw(gate, h_coarse, h_fine, out=None):
                          (tuple(gate.shape), tuple(h_coarse.shape), tuple(h_fine.shape)))
     if out is not None:
         h_dual, indices, cmask = out
-        _check_out_dtype(h_dual, h_fine)
+        _check_out_dtype(h_dual, h_fine, flag)
     else:
         h_dual = torch.empty_like(h_fine)
         indices = torch.empty((B, hc, wc), dtype=torch.int64, device=h_fine.device)
@@ -101,8 +115,8 @@ def _route_select_dual_entropy_raw(entropy, threshold, h_coarse, h_fine, out=Non
     (RouterDual.py:53-57 + EncoderDual.py:134-156): entropy [B, hc, wc] f32 -> the same dict as
     route_select_dual, "gate" being the router's int64 gate permuted to [B, 2, hc, wc].
     out = (h_dual, indices, codebook_mask, gate[B, hc, wc, 2] int64) to reuse buffers.
-    float16 / bfloat16 features (entropy stays float32): TWO launches, `dvq_entropy_gate_f32` and the int64-gate select on
-    16-bit features -- the fused entry point has no argument that could carry a dtype; same outputs."""
+    float16 / bfloat16 features (entropy stays float32), and channels_last features of any dtype: TWO launches,
+    `dvq_entropy_gate_f32` and the int64-gate select -- the fused entry point has no argument that could carry a flag; same outputs."""
     entropy = _lib.require_cuda_f32(entropy, "entropy")
     (h_coarse, h_fine), flag = _branch_features([("h_coarse", h_coarse), ("h_fine", h_fine)])
     B, C, hc, wc = h_coarse.shape
@@ -139,7 +153,8 @@ def _route_select_dual_entropy_raw(entropy, threshold, h_coarse, h_fine, out=Non
 def _route_select_triple_raw(gate, h_coarse, h_median, h_fine, out=None):
     """gate [B, hc, wc, 3]; h_coarse [B,C,hc,wc], h_median [B,C,2hc,2wc], h_fine [B,C,4hc,4wc]
     -> dict(h_triple, indices, codebook_mask, gate) as TripleGrainEncoder.forward (EncoderTriple.py:178-183);
-    mask values 0.0625 / 0.25 / 1.0.  Features: float32, or all three float16 / bfloat16 (see _route_select_dual_raw)."""
+    mask values 0.0625 / 0.25 / 1.0.  Features: float32, or all three float16 / bfloat16; NCHW, or a channels_last h_fine (see
+    _route_select_dual_raw)."""
     g, gdt = _gate_arg(gate, 3)
     (h_coarse, h_median, h_fine), flag = _branch_features([("h_coarse", h_coarse), ("h_median", h_median), ("h_fine", h_fine)])
     B, C, hc, wc = h_coarse.shape
@@ -149,7 +164,7 @@ def _route_select_triple_raw(gate, h_coarse, h_median, h_fine, out=None):
                          (tuple(gate.shape), tuple(h_coarse.shape), tuple(h_median.shape), tuple(h_fine.shape)))
     if out is not None:
         h_triple, indices, cmask = out
-        _check_out_dtype(h_triple, h_fine)
+        _check_out_dtype(h_triple, h_fine, flag)
     else:
         h_triple = torch.empty_like(h_fine)
         indices = torch.empty((B, hc, wc), dtype=torch.int64, device=h_fine.device)
@@ -309,11 +324,18 @@ def fused_router_gate(gate, gate_type, norms, branches, weight_prep=None):
     (statistics + per-cell averages), then the gate MLP on the averages.  weight_prep: a _GateWeightPrep kept by the
     module (None: the weight images are rebuilt inside the call).
     branches: float32, or all float16 / all bfloat16 -- widened where the pooling pass loads them, everything behind the load is
-    the float32 op: the logits (float32 either way) are those of this function on `h.float()`, bit for bit."""
+    the float32 op: the logits (float32 either way) are those of this function on `h.float()`, bit for bit.
+    A channels_last finest branch: every branch is read in place as [B, rows, cols, C] (DVQ_NHWC); the pooled averages are the NCHW
+    pass's bits, the GroupNorm sums are added in another order, so the logits agree with the NCHW form's within rounding."""
     nb = len(branches)
     hs, flag = _branch_features([("router input %d" % i, h) for i, h in enumerate(branches)])
-    # the pooling pass reads four 16-bit elements with one 8-byte load (a view that starts inside its storage is copied)
-    hs = [h.clone() if flag and h.data_ptr() % 8 != 0 else h for h in hs]
+    # the NCHW pooling pass reads four 16-bit elements with one 8-byte load, the channels_last pass 16-byte pieces: a view that starts
+    # inside its storage is copied (clone keeps the layout).  At the ABI the channels_last pass also takes narrower pieces; the copy
+    # keeps ONE summation order, hence one set of logits, for a tensor's values wherever they lie
+    if flag & _lib.NHWC:
+        hs = [h.clone() if h.data_ptr() % 16 != 0 else h for h in hs]
+    else:
+        hs = [h.clone() if flag and h.data_ptr() % 8 != 0 else h for h in hs]
     B, C, hc, wc = hs[0].shape
     for i, h in enumerate(hs):
         if tuple(h.shape) != (B, C, hc << i, wc << i):

@@ -30,6 +30,10 @@
  *     dvq_vq_assign_narrow_*_f32 below; every other entry point refuses them as before.
  *
  * Versions (dvq_version() = 100 major + minor; re-query every *_bytes function after an upgrade: buffer sizes are part of a version)
+ *   0.20.0 DVQ_NHWC: the same three entry points take channels_last branch features ([B, rows, cols, C]: a torch.channels_last tensor's
+ *          bytes) when DVQ_NHWC is OR-ed into the same enumerated argument, alone or with DVQ_FEATURES(dtype); h_out of the selects is
+ *          then channels_last too.  The dtype field is bits 8 - 11 of the argument, the layout bit 12, any bit above it DVQ_EINVAL.
+ *          Workspace and prep sizes are unchanged; without the flag nothing changed; no new entry point.
  *   0.19.0 DVQ_FEATURES(dtype): dvq_route_select_dual_f32, dvq_route_select_triple_f32 and dvq_router_gate_f32 take fp16 / bf16 branch
  *          features when DVQ_FEATURES(DVQ_DTYPE_F16 / DVQ_DTYPE_BF16) is OR-ed into their enumerated argument (gate_dtype, activation);
  *          the h_* / h_out parameters of the three are declared `const void *` / `void *` for that (binary- and source-compatible
@@ -142,6 +146,20 @@ extern "C" {
  * are DVQ_EINVAL.  Every other entry point refuses the flag by its own enumerator check. */
 #define DVQ_FEATURES(dtype) ((dtype) << 8)
 
+/* Flag, OR-ed into the same argument of the same three entry points, alone or together with DVQ_FEATURES(dtype): the branch features
+ * are CHANNELS_LAST.  Every branch (h_coarse, h_median, h_fine) and h_out of the selects is [B, rows, cols, C] row-major -- the bytes
+ * of a torch.channels_last tensor -- instead of [B, C, rows, cols]; shapes, indices, cmask (one channel: the same bytes in both
+ * layouts) and the gate logits are unchanged.  The selects move a pixel's run of C elements in pieces of 16, 8, 4 or 2 bytes, as
+ * the run's length and the actual alignment of the four tensors allow (DVQ_EUNSUPPORTED for 16 * wc * C >= 2^31); h_out holds
+ * exactly the selected values.  The router gate reads the branches in place: its pooled averages are the bits of the NCHW form,
+ * its GroupNorm sums are added in another (fixed) order, so the logits agree with the NCHW form's within rounding, not bit for bit;
+ * on 16-bit features they are the float32 DVQ_NHWC op's on the widened values, bit for bit.  Branches must be aligned to their
+ * element size (DVQ_EINVAL); dvq_router_gate_workspace_bytes / _prep_bytes do not depend on the layout.
+ * The argument as a whole: enumerator = low byte, dtype = bits 8 - 11, layout = bit 12; a bit above 12 in a non-negative value is
+ * DVQ_EINVAL.  dvq_route_select_dual_entropy_f32 has no argument that can carry a flag (run dvq_entropy_gate_f32, then the int64
+ * select); every other entry point refuses the flag by its own enumerator check. */
+#define DVQ_NHWC (1 << 12)   /* 0x1000: the bit above the four of DVQ_FEATURES(dtype) */
+
 DVQ_API int dvq_version(void);
 DVQ_API const char *dvq_last_error_string(void);
 
@@ -216,6 +234,7 @@ DVQ_API int dvq_entropy_gate_f32(const float *entropy, int64_t n, float thr, int
  * h_coarse, h_fine and h_out hold float32; with gate_dtype | DVQ_FEATURES(DVQ_DTYPE_F16 / DVQ_DTYPE_BF16) they hold 2-byte elements
  * of that type (2-byte aligned, DVQ_EINVAL otherwise; h_out = the selected elements, bit for bit; any hc, wc, C).  This and the
  * triple select move the widest pieces the row length and the alignment of h_fine / h_out / cmask allow, 16 bytes at the best.
+ * With gate_dtype | DVQ_NHWC (alone or with DVQ_FEATURES) h_coarse, h_fine and h_out are [B, rows, cols, C]: see DVQ_NHWC.
  */
 DVQ_API int dvq_route_select_dual_f32(const void *gate, int gate_dtype,
                               const void *h_coarse, const void *h_fine,
@@ -234,7 +253,8 @@ DVQ_API int dvq_route_select_dual_entropy_f32(const float *entropy, float thresh
  * Routing tail of TripleGrainEncoder.forward in eval mode (EncoderTriple.py:148-176).
  *   gate [B, hc, wc, 3]; h_coarse [B,C,hc,wc], h_median [B,C,2hc,2wc], h_fine [B,C,4hc,4wc]
  *   cmask values 0.0625 / 0.25 / 1.0
- * h_* and h_out: float32, or 2-byte elements with gate_dtype | DVQ_FEATURES(dtype), as for dvq_route_select_dual_f32.
+ * h_* and h_out: float32, or 2-byte elements with gate_dtype | DVQ_FEATURES(dtype), as for dvq_route_select_dual_f32; channels_last
+ * with gate_dtype | DVQ_NHWC.
  */
 DVQ_API int dvq_route_select_triple_f32(const void *gate, int gate_dtype,
                                 const void *h_coarse, const void *h_median,
@@ -529,7 +549,9 @@ DVQ_API int dvq_router_gate_prepare_norm_f32(int num_branches, int C, int hidden
                                      void *w1_prep, size_t w1_prep_bytes, void *stream);
 /* h_*: float32; with activation | DVQ_FEATURES(DVQ_DTYPE_F16 / DVQ_DTYPE_BF16) 2-byte elements of that type (8-byte aligned, DVQ_EINVAL
  * otherwise), widened to float32 where the pooling pass loads them: the logits are those of this op on the widened features, bit for
- * bit.  Workspace, prep and every other argument are the same (dvq_router_gate_workspace_bytes takes no dtype). */
+ * bit.  Workspace, prep and every other argument are the same (dvq_router_gate_workspace_bytes takes no dtype).
+ * With activation | DVQ_NHWC (alone or with DVQ_FEATURES) the branches are [B, rows, cols, C], aligned to their element size: see
+ * DVQ_NHWC. */
 DVQ_API int dvq_router_gate_f32(int num_branches, const void *h_coarse, const void *h_median, const void *h_fine,
                         int B, int C, int hc, int wc, int num_groups, float eps,
                         const float *gn_w_coarse, const float *gn_b_coarse,
