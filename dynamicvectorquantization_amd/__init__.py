@@ -8,5 +8,8 @@ Submodules:
   synth     deterministic synthetic inputs (numpy only)
   _lib      ctypes binding of csrc/libdvq.so -- raises if the library is missing (no CPU fallback)
 `quantize`, `router` and `encode` import `_lib`; `synth` does not, so host-only tooling can use it.
+`set_deterministic(None | True | False)`: bit-reproducible EMA statistics and codebook gradient (`_det`; None follows torch's flag).
 """
+from ._det import is_deterministic, set_deterministic  # noqa: F401  (imports nothing itself)
+
 __version__ = "0.1.0"

@@ -112,7 +112,12 @@ def build(force=False):
     return LIB_PATH
 
 
-_INT_QUERIES = ("dvq_version", "dvq_vq_assign_narrow_tile_codes")     # return an int that is a value, not a status
+_VALUE_QUERIES = ("dvq_version", "dvq_vq_assign_narrow_tile_codes")   # return an int that is a value, not a status
+# status calls whose refusals tests/golden/abi_rejections_det.json pins (tools/gen_golden_abi_rejections.py writes that table beside
+# abi_rejections.json, which holds every other status call and is kept as it was): ordinary `int` status, checked.* raises as for the rest
+_TABLED_APART = ("dvq_code_sums_det", "dvq_vq_backward_codebook_det_f32")
+# the int-returning entry points that tests/golden/abi_rejections.json does not cover: the value queries and the calls tabled apart
+_INT_QUERIES = _VALUE_QUERIES + _TABLED_APART
 
 
 def _raise_on_error(rc, func, args):
@@ -139,7 +144,7 @@ def _load():
         raw, fn = getattr(lib, name), lib[name]            # lib[name] is a function object of its own, lib.name the cached one
         raw.restype, raw.argtypes = restype, argtypes
         fn.restype, fn.argtypes = restype, argtypes
-        if restype is ctypes.c_int and name not in _INT_QUERIES:
+        if restype is ctypes.c_int and name not in _VALUE_QUERIES:
             fn.errcheck = _raise_on_error
         setattr(checked, name, fn)
     return lib, checked
@@ -236,3 +241,57 @@ def refuse_x16(t, name):
 
 def ptr(t):
     return 0 if t is None else t.data_ptr()
+
+
+from ._det import is_deterministic, set_deterministic, torch_deterministic  # noqa: E402,F401
+
+DET_MAX_K = 16384              # DVQ_DET_MAX_K: the codebook size the fixed-order sums serve
+DET_TILE, DET_RUN = 2048, 32   # DVQ_DET_TILE / DVQ_DET_RUN: the summation order's tile and run (include/dvq.h)
+
+
+def det_workspace(B, D, HW, K, device):
+    """a fresh workspace of the fixed-order sums (the caching allocator hands the same block back step after step)"""
+    nbytes = checked.dvq_code_sums_det_workspace_bytes(B, D, HW, K)
+    if nbytes == 0:
+        raise DvqError("fixed-order sums: shape B=%d D=%d HW=%d K=%d unsupported (D %% 4 == 0, K <= %d)" % (B, D, HW, K, DET_MAX_K))
+    return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def code_sums_into(z, codes, B, D, HW, K, counts, sums, deterministic=None):
+    """counts [K] / sums [K, D] (float32, overwritten) of the GPU latents z -- [B, D, HW] contiguous, HW == 1: rows [N, D]; float32,
+    float16 or bfloat16 -- under int64 `codes`: the statistics of the EMA update, k-means and the lucidrains codebooks.
+    Switch off (`set_deterministic`): `dvq_ema_accumulate_nchw_f32` / `_x16`, float atomics, exactly as before the switch existed.
+    Switch on: `dvq_code_sums_det`, one fixed summation order (a width that is no multiple of 4 runs with zero channels appended);
+    K above DET_MAX_K: bincount and index_add_ under torch's own deterministic flag -- never the atomic kernel.  That fallback
+    selects the valid tokens with a boolean mask, which synchronises with the host: it cannot be captured in a graph (the kernel
+    path can), and it holds torch's process-wide flag on while it runs (`_det.torch_deterministic`: not thread-safe)."""
+    x16 = X16.get(z.dtype, 0)
+    st = stream_ptr(z.device)
+    if not is_deterministic(deterministic):
+        with on_device(z.device):
+            if x16:
+                checked.dvq_ema_accumulate_nchw_x16(z.data_ptr(), x16, codes.data_ptr(), B, D, HW, K, counts.data_ptr(), sums.data_ptr(), st)
+            else:
+                checked.dvq_ema_accumulate_nchw_f32(z.data_ptr(), codes.data_ptr(), B, D, HW, K, counts.data_ptr(), sums.data_ptr(), st)
+        return
+    sums = sums.view(K, D)
+    if K > DET_MAX_K:
+        rows = (z.reshape(B, D) if HW == 1 else z.reshape(B, D, HW).permute(0, 2, 1).reshape(-1, D)).to(torch.float32)
+        flat = codes.reshape(-1)
+        ok = (flat >= 0) & (flat < K)
+        with torch_deterministic():
+            counts.copy_(torch.bincount(flat[ok], minlength=K))
+            sums.zero_().index_add_(0, flat[ok], rows[ok])
+        return
+    Dp, out = D, sums
+    if D % 4 != 0:                                       # (the narrow width 3: a zero channel adds nothing to the other sums)
+        Dp = (D + 3) // 4 * 4
+        zp = torch.zeros((B, Dp, HW) if HW != 1 else (B, Dp), dtype=z.dtype, device=z.device)
+        zp[:, :D] = z.reshape(B, D, HW) if HW != 1 else z.reshape(B, D)
+        z, out = zp, torch.empty((K, Dp), dtype=torch.float32, device=z.device)
+    ws = det_workspace(B, Dp, HW, K, z.device)
+    with on_device(z.device):
+        checked.dvq_code_sums_det(z.data_ptr(), x16, codes.data_ptr(), B, Dp, HW, K, counts.data_ptr(), out.data_ptr(),
+                                  ws.data_ptr(), ws.numel(), st)
+    if out is not sums:
+        sums.copy_(out[:, :D])

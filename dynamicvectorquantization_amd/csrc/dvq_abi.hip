@@ -650,6 +650,53 @@ int dvq_ema_accumulate_nchw_x16(const void *z, int dtype, const int64_t *codes, 
     return ema_accumulate_nchw(fn, dtype, z, codes, B, D, HW, K, cluster_size, vectors_sum, stream);
 }
 
+// the per-code sums in the fixed order of dvq.h (code_sums_det.hip): codebook == nullptr the statistics, else the codebook gradient
+static int code_sums_det(const char *fn, const void *z, int dtype, const float *codebook, const int64_t *codes, const float *mask,
+                         const float *g_loss, float coef_scale, int B, int D, int HW, int K, float *count, float *out, void *ws,
+                         size_t ws_bytes, void *stream)
+{
+    if (B <= 0 || D <= 0 || HW <= 0 || K <= 0) { dvq_set_error("%s: sizes must be positive", fn); return DVQ_EINVAL; }
+    if (D % 4 != 0) { dvq_set_error("%s: D=%d must be a multiple of 4", fn, D); return DVQ_EUNSUPPORTED; }
+    if (K > DVQ_DET_MAX_K) { dvq_set_error("%s: K=%d > %d (the 16-bit code fields of the sorted tile)", fn, K, DVQ_DET_MAX_K); return DVQ_EUNSUPPORTED; }
+    const size_t N = (size_t)B * HW;
+    if (int rc = check_size(fn, N, true, (size_t)D)) return rc;
+    if ((((uintptr_t)z) & (dtype != 0 ? 1 : 3)) != 0 || (((uintptr_t)out | (uintptr_t)codebook) & 15) != 0) {
+        dvq_set_error("%s: z must be aligned to its element, the [K, D] arrays to 16 bytes", fn); return DVQ_EINVAL;
+    }
+    if (int rc = check_workspace(fn, ws, ws_bytes, dvq_code_sums_det_ws_bytes((long)N, D, K), true)) return rc;
+    return hip_rc(dvq_launch_code_sums_det(z, dtype, codebook, (const long long *)codes, mask, g_loss, coef_scale, D, HW, (long)N, K, count,
+                                           out, ws, (hipStream_t)stream), fn);
+}
+
+size_t dvq_code_sums_det_workspace_bytes(int B, int D, int HW, int K)
+{
+    if (B <= 0 || D <= 0 || HW <= 0 || K <= 0 || D % 4 != 0 || K > DVQ_DET_MAX_K || (size_t)B * HW >= ((size_t)1 << 31)) return 0;
+    return dvq_code_sums_det_ws_bytes((long)B * HW, D, K);
+}
+
+int dvq_code_sums_det(const void *z, int dtype, const int64_t *codes, int B, int D, int HW, int K, float *cluster_size,
+                      float *vectors_sum, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_code_sums_det";
+    if (!z || !codes || !cluster_size || !vectors_sum) return null_pointer(fn);
+    if (dtype != 0) { if (int rc = check_x16_dtype(fn, dtype)) return rc; }
+    return code_sums_det(fn, z, dtype, nullptr, codes, nullptr, nullptr, 0.0f, B, D, HW, K, cluster_size, vectors_sum, ws, ws_bytes, stream);
+}
+
+size_t dvq_vq_backward_codebook_det_workspace_bytes(int B, int D, int HW, int K)
+{
+    return dvq_code_sums_det_workspace_bytes(B, D, HW, K);
+}
+
+int dvq_vq_backward_codebook_det_f32(const float *z, const float *codebook, const int64_t *codes, const float *mask,
+                                     const float *g_loss, float coef_scale, int B, int D, int HW, int K, float *g_weight,
+                                     void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_vq_backward_codebook_det_f32";
+    if (!z || !codebook || !codes || !g_loss || !g_weight) return null_pointer(fn);
+    return code_sums_det(fn, z, 0, codebook, codes, mask, g_loss, coef_scale, B, D, HW, K, nullptr, g_weight, ws, ws_bytes, stream);
+}
+
 int dvq_code_stats_f32(const int64_t *codes, int64_t N, int K, int64_t *counts, int64_t *n_used, float *perplexity, float *onehot,
                        void *stream)
 {

@@ -67,6 +67,11 @@ int dvq_launch_codebook_grad_rows(const float *z, const float *E, const long lon
 int dvq_launch_ema_zero(float *a, size_t na, float *b, size_t nb, hipStream_t st);
 int dvq_launch_ema_accumulate_sorted_rows(const float *z, const long long *codes, int D, long N, int K, float *cluster_size,
                                           float *vectors_sum, hipStream_t st);   // -1: not its shape, nothing launched
+// the same sums in one fixed summation order (code_sums_det.hip; include/dvq.h: dvq_code_sums_det): E == nullptr the statistics, else
+// the codebook gradient (float32 z); no float atomics; ws of dvq_code_sums_det_ws_bytes(N, D, K) bytes; D % 4 == 0, K <= 16384, N < 2^31
+size_t dvq_code_sums_det_ws_bytes(long N, int D, int K);
+int dvq_launch_code_sums_det(const void *z, int xt, const float *E, const long long *codes, const float *mask, const float *g_loss,
+                             float coef_scale, int D, int HW, long N, int K, float *count, float *out, void *ws, hipStream_t st);
 int dvq_launch_embed_gather(const float *E, int K, int D, const long long *idx, long n, float *out,
                             hipStream_t st);
 

@@ -256,9 +256,7 @@ class _Codebook(InvalidatesPrepared, nn.Module):
         else:
             flat = torch.empty(K * D + K, dtype=torch.float32, device=dev)
             sums, counts = flat[:K * D].view(K, D), flat[K * D:]
-            with _lib.on_device(dev):
-                checked.dvq_ema_accumulate_nchw_f32(toks.data_ptr(), codes.data_ptr(), N, D, 1, K, counts.data_ptr(),
-                                                    sums.data_ptr(), _lib.stream_ptr(dev))
+            _lib.code_sums_into(toks, codes, N, D, 1, K, counts, sums)
         if _ddp():
             dist.all_reduce(flat, op=dist.ReduceOp.SUM)            # the step's statistics: one collective
         thr = float(self.threshold_ema_dead_code)

@@ -816,14 +816,22 @@ class _VQStraightThrough(torch.autograd.Function):
                     checked.dvq_vq_backward_nchw_f32(
                         z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), _lib.ptr(gq), gl.data_ptr(),
                         float(ctx.coef_z * scale), n_tok // HW, D, HW, snap.shape[0], gz.data_ptr(), _lib.stream_ptr(z.device))
-        if need_w and g_loss is not None and z.is_cuda and z.dtype == torch.float32 and dense and snap.shape[0] <= 8192:
+        det = _lib.is_deterministic()                     # `set_deterministic`: the codebook gradient summed in one fixed order
+        if (need_w and g_loss is not None and z.is_cuda and z.dtype == torch.float32 and dense
+                and (snap.shape[0] <= _lib.DET_MAX_K and D % 4 == 0 if det else snap.shape[0] <= 8192)):
             gw = torch.zeros(ctx.wshape, dtype=z.dtype, device=z.device)
             gl = g_loss.reshape(1).to(torch.float32).contiguous()
             m = None if mask is None else _lib.require_cuda_f32(mask, "codebook_mask")
             with _lib.on_device(z.device):
-                checked.dvq_vq_backward_codebook_nchw_f32(
-                    z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), gl.data_ptr(), float(ctx.coef_e * scale),
-                    n_tok // HW, D, HW, snap.shape[0], gw.data_ptr(), _lib.stream_ptr(z.device))
+                if det:
+                    ws = _lib.det_workspace(n_tok // HW, D, HW, snap.shape[0], z.device)
+                    checked.dvq_vq_backward_codebook_det_f32(
+                        z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), gl.data_ptr(), float(ctx.coef_e * scale),
+                        n_tok // HW, D, HW, snap.shape[0], gw.data_ptr(), ws.data_ptr(), ws.numel(), _lib.stream_ptr(z.device))
+                else:
+                    checked.dvq_vq_backward_codebook_nchw_f32(
+                        z.data_ptr(), snap.data_ptr(), codes.data_ptr(), _lib.ptr(m), gl.data_ptr(), float(ctx.coef_e * scale),
+                        n_tok // HW, D, HW, snap.shape[0], gw.data_ptr(), _lib.stream_ptr(z.device))
             need_w = False                                # done
         diff = None
         if (need_z and gz is None) or (need_w and g_loss is not None):
@@ -839,7 +847,11 @@ class _VQStraightThrough(torch.autograd.Function):
             gw = torch.zeros(ctx.wshape, dtype=snap.dtype, device=z.device)
             if g_loss is not None and need_w:
                 ge = (-(g_loss * (ctx.coef_e * scale)) * diff).reshape(B, D, -1).permute(0, 2, 1).reshape(-1, D)
-                gw.index_add_(0, codes.reshape(-1), ge)
+                if det:                                   # where the kernel does not apply: torch's order-stable index_add_, or its error
+                    with _lib.torch_deterministic():
+                        gw.index_add_(0, codes.reshape(-1), ge)
+                else:
+                    gw.index_add_(0, codes.reshape(-1), ge)
         return gz, gw, None, None, None, None, None, None
 
 
@@ -972,13 +984,12 @@ class VQEmbedding(InvalidatesPrepared, nn.Embedding):
         if lat is not None:
             z, B, HW = lat
             codes = idxs.reshape(B, HW).contiguous()
-            x16 = _lib.X16.get(z.dtype, 0)               # 16-bit latents: summed in float32 from the exact widened values
-            out = (cluster_size.data_ptr(), vsum.data_ptr(), _lib.stream_ptr(z.device))
-            with _lib.on_device(z.device):
-                if x16:
-                    checked.dvq_ema_accumulate_nchw_x16(z.data_ptr(), x16, codes.data_ptr(), B, embed_dim, HW, n_embed, *out)
-                else:
-                    checked.dvq_ema_accumulate_nchw_f32(z.data_ptr(), codes.data_ptr(), B, embed_dim, HW, n_embed, *out)
+            # 16-bit latents: summed in float32 from the exact widened values.  `set_deterministic` on: the fixed-order kernels
+            _lib.code_sums_into(z, codes, B, embed_dim, HW, n_embed, cluster_size, vsum)
+        elif _lib.is_deterministic():                     # CPU tensors: torch's own order-stable scatter, or its error
+            with _lib.torch_deterministic():
+                cluster_size.copy_(torch.bincount(idxs, minlength=n_embed))
+                vsum.zero_().index_add_(0, idxs, vectors.to(torch.float32))
         else:
             cluster_size.copy_(torch.bincount(idxs, minlength=n_embed))
             vsum.zero_().index_add_(0, idxs, vectors.to(torch.float32))
@@ -1374,6 +1385,31 @@ def _noop(*args, **kwargs):
     pass
 
 
+@torch.no_grad()
+def code_sums(z, codes, K, deterministic=None):
+    """(cluster_size [K], vectors_sum [K, D]) float32: per code, how many tokens of z chose it and the sum of their vectors -- the
+    statistics of the EMA codebook update.  z: GPU latents [B, D, *spatial] (NCHW; a channels_last tensor is read as the rows it is)
+    or token rows [N, D]; float32, float16 or bfloat16 (summed in float32 from the widened values); codes: int64, one per token,
+    values outside [0, K) ignored.  deterministic: None follows `set_deterministic` (and through it torch's flag); True: the
+    fixed summation order of include/dvq.h (`dvq_code_sums_det`), bit-reproducible and independent of layout and B x HW
+    factorisation; False: the float-atomic kernels (`dvq_ema_accumulate_nchw_f32` / `_x16`)."""
+    z = _lib.require_cuda_latents(z, "z", keep_channels_last=True)
+    if z.dim() < 2:
+        raise ValueError("z must be [B, D, *spatial] or [N, D]")
+    if _lib.is_channels_last(z):
+        z = _lib.channels_last_rows(z)
+    B, D = z.shape[0], z.shape[1]
+    HW = z[0, 0].numel() if z.dim() > 2 else 1
+    if codes.dtype != torch.int64 or codes.device != z.device or codes.numel() != B * HW:
+        raise ValueError("codes must be int64 on z's device, one per token (%d), got %s %s" % (B * HW, codes.dtype, tuple(codes.shape)))
+    if z.numel() == 0 or K < 1:
+        raise ValueError("code_sums needs at least one token and one code")
+    counts = torch.empty(K, dtype=torch.float32, device=z.device)
+    sums = torch.empty((K, D), dtype=torch.float32, device=z.device)
+    _lib.code_sums_into(z, codes.contiguous(), B, D, HW, K, counts, sums, deterministic)
+    return counts, sums
+
+
 def _kmeans_lloyd(flat, means, iters, all_reduce_fn=_noop, cosine=False):
     """The Lloyd loop of common_utils.kmeans:128-154 on the kernels: flat [N, D] f32 GPU tokens, means [1, K, D] the initial rows
     -> (means [1, K, D], bins [1, K] int64 of the last iteration).  Per iteration the exact-mode assign, codes only (cosine: the
@@ -1392,10 +1428,7 @@ def _kmeans_lloyd(flat, means, iters, all_reduce_fn=_noop, cosine=False):
             buckets = score_assign(flat, cb, prep, _lib.METRIC_DOT)
         else:
             _, buckets, _ = vq_assign(flat, cb, prep, want_zq=False, want_loss=False, mode=_lib.MODE_EXACT)
-        with _lib.on_device(dev):
-            checked.dvq_ema_accumulate_nchw_f32(
-                flat.data_ptr(), buckets.data_ptr(), N, D, 1, K, counts.data_ptr(), sums.data_ptr(),
-                _lib.stream_ptr(dev))
+        _lib.code_sums_into(flat, buckets, N, D, 1, K, counts, sums)
         bins = counts.round().to(torch.int64).unsqueeze(0)        # [1, K]
         all_reduce_fn(bins)
         zero_mask = bins == 0
@@ -2037,10 +2070,9 @@ class EMAVectorQuantizer(InvalidatesPrepared, nn.Module):
         stats = torch.empty(K * D + K, dtype=torch.float32, device=z.device)
         vsum, csize = stats[:K * D], stats[K * D:]
         cs_new = torch.empty_like(emb.cluster_size.data)          # the update kernel's no-alias rule: every workgroup sums the OLD counts
+        _lib.code_sums_into(z, codes, B, D, HW, K, csize, vsum)
         with _lib.on_device(z.device):
             st = _lib.stream_ptr(z.device)
-            checked.dvq_ema_accumulate_nchw_f32(z.data_ptr(), codes.data_ptr(), B, D, HW, K, csize.data_ptr(),
-                                                vsum.data_ptr(), st)
             checked.dvq_ema_update_f32(
                 vsum.data_ptr(), csize.data_ptr(), float(emb.decay), float(emb.eps), K, D, emb.cluster_size.data_ptr(),
                 cs_new.data_ptr(), emb.embed_avg.data_ptr(), emb.weight.data_ptr(), 0, 0, 0, B, HW, 0, st)

@@ -34,6 +34,9 @@
  *          bytes) when DVQ_NHWC is OR-ed into the same enumerated argument, alone or with DVQ_FEATURES(dtype); h_out of the selects is
  *          then channels_last too.  The dtype field is bits 8 - 11 of the argument, the layout bit 12, any bit above it DVQ_EINVAL.
  *          Workspace and prep sizes are unchanged; without the flag nothing changed; no new entry point.
+ *          Added later under the same version number (detect them by their symbols): dvq_code_sums_det, dvq_vq_backward_codebook_det_f32
+ *          and their *_workspace_bytes queries -- the per-code sums of the training step (EMA statistics, codebook gradient) in one
+ *          documented, fixed summation order, without float atomics.  Nothing else changed.
  *   0.19.0 DVQ_FEATURES(dtype): dvq_route_select_dual_f32, dvq_route_select_triple_f32 and dvq_router_gate_f32 take fp16 / bf16 branch
  *          features when DVQ_FEATURES(DVQ_DTYPE_F16 / DVQ_DTYPE_BF16) is OR-ed into their enumerated argument (gate_dtype, activation);
  *          the h_* / h_out parameters of the three are declared `const void *` / `void *` for that (binary- and source-compatible
@@ -1042,6 +1045,43 @@ DVQ_API int dvq_vq_backward_nchw_x16(const void *z, int dtype, const float *code
                                      void *g_z, void *stream);
 DVQ_API int dvq_ema_accumulate_nchw_x16(const void *z, int dtype, const int64_t *codes, int B, int D, int HW, int K,
                                         float *cluster_size, float *vectors_sum, void *stream);
+
+/*
+ * BIT-REPRODUCIBLE per-code sums: the statistics of dvq_ema_accumulate_nchw_f32 / _x16 and the gradient of
+ * dvq_vq_backward_codebook_nchw_f32 in ONE FIXED summation order -- no float atomic and no rank taken from a returning atomic on the
+ * path, so two calls on equal inputs give equal bits, whatever the grid, the occupancy or the timing.
+ * Tokens are numbered n = b * HW + hw (HW == 1: n = the row of a row-major z [N, D], B = N); v[n][c] is the token's fp32 value at
+ * channel c -- float32(z) for the statistics (exact for DVQ_DTYPE_F16 / DVQ_DTYPE_BF16), fl(fl(z - codebook[j][c]) * mask[n]) with
+ * j = codes[n] for the gradient (mask == NULL: 1).  Codes outside [0, K) are ignored.  For every code j and channel c:
+ *   1. the tokens are cut into tiles of DVQ_DET_TILE = 2048 consecutive n (tile i holds n in [2048 i, 2048 i + 2048));
+ *   2. inside a tile the members of j (tokens with codes[n] == j) are taken in ascending n and cut into runs of DVQ_DET_RUN = 32 members
+ *      (the last run of a tile may be shorter);
+ *   3. a run's sum is r = v[first member]; r = fl(r + v[next member]) ... in that order;
+ *   4. the tile's partial is p = r_0; p = fl(p + r_1); ... over its runs in order;
+ *   5. S[j][c] = p of the first tile that has a member of j; S = fl(S + p of the next such tile) ... in ascending tile index.
+ *      A code without members has S = +0.0f.
+ * The order is a function of (v, codes, N, D, K) only: not of the B x HW factorisation, the layout (NCHW or row-major), the storage
+ * type beyond the widening, or the alignment of z (which only select how values are loaded).
+ *   dvq_code_sums_det                  cluster_size[j] = the member count (exact below 2^24), vectors_sum[j][c] = S[j][c]; both overwritten.
+ *                                      dtype 0 (float32), DVQ_DTYPE_F16, DVQ_DTYPE_BF16; z [B, D, HW] of that type.
+ *   dvq_vq_backward_codebook_det_f32   g_weight[j][c] = fl(k * S[j][c]) with k = -fl(g_loss[0] * coef_scale), WRITTEN (not accumulated) for
+ *                                      rows 0 .. K - 1 (a row without members: k * 0); arguments as dvq_vq_backward_codebook_nchw_f32.
+ * D % 4 == 0 and K <= DVQ_DET_MAX_K = 16384 (DVQ_EUNSUPPORTED otherwise; the message names the limit), B * HW < 2^31.  ws: caller-provided,
+ * 256-byte aligned, at least the *_workspace_bytes of the same (B, D, HW, K) -- (B HW / 2048 tiles) x (min(K, 2048) rows of D floats, plus
+ * 2 K + 12 KiB of tables); contents need not be kept or cleared between calls.  The query returns 0 for a shape the call refuses.
+ * Three launches on `stream`, no host synchronisation, capturable in a graph.  DVQ_EINVAL: null pointer (mask is nullable), dtype not
+ * 0 / 1 / 2, a size <= 0, z not aligned to its element, vectors_sum / g_weight / codebook not 16-byte aligned, ws not 256-byte aligned.
+ * DVQ_EWORKSPACE: ws null or too small.  No atomics: a partial row leaves as 4-byte vector stores, sixteen
+ * lanes writing 64 contiguous bytes; the results as 16-byte stores.
+ */
+enum { DVQ_DET_TILE = 2048, DVQ_DET_RUN = 32, DVQ_DET_MAX_K = 16384 };
+DVQ_API size_t dvq_code_sums_det_workspace_bytes(int B, int D, int HW, int K);
+DVQ_API int dvq_code_sums_det(const void *z, int dtype, const int64_t *codes, int B, int D, int HW, int K, float *cluster_size,
+                              float *vectors_sum, void *ws, size_t ws_bytes, void *stream);
+DVQ_API size_t dvq_vq_backward_codebook_det_workspace_bytes(int B, int D, int HW, int K);
+DVQ_API int dvq_vq_backward_codebook_det_f32(const float *z, const float *codebook, const int64_t *codes, const float *mask,
+                                             const float *g_loss, float coef_scale, int B, int D, int HW, int K, float *g_weight,
+                                             void *ws, size_t ws_bytes, void *stream);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,9 @@
       calls the entry points of include/dvq.h with arguments that argument validation refuses and records, per call,
       {fn, args, rc, message}: the status code and the bytes of dvq_last_error_string().  Run it against a build of the commit
       whose behaviour is to be pinned (DVQ_LIBRARY=<path> selects another build than csrc/libdvq.so).
+      The entry points of DET_FNS (dvq_code_sums_det, dvq_vq_backward_codebook_det_f32: ordinary status calls) have a table of their
+      own, tests/golden/abi_rejections_det.json (--det-o), written in the same run: the first table is kept byte for byte as it was
+      when they were added, and a later change that may touch it can merge the two.
   tools/gen_golden_abi_rejections.py --replay table.json
       makes the table's calls again and prints [[rc, message], ...] as JSON (tests/test_abi_rejections.py compares).
 
@@ -29,6 +32,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "dvq.h")
 LIB = os.environ.get("DVQ_LIBRARY") or os.path.join(ROOT, "dynamicvectorquantization_amd", "csrc", "libdvq.so")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_rejections.json")
+GOLDEN_DET = os.path.join(ROOT, "tests", "golden", "abi_rejections_det.json")
+DET_FNS = ("dvq_code_sums_det", "dvq_vq_backward_codebook_det_f32")     # their rows go to GOLDEN_DET
 _CTYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 REFUSALS = (-1, -2, -3)          # DVQ_EINVAL, DVQ_EUNSUPPORTED, DVQ_EWORKSPACE
@@ -224,6 +229,13 @@ ladder("dvq_router_gate_f32", d(num_branches=2, gate=0, h_median=P, wc=0, activa
                                 ws=0, ws_bytes=BIG), d(gate=P), d(h_median=0), d(wc=1), d(activation=2), d(b1=P), d(num_groups=3), d(gn_b_coarse=P),
        d(C=24, num_groups=12), d(num_groups=3), d(hidden=64), d(ws=16))
 
+# the per-code sums in a fixed order: a table of their own (GOLDEN_DET)
+ladder("dvq_code_sums_det", d(z=0, dtype=3, B=0, D=6, K=20000, HW=1 << 12, vectors_sum=8, ws=16, ws_bytes=0), d(z=1), d(dtype=2), d(B=1 << 20),
+       d(D=4), d(K=64), ONE, d(z=2), d(vectors_sum=P), d(ws_bytes=BIG), d(ws=0))
+ladder("dvq_code_sums_det", d(dtype=0, z=2, D=4, K=16385), d(K=16384), d(z=4, D=0), d(D=4, HW=0), d(HW=1, K=0), d(K=1, cluster_size=0))
+ladder("dvq_vq_backward_codebook_det_f32", d(g_loss=0, B=0, D=6, K=20000, codebook=8, ws=16, ws_bytes=0), d(g_loss=P), d(B=1), d(D=8), d(K=8193),
+       d(codebook=P), d(ws_bytes=BIG), d(ws=0), d(ws=P, g_weight=0))
+
 
 def rows(protos):
     out = []
@@ -247,6 +259,7 @@ def _num(v):
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("-o", default=GOLDEN)
+    ap.add_argument("--det-o", default=GOLDEN_DET)
     ap.add_argument("--replay", metavar="TABLE")
     a = ap.parse_args()
     os.environ["HIP_VISIBLE_DEVICES"] = os.environ["ROCR_VISIBLE_DEVICES"] = ""      # before the library and the HIP runtime load
@@ -266,9 +279,10 @@ def main():
             table.append(dict(r, rc=rc, message=msg))
     missing = set(protos) - {r["fn"] for r in table}
     assert not missing, "entry points without a row: %s" % sorted(missing)
-    with open(a.o, "w") as f:                                 # a row per line
-        f.write("[\n" + ",\n".join(json.dumps(r) for r in table) + "\n]\n")
-    print("%d refusals of %d entry points -> %s" % (len(table), len({r["fn"] for r in table}), a.o))
+    for path, part in ((a.o, [r for r in table if r["fn"] not in DET_FNS]), (a.det_o, [r for r in table if r["fn"] in DET_FNS])):
+        with open(path, "w") as f:                            # a row per line
+            f.write("[\n" + ",\n".join(json.dumps(r) for r in part) + "\n]\n")
+        print("%d refusals of %d entry points -> %s" % (len(part), len({r["fn"] for r in part}), path))
 
 
 if __name__ == "__main__":
