@@ -16,6 +16,40 @@ def codes_small():
                 fine_position_sos_code=66, max_coarse_postion_idx=15, hw1=4, fine_hw=8, V_content=40, V_coarse=19, V_fine=67)
 
 
+def codes_for(V, hw1, layout="top"):
+    """special codes for one vocabulary size V (all three step kinds share it) and a coarse grid hw1 x hw1.
+    "top":    pad, eos, sos = V - 3, V - 2, V - 1 and max_coarse_postion_idx = V - 3, as the real models (positions below,
+              special codes above); with V >= 4 * hw1 * hw1 + 3 no code collides with a coarse or fine position.
+    "spread": one special code at index 0, one at 31 or 32 (the edge of a 32-bit word of the history bitmap) and one at
+              V - 1; the coarse position range is banned from 3 V / 4 on, so the coarse eos (V - 1) is restored out of it.
+    Below V = 4 there is no room for three codes: some coincide, chosen so that every unflagged row keeps a finite entry.
+    Every code meets the range rules of dvq_sample_head_f32 (pad in [0, V), ban ranges in [0, V], the others in [0, V))."""
+    V, hw1 = int(V), int(hw1)
+    if V < 2:
+        raise ValueError("V=%d: a vocabulary needs a pad code and one more entry" % V)
+    if layout not in ("top", "spread"):
+        raise ValueError("layout %r" % (layout,))
+    if V == 2:                                           # index 0 stays finite: position eos = 0, content bans 1 only
+        coarse = fine = (1, 0, 1)
+        content, max_idx = (1, 1, 1), 1
+    elif V == 3:
+        coarse = fine = content = (1, 2, 1)
+        max_idx = 1
+    elif layout == "top":
+        coarse = fine = content = (V - 3, V - 2, V - 1)
+        max_idx = V - 3
+    else:
+        m31, m32 = (31, 32) if V > 33 else (V // 2, V // 2)
+        coarse = (0, V - 1, m31)
+        fine = (m32, V - 1, 0)
+        content = (0, V - 1, m31)                        # content bans from eos on: eos stays at the top
+        max_idx = max(3 * V // 4, 2)
+    return dict(content_pad_code=content[0], content_eos_code=content[1], content_sos_code=content[2],
+                coarse_position_pad_code=coarse[0], coarse_position_eos_code=coarse[1], coarse_position_sos_code=coarse[2],
+                fine_position_pad_code=fine[0], fine_position_eos_code=fine[1], fine_position_sos_code=fine[2],
+                max_coarse_postion_idx=max_idx, hw1=hw1, fine_hw=2 * hw1, V_content=V, V_coarse=V, V_fine=V)
+
+
 def mask(logits, kind, variant, c, history, flag):
     """the avoid_* helper of the step kind (logits already divided by the temperature)"""
     B, V = logits.shape
@@ -75,6 +109,39 @@ def top_p(probs, p):
     return kept / kept.sum(-1, keepdim=True)
 
 
+def softmax64(masked32):
+    """float64 softmax of float32 masked logits.  The row maximum is subtracted in float32, as the kernel does: that
+    difference is one IEEE operation and the same on every device, so exp and the normalisation are the only things a
+    float32 softmax can get wrong against this.  Returns a float64 tensor."""
+    assert masked32.dtype == torch.float32
+    d = masked32 - masked32.max(dim=-1, keepdim=True).values
+    e = torch.exp(d.double())
+    return e / e.sum(-1, keepdim=True)
+
+
+def top_p_exact(p32, top_p):
+    """top_p_logits on float32 probabilities with float64 masses.  Order: value descending, index ascending (a stable sort).
+    An element is kept iff the mass strictly before it is < float32(top_p); the first element is always kept.
+    Returns (keep bool [B, V], float64 [B, V] kept values renormalised, margin float64 [B]): margin is the per-row minimum of
+    |mass before j - top_p| over the elements with p > 0 (whether an element of probability 0 counts as kept changes neither
+    the set of non-zero outputs nor their sum).  A row whose margin is above the error of the masses being compared has one
+    correct kept set."""
+    p = np.ascontiguousarray(p32.detach().cpu().numpy())
+    assert p.dtype == np.float32 and p.ndim == 2
+    t = float(np.float32(top_p))
+    p64 = p.astype(np.float64)
+    order = np.argsort(-p64, axis=-1, kind="stable")
+    sp = np.take_along_axis(p64, order, -1)
+    before = np.concatenate([np.zeros_like(sp[:, :1]), np.cumsum(sp, -1)[:, :-1]], -1)
+    keep_sorted = before < t
+    keep_sorted[:, 0] = True
+    keep = np.zeros_like(keep_sorted)
+    np.put_along_axis(keep, order, keep_sorted, -1)
+    kept = np.where(keep, p64, 0.0)
+    margin = np.where(sp > 0, np.abs(before - t), np.inf).min(-1)
+    return torch.from_numpy(keep), torch.from_numpy(kept / kept.sum(-1, keepdims=True)), torch.from_numpy(margin)
+
+
 def head(logits_last, kind, variant, c, history, flag, temperature, k, p, sample, generator):
     x = logits_last / temperature
     x = mask(x, kind, variant, c, history, flag)
@@ -88,18 +155,29 @@ def head(logits_last, kind, variant, c, history, flag, temperature, k, p, sample
     return torch.topk(probs, 1, dim=-1).indices
 
 
-def transfer(c, coarse_position, remain, order, sos_mode):
-    """sos_mode: "const" (fine_position_sos_code), "copy" (coarse_position[:, 0]) or None"""
-    hw1, fine_hw = c["hw1"], c["fine_hw"]
+def transfer_selected(c, coarse_position, remain):
+    """bool [B, hw1 * hw1]: the coarse cells whose fine positions the transfer emits (sampled before the row's first coarse
+    EOS, or with `remain` the others).  Column 0 is the sos; a row of that column alone has sampled nothing."""
+    hw1 = c["hw1"]
     B, Lc = coarse_position.shape
     dev = coarse_position.device
     cp = coarse_position[:, 1:]
     is_eos = cp == c["coarse_position_eos_code"]
-    first = torch.where(is_eos.any(1), is_eos.float().argmax(1), torch.full((B,), Lc - 1, device=dev))
+    first = torch.full((B,), Lc - 1, device=dev)
+    if Lc > 1:                                           # argmax over an empty dimension raises
+        first = torch.where(is_eos.any(1), is_eos.float().argmax(1), first)
     valid = (torch.arange(Lc - 1, device=dev)[None, :] < first[:, None]) & (cp >= 0) & (cp < hw1 * hw1)
     mark = torch.zeros((B, hw1 * hw1 + 1), dtype=torch.bool, device=dev)
     mark.scatter_(1, torch.where(valid, cp, torch.full_like(cp, hw1 * hw1)), True)
-    sel = mark[:, :-1] != bool(remain)
+    return mark[:, :-1] != bool(remain)
+
+
+def transfer(c, coarse_position, remain, order, sos_mode):
+    """sos_mode: "const" (fine_position_sos_code), "copy" (coarse_position[:, 0]) or None"""
+    hw1, fine_hw = c["hw1"], c["fine_hw"]
+    B = coarse_position.shape[0]
+    dev = coarse_position.device
+    sel = transfer_selected(c, coarse_position, remain)
     seq = torch.arange(fine_hw * fine_hw, device=dev).view(fine_hw, fine_hw)
     if order == "region-first":
         seq = seq.view(hw1, 2, hw1, 2).permute(0, 2, 1, 3).reshape(hw1 * hw1, 4)
