@@ -10,7 +10,9 @@
 //                        branches): (mean, rstd) per (image, group) and the raw per-cell averages
 //                        pooled[b][k = branch * C + c][cell] (the average of normalised pixels is the normalised
 //                        average, so the GroupNorm affine is applied to the averages later).  Streaming, high
-//                        occupancy: bound by the feature read.
+//                        occupancy: bound by the feature read.  gate_pool_rows_kernel is the same pass on channels_last
+//                        branches: one skeleton (gate_pool_xscale, gate_pool_finish), two walks over the features; the
+//                        host picks the instantiation in gate_pool_launch.
 //   2. w1_split_kernel   hidden-layer weight -> 32-row MFMA tile images, split w = hi + lo with
 //                        hi = fp16(w), lo = fp16(w - hi) (22 significand bits between them); done once per
 //                        weight version when the caller keeps the images (dvq_router_gate_prepare_f32).
@@ -90,20 +92,13 @@ template <int XT, bool NT> __device__ __forceinline__ float gate_ld1(const typen
 #define DVQ_POOL_WPE 8           // workgroups per CU the pooling pass is compiled for (a streaming pass lives on occupancy)
 #endif
 #define DVQ_GATE_NORM_MAGIC 0x44563531      // tail of the weight prep: [magic][max |gn_w|, max |gn_b| per branch] (dvq_router_gate_prepare_norm_f32)
-template <bool IMG, bool NT, int XT = 0>
-__global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArgs a, float2 *__restrict__ ab,
-                                                        float *__restrict__ pool, char *__restrict__ ximg,
-                                                        float *__restrict__ xs, const float *__restrict__ nbound)
+// The skeleton of the pooling pass, shared by gate_pool_kernel and gate_pool_rows_kernel (which differ in their walk over the
+// features only): gate_pool_xscale before the branches, gate_pool_finish after each.  The LDS arrays are the kernels'.
+// IMG: the power-of-two scale of the operand images (returned; 1 otherwise), its inverse to xs[0] by the `first` workgroup.
+template <bool IMG>
+__device__ __forceinline__ float gate_pool_xscale(const DvqGateArgs &a, int cpg, int F, const float *__restrict__ nbound,
+                                                  float (&s_bound)[4], float *__restrict__ xs, bool first)
 {
-    const int G = a.groups > 0 ? a.groups : a.C / 8;
-    const int cpg = a.C / G;
-    const int b = blockIdx.x / G, g = blockIdx.x - b * G;
-    const int ncell = a.hc * a.wc, F = a.nb * a.C;
-    const int npair = cpg * ncell;
-    __shared__ double red[3][2][4];                          // [branch (IMG; else 0)][sum | sum of squares][wave]
-    __shared__ float s_bound[4];
-    __shared__ float2 s_aff[3 * 64];                         // IMG: (scale, shift) of the group's channels, per branch
-    extern __shared__ float lp[];                            // IMG: [branch][cpg][ncell] pooled averages
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float xscale = 1.0f;
     if (IMG) {
@@ -118,16 +113,16 @@ __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArg
                 bound = fmaxf(bound, nbound[1 + 2 * br] * sqrtf(n) * 1.0001f + nbound[2 + 2 * br]);
             }
         } else {
-        for (int k = tid; k < F; k += 256) {
-            const int br = k / a.C, ch = k - br * a.C;
-            const float n = (float)cpg * (float)(a.hc * a.scale[br]) * (float)(a.wc * a.scale[br]);
-            bound = fmaxf(bound, fabsf(a.gn_w[br][ch]) * sqrtf(n) * 1.0001f + fabsf(a.gn_b[br][ch]));
-        }
+            for (int k = tid; k < F; k += 256) {
+                const int br = k / a.C, ch = k - br * a.C;
+                const float n = (float)cpg * (float)(a.hc * a.scale[br]) * (float)(a.wc * a.scale[br]);
+                bound = fmaxf(bound, fabsf(a.gn_w[br][ch]) * sqrtf(n) * 1.0001f + fabsf(a.gn_b[br][ch]));
+            }
 #pragma unroll
-        for (int off = 32; off > 0; off >>= 1) bound = fmaxf(bound, __shfl_xor(bound, off));
-        if (lane == 0) s_bound[wave] = bound;
-        __syncthreads();
-        bound = fmaxf(fmaxf(s_bound[0], s_bound[1]), fmaxf(s_bound[2], s_bound[3]));
+            for (int off = 32; off > 0; off >>= 1) bound = fmaxf(bound, __shfl_xor(bound, off));
+            if (lane == 0) s_bound[wave] = bound;
+            __syncthreads();
+            bound = fmaxf(fmaxf(s_bound[0], s_bound[1]), fmaxf(s_bound[2], s_bound[3]));
         }
         float inv = 1.0f;
         if (bound > 0.0f && bound < __builtin_inff()) {
@@ -137,8 +132,84 @@ __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArg
             xscale = ldexpf(1.0f, sh);                       // ~sqrt(n) above typical values, whose lo halves would otherwise be fp16
             inv = ldexpf(1.0f, -sh);                         // subnormals (an absolute 2^-25 instead of 22 significand bits)
         }
-        if (blockIdx.x == 0 && tid == 0) xs[0] = inv;
+        if (first && tid == 0) xs[0] = inv;
     }
+    return xscale;
+}
+// The tail of branch br of workgroup (image b, group g): its GroupNorm sums s, ss (this thread's) reduced over the workgroup in a
+// fixed order -- thread, shuffle, red[..][wave], ((w0 + w1) + (w2 + w3)) -- and folded with the affine into ab (not IMG), or (IMG)
+// kept in red[br] until, after the last branch, the averages in lp are normalised, scaled, split and stored as operand images.
+template <bool IMG>
+__device__ __forceinline__ void gate_pool_finish(const DvqGateArgs &a, int br, int b, int g, int cpg, int ncell, int F, int npair,
+                                                 double s, double ss, double (&red)[3][2][4], float2 (&s_aff)[3 * 64],
+                                                 const float *lp, float2 *__restrict__ ab, char *__restrict__ ximg, float xscale)
+{
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    auto affine = [&](int brr, int chl) -> float2 {          // the group's statistics of branch brr folded with channel chl's affine
+        const double n = (double)cpg * (double)(a.hc * a.scale[brr]) * (double)(a.wc * a.scale[brr]);
+        const int rb = IMG ? brr : 0;
+        const double mean = ((red[rb][0][0] + red[rb][0][1]) + (red[rb][0][2] + red[rb][0][3])) / n;
+        double var = ((red[rb][1][0] + red[rb][1][1]) + (red[rb][1][2] + red[rb][1][3])) / n - mean * mean;   // biased, as GroupNorm
+        if (var < 0.0) var = 0.0;
+        const float mf = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)a.eps));
+        const int ch = g * cpg + chl;
+        const float sc_ = rstd * a.gn_w[brr][ch];
+        return make_float2(sc_, a.gn_b[brr][ch] - mf * sc_);
+    };
+    if (a.groups > 0) {
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off); ss += __shfl_xor(ss, off); }
+        if (IMG) {                                           // one barrier for all branches, after the last
+            if (lane == 0) { red[br][0][wave] = s; red[br][1][wave] = ss; }
+        } else {
+            __syncthreads();                                 // red[] of the previous branch consumed
+            if (lane == 0) { red[0][0][wave] = s; red[0][1][wave] = ss; }
+            __syncthreads();
+            if (tid < cpg) ab[(size_t)b * F + (size_t)br * a.C + g * cpg + tid] = affine(br, tid);
+        }
+    }
+    if (!IMG || br + 1 < a.nb) return;
+    // IMG, after the last branch: every branch's pooled averages are in LDS and its sums in red[]
+    __syncthreads();
+    for (int i = tid; i < a.nb * cpg; i += 256) s_aff[(i / cpg) * 64 + (i % cpg)] = affine(i / cpg, i % cpg);
+    __syncthreads();
+    // one thread per (branch, cell, octet of channels): 8 LDS reads, normalise, scale, split, two 16-B stores
+    const int noct = cpg / 8;
+    for (int u = tid; u < a.nb * ncell * noct; u += 256) {
+        const int brr = u / (ncell * noct), r2 = u - brr * (ncell * noct);
+        const int o = r2 / ncell, cell = r2 - o * ncell;
+        f16x8 hi, lo;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float2 af = s_aff[brr * 64 + 8 * o + j];
+            const float x = (lp[(size_t)brr * npair + (8 * o + j) * ncell + cell] * af.x + af.y) * xscale;
+            const _Float16 hh = (_Float16)x;
+            hi[j] = hh;
+            lo[j] = (_Float16)(x - (float)hh);
+        }
+        const int kk = brr * a.C + g * cpg + 8 * o;          // first feature of the octet
+        const long cg = (long)b * ncell + cell;
+        char *dst = ximg + ((size_t)(cg >> 5) * (F / 16) + (kk >> 4)) * 2048 + (((kk >> 3) & 1) * 32 + (int)(cg & 31)) * 16;
+        *(f16x8 *)dst = hi;
+        *(f16x8 *)(dst + 1024) = lo;
+    }
+}
+template <bool IMG, bool NT, int XT = 0>
+__global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArgs a, float2 *__restrict__ ab,
+                                                        float *__restrict__ pool, char *__restrict__ ximg,
+                                                        float *__restrict__ xs, const float *__restrict__ nbound)
+{
+    const int G = a.groups > 0 ? a.groups : a.C / 8;
+    const int cpg = a.C / G;
+    const int b = blockIdx.x / G, g = blockIdx.x - b * G;
+    const int ncell = a.hc * a.wc, F = a.nb * a.C;
+    const int npair = cpg * ncell;
+    __shared__ double red[3][2][4];                          // [branch (IMG; else 0)][sum | sum of squares][wave]
+    __shared__ float s_bound[4];
+    __shared__ float2 s_aff[3 * 64];                         // IMG: (scale, shift) of the group's channels, per branch
+    extern __shared__ float lp[];                            // IMG: [branch][cpg][ncell] pooled averages
+    const int tid = threadIdx.x;
+    const float xscale = gate_pool_xscale<IMG>(a, cpg, F, nbound, s_bound, xs, blockIdx.x == 0);
     for (int br = 0; br < a.nb; ++br) {
         const int sc = a.scale[br];
         const int Wb = a.wc * sc;
@@ -219,54 +290,7 @@ __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArg
             }
             o0[pr] = v;
         }
-        auto affine = [&](int brr, int chl) -> float2 {      // the group's statistics of branch brr folded with channel chl's affine
-            const double n = (double)cpg * (double)(a.hc * a.scale[brr]) * (double)(a.wc * a.scale[brr]);
-            const int rb = IMG ? brr : 0;
-            const double mean = ((red[rb][0][0] + red[rb][0][1]) + (red[rb][0][2] + red[rb][0][3])) / n;
-            double var = ((red[rb][1][0] + red[rb][1][1]) + (red[rb][1][2] + red[rb][1][3])) / n - mean * mean;   // biased, as GroupNorm
-            if (var < 0.0) var = 0.0;
-            const float mf = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)a.eps));
-            const int ch = g * cpg + chl;
-            const float sc_ = rstd * a.gn_w[brr][ch];
-            return make_float2(sc_, a.gn_b[brr][ch] - mf * sc_);
-        };
-        if (a.groups > 0) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off); ss += __shfl_xor(ss, off); }
-            if (IMG) {                                       // one barrier for all branches, after the loop
-                if (lane == 0) { red[br][0][wave] = s; red[br][1][wave] = ss; }
-            } else {
-                __syncthreads();                             // red[] of the previous branch consumed
-                if (lane == 0) { red[0][0][wave] = s; red[0][1][wave] = ss; }
-                __syncthreads();
-                if (tid < cpg) ab[(size_t)b * F + (size_t)br * a.C + g * cpg + tid] = affine(br, tid);
-            }
-        }
-        if (!IMG || br + 1 < a.nb) continue;
-        // IMG, after the last branch: every branch's pooled averages are in LDS and its sums in red[]
-        __syncthreads();
-        for (int i = tid; i < a.nb * cpg; i += 256) s_aff[(i / cpg) * 64 + (i % cpg)] = affine(i / cpg, i % cpg);
-        __syncthreads();
-        // one thread per (branch, cell, octet of channels): 8 LDS reads, normalise, scale, split, two 16-B stores
-        const int noct = cpg / 8;
-        for (int u = tid; u < a.nb * ncell * noct; u += 256) {
-            const int brr = u / (ncell * noct), r2 = u - brr * (ncell * noct);
-            const int o = r2 / ncell, cell = r2 - o * ncell;
-            f16x8 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float2 af = s_aff[brr * 64 + 8 * o + j];
-                const float x = (lp[(size_t)brr * npair + (8 * o + j) * ncell + cell] * af.x + af.y) * xscale;
-                const _Float16 hh = (_Float16)x;
-                hi[j] = hh;
-                lo[j] = (_Float16)(x - (float)hh);
-            }
-            const int kk = brr * a.C + g * cpg + 8 * o;      // first feature of the octet
-            const long cg = (long)b * ncell + cell;
-            char *dst = ximg + ((size_t)(cg >> 5) * (F / 16) + (kk >> 4)) * 2048 + (((kk >> 3) & 1) * 32 + (int)(cg & 31)) * 16;
-            *(f16x8 *)dst = hi;
-            *(f16x8 *)(dst + 1024) = lo;
-        }
+        gate_pool_finish<IMG>(a, br, b, g, cpg, ncell, F, npair, s, ss, red, s_aff, lp, ab, ximg, xscale);
     }
 }
 
@@ -283,8 +307,8 @@ __global__ __launch_bounds__(256, DVQ_POOL_WPE) void gate_pool_kernel(DvqGateArg
 // C-element rows, whose remaining bytes the workgroups of the neighbouring groups read.  Those workgroups are therefore dealt to
 // ONE XCD, one after the other (workgroups go round-robin over the 8 XCDs: workgroup i takes the logical index
 // (i % 8) * chunk + i / 8, the grid is rounded up to 8 * chunk and the surplus exits), so that a line fetched for one of them is
-// an L2 hit for the others.  Arithmetic behind the load, LDS staging and the IMG epilogue: gate_pool_kernel's, restated here so
-// that its instantiations keep their machine code.
+// an L2 hit for the others.  The fp16 range scale before the walk and everything behind it -- reduction, affine, LDS staging and
+// the IMG epilogue -- are the pieces gate_pool_kernel calls: gate_pool_xscale and gate_pool_finish.
 template <int XT, bool NT, int E> __device__ __forceinline__ void gate_ld_piece(const typename GateElem<XT>::T *p, float (&r)[E])
 {
     static_assert(XT != 0 || E <= 4, "a piece is at most 16 bytes");
@@ -368,37 +392,7 @@ __global__ __launch_bounds__(256, 4) void gate_pool_rows_kernel(DvqGateArgs a, f
     __shared__ float s_bound[4];
     __shared__ float2 s_aff[3 * 64];                         // IMG: (scale, shift) of the group's channels, per branch
     extern __shared__ float lp[];                            // IMG: [branch][cpg][ncell] pooled averages
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    float xscale = 1.0f;
-    if (IMG) {                                               // the fp16 range bound and its power-of-two scale: gate_pool_kernel's
-        float bound = 0.0f;
-        if (nbound != nullptr && __builtin_bit_cast(int, nbound[0]) == DVQ_GATE_NORM_MAGIC) {
-            for (int br = 0; br < a.nb; ++br) {
-                const float n = (float)cpg * (float)(a.hc * a.scale[br]) * (float)(a.wc * a.scale[br]);
-                bound = fmaxf(bound, nbound[1 + 2 * br] * sqrtf(n) * 1.0001f + nbound[2 + 2 * br]);
-            }
-        } else {
-            for (int k = tid; k < F; k += 256) {
-                const int br = k / a.C, ch = k - br * a.C;
-                const float n = (float)cpg * (float)(a.hc * a.scale[br]) * (float)(a.wc * a.scale[br]);
-                bound = fmaxf(bound, fabsf(a.gn_w[br][ch]) * sqrtf(n) * 1.0001f + fabsf(a.gn_b[br][ch]));
-            }
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) bound = fmaxf(bound, __shfl_xor(bound, off));
-            if (lane == 0) s_bound[wave] = bound;
-            __syncthreads();
-            bound = fmaxf(fmaxf(s_bound[0], s_bound[1]), fmaxf(s_bound[2], s_bound[3]));
-        }
-        float inv = 1.0f;
-        if (bound > 0.0f && bound < __builtin_inff()) {
-            int e;
-            (void)frexpf(bound, &e);
-            const int sh = 13 - e < 100 ? 13 - e : 100;
-            xscale = ldexpf(1.0f, sh);
-            inv = ldexpf(1.0f, -sh);
-        }
-        if (wg == 0 && tid == 0) xs[0] = inv;
-    }
+    const float xscale = gate_pool_xscale<IMG>(a, cpg, F, nbound, s_bound, xs, wg == 0);
     for (int br = 0; br < a.nb; ++br) {
         const int sc = a.scale[br];
         typedef typename GateElem<XT>::T elem_t;
@@ -410,54 +404,7 @@ __global__ __launch_bounds__(256, 4) void gate_pool_rows_kernel(DvqGateArgs a, f
         } else if (a.vec == 4) gate_pool_rows_branch<XT, NT, 4>(p0, a.C, sc, a.wc, cpg, ncell, o0, s, ss);
         else if (a.vec == 2) gate_pool_rows_branch<XT, NT, 2>(p0, a.C, sc, a.wc, cpg, ncell, o0, s, ss);
         else gate_pool_rows_branch<XT, NT, 1>(p0, a.C, sc, a.wc, cpg, ncell, o0, s, ss);
-        auto affine = [&](int brr, int chl) -> float2 {      // the group's statistics of branch brr folded with channel chl's affine
-            const double n = (double)cpg * (double)(a.hc * a.scale[brr]) * (double)(a.wc * a.scale[brr]);
-            const int rb = IMG ? brr : 0;
-            const double mean = ((red[rb][0][0] + red[rb][0][1]) + (red[rb][0][2] + red[rb][0][3])) / n;
-            double var = ((red[rb][1][0] + red[rb][1][1]) + (red[rb][1][2] + red[rb][1][3])) / n - mean * mean;   // biased, as GroupNorm
-            if (var < 0.0) var = 0.0;
-            const float mf = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)a.eps));
-            const int ch = g * cpg + chl;
-            const float sc_ = rstd * a.gn_w[brr][ch];
-            return make_float2(sc_, a.gn_b[brr][ch] - mf * sc_);
-        };
-        if (a.groups > 0) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) { s += __shfl_xor(s, off); ss += __shfl_xor(ss, off); }
-            if (IMG) {                                       // one barrier for all branches, after the loop
-                if (lane == 0) { red[br][0][wave] = s; red[br][1][wave] = ss; }
-            } else {
-                __syncthreads();                             // red[] of the previous branch consumed
-                if (lane == 0) { red[0][0][wave] = s; red[0][1][wave] = ss; }
-                __syncthreads();
-                if (tid < cpg) ab[(size_t)b * F + (size_t)br * a.C + g * cpg + tid] = affine(br, tid);
-            }
-        }
-        if (!IMG || br + 1 < a.nb) continue;
-        // IMG, after the last branch: every branch's pooled averages are in LDS and its sums in red[]
-        __syncthreads();
-        for (int i = tid; i < a.nb * cpg; i += 256) s_aff[(i / cpg) * 64 + (i % cpg)] = affine(i / cpg, i % cpg);
-        __syncthreads();
-        // one thread per (branch, cell, octet of channels): 8 LDS reads, normalise, scale, split, two 16-B stores
-        const int noct = cpg / 8;
-        for (int u = tid; u < a.nb * ncell * noct; u += 256) {
-            const int brr = u / (ncell * noct), r2 = u - brr * (ncell * noct);
-            const int o = r2 / ncell, cell = r2 - o * ncell;
-            f16x8 hi, lo;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float2 af = s_aff[brr * 64 + 8 * o + j];
-                const float x = (lp[(size_t)brr * npair + (8 * o + j) * ncell + cell] * af.x + af.y) * xscale;
-                const _Float16 hh = (_Float16)x;
-                hi[j] = hh;
-                lo[j] = (_Float16)(x - (float)hh);
-            }
-            const int kk = brr * a.C + g * cpg + 8 * o;      // first feature of the octet
-            const long cg = (long)b * ncell + cell;
-            char *dst = ximg + ((size_t)(cg >> 5) * (F / 16) + (kk >> 4)) * 2048 + (((kk >> 3) & 1) * 32 + (int)(cg & 31)) * 16;
-            *(f16x8 *)dst = hi;
-            *(f16x8 *)(dst + 1024) = lo;
-        }
+        gate_pool_finish<IMG>(a, br, b, g, cpg, ncell, F, npair, s, ss, red, s_aff, lp, ab, ximg, xscale);
     }
 }
 
@@ -614,9 +561,6 @@ __global__ __launch_bounds__(GATE_NW * 64) void router_gate_kernel(
     if (tid == 0) s_amax = 0u;
     __syncthreads();
     float inv_scale = 1.0f;
-#ifdef GATE_PROBE_NO_BUILD
-    if (false)
-#endif
     {
         float vmax = 0.0f;
 #pragma unroll
@@ -678,9 +622,6 @@ __global__ __launch_bounds__(GATE_NW * 64) void router_gate_kernel(
     }
 
     __syncthreads();
-#ifdef GATE_PROBE_NO_MFMA
-    if (gate != nullptr) return;
-#endif
     // ---- hidden layer on the fp16 matrix cores (split operands): wave w takes hidden-row tiles w, w + GATE_NW, ...
     const int T = (Hid + 31) / 32;
     const int S = Fp / 16;
@@ -715,13 +656,8 @@ __global__ __launch_bounds__(GATE_NW * 64) void router_gate_kernel(
             const int t = wave + GATE_NW * (gg / GPT), s0 = 4 * (gg % GPT);
             const f16x8 *ah = (const f16x8 *)imgH + (size_t)t * S * 64 + lane;
             const f16x8 *al = (const f16x8 *)imgL + (size_t)t * S * 64 + lane;
-#ifdef GATE_PROBE_NO_LOADS
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { vh[u] = xh[u * 64]; vl[u] = xh[XLO + u * 64]; (void)ah; (void)al; }
-#else
 #pragma unroll
             for (int u = 0; u < 4; ++u) { vh[u] = ah[(s0 + u) * 64]; vl[u] = al[(s0 + u) * 64]; }
-#endif
         };
         f32x16 acc[CB];
         auto step = [&](int g, const f16x8 (&vh)[4], const f16x8 (&vl)[4]) {
@@ -744,13 +680,8 @@ __global__ __launch_bounds__(GATE_NW * 64) void router_gate_kernel(
                 }
             }
             if (s0 + 4 == S) {
-#ifdef GATE_PROBE_NO_EPI
-#pragma unroll
-                for (int cb = 0; cb < CB; ++cb) part[cb][0] += acc[cb][0];
-#else
 #pragma unroll
                 for (int cb = 0; cb < CB; ++cb) epilogue(t, acc[cb], part[cb]);
-#endif
             }
         };
         if (NG > 0) {
@@ -916,6 +847,34 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
     issue(RING - 2);
     rd_base = lds_lane;
     GG_RD(0, 0); GG_RD(1, 1); GG_RD(2, 2); GG_RD(3, 3);
+    // The S k-steps of cell block I into acc, for both forms below.  A macro and not a lambda: this instruction order was placed by
+    // hand and measured, and as text it reaches the compiler unchanged (two hooks on a shared lambda moved the schedule).  Per k-step:
+    //   - four pairs (k-steps sk .. sk + 3) are in flight: the oldest has landed when at most six reads are outstanding;
+    //   - three MFMAs, small terms first, and one ring piece per k-step behind the first, which keeps the pipe busy while the DMA
+    //     instruction issues; MID sits between the second and the third, END behind the third (PIPE's epilogue rows; else empty);
+    //   - k-step u = sk + 4 of this block (= k-step u % S of block I or I + 1) takes over the pair's registers, entering a new chunk
+    //     where it starts one (past the last chunk the ring repeats the last one).  An output of these reads must always have a
+    //     later use -- here the counted wait four k-steps on, at the end of a block the drain: hipcc reuses the registers of a dead
+    //     asm output while the read is still in flight.
+#define GG_KSTEPS(I, MID, END)                                                                                          \
+    _Pragma("unroll")                                                                                                   \
+    for (int sk = 0; sk < S; ++sk) {                                                                                    \
+        const int u = sk + 4;                                                                                           \
+        asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(bh[sk & 3]), "+v"(bl[sk & 3]) :: "memory");                          \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sk], bh[sk & 3], acc, 0, 0, 0);                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
+        if (u % CH > 0 && u % CH < PPW) issue_piece(u % CH);                                                            \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bl[sk & 3], acc, 0, 0, 0);                                 \
+        MID                                                                                                             \
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bh[sk & 3], acc, 0, 0, 0);                                 \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
+        END                                                                                                             \
+        if (u % CH == 0) enter_chunk((I) * NCH + u / CH);                                                               \
+        GG_RD(u, u % CH);                                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
+    }
     // Epilogue of a cell block = bias, activation, contraction with the output layer: register r of lane half h is hidden row
     // (r & 3) + 8 (r >> 2) + 4 h of the tile, cell c.  SiLU = y / (1 + 2^(-y log2 e)) on v_exp_f32 / v_rcp_f32 (~2 ulp; the logits'
     // tolerance is 1e-4): the IEEE division sequence and a branch per element were a quarter of the kernel.  PIPE (dual router,
@@ -942,7 +901,7 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
             if (h == 0 && cgl < ncell) po[g] = v;
         }
     };
-    auto run = [&](auto silu_tag) {
+    auto run = [&](auto silu_tag) {                          // PIPE's stream of cell blocks, one copy per activation
         constexpr bool SILU = decltype(silu_tag)::value;
         auto activ = [&](float yv) -> float {
             return SILU ? yv * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504088896f * yv)) : (yv > 0.0f ? yv : 0.0f);
@@ -963,72 +922,24 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#pragma unroll
-            for (int sk = 0; sk < S; ++sk) {
-                const int u = sk + 4;                        // read-ahead: k-step sk + 4 of this block = k-step (sk + 4) % S of block i or i + 1
-                // four pairs (k-steps sk .. sk + 3) are in flight: the oldest has landed when at most six reads are outstanding
-                asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(bh[sk & 3]), "+v"(bl[sk & 3]) :: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sk], bh[sk & 3], acc, 0, 0, 0);     // small terms first
-                __builtin_amdgcn_sched_barrier(0);
-                // one ring piece per k-step, behind an MFMA that keeps the pipe busy while the DMA instruction issues
-                if (u % CH > 0 && u % CH < PPW) issue_piece(u % CH);
-                __builtin_amdgcn_sched_barrier(0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bl[sk & 3], acc, 0, 0, 0);
-                if (PIPE && PREV && sk < 16) { __builtin_amdgcn_sched_barrier(0); epi_row(sk); __builtin_amdgcn_sched_barrier(0); }
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bh[sk & 3], acc, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (PIPE && PREV && sk == 16) {
-                    store_part(i - 1, ptp);
-#pragma unroll
-                    for (int g = 0; g < G; ++g) ptp[g] = 0.0f;
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-                // k-step sk + 4 takes over the pair's registers (an output of these reads must always have a later use -- here
-                // the counted wait four k-steps on, at the end of a block the drain below: hipcc reuses the registers of a dead
-                // asm output while the read is still in flight)
-                if (u % CH == 0) enter_chunk(i * NCH + u / CH);  // (past the last chunk: the ring repeats the last one)
-                GG_RD(u, u % CH);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if (PIPE) {
-                accp = acc;                                  // consumed during the next block (or after the loop)
-                return;
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bh[0]), "+v"(bl[0]), "+v"(bh[1]), "+v"(bl[1]), "+v"(bh[2]), "+v"(bl[2]),
-                         "+v"(bh[3]), "+v"(bl[3]) :: "memory");  // the next block's first four pairs: landed before other LDS traffic
-            float pt[G];
-#pragma unroll
-            for (int g = 0; g < G; ++g) pt[g] = 0.0f;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const f32x4 bb = *(const f32x4 *)(pb + 8 * q4 + 4 * h);
-                f32x4 ww[G];
-#pragma unroll
-                for (int g = 0; g < G; ++g) ww[g] = *(const f32x4 *)(pb + (1 + g) * 32 + 8 * q4 + 4 * h);
-#pragma unroll
-                for (int r4 = 0; r4 < 4; ++r4) {
-                    const float hv = activ(acc[4 * q4 + r4] * inv_scale + bb[r4]);
-#pragma unroll
-                    for (int g = 0; g < G; ++g) pt[g] = __builtin_fmaf(ww[g][r4], hv, pt[g]);
-                }
-            }
-            store_part(i, pt);
+            GG_KSTEPS(i,
+                      if (PREV && sk < 16) { __builtin_amdgcn_sched_barrier(0); epi_row(sk); __builtin_amdgcn_sched_barrier(0); },
+                      if (PREV && sk == 16) {
+                          store_part(i - 1, ptp);
+                          _Pragma("unroll")
+                          for (int g = 0; g < G; ++g) ptp[g] = 0.0f;
+                          __builtin_amdgcn_sched_barrier(0);
+                      })
+            accp = acc;                                      // consumed during the next block (or after the loop)
         };
-        if constexpr (PIPE) {
-            block(0, std::false_type{});
-            for (int i = 1; i < nmine; ++i) block(i, std::true_type{});
-        } else {
-            for (int i = 0; i < nmine; ++i) block(i, std::false_type{});
-        }
-        // drain the read-ahead (its last four pairs are never consumed) and, PIPE, the last block's epilogue
+        block(0, std::false_type{});
+        for (int i = 1; i < nmine; ++i) block(i, std::true_type{});
+        // drain the read-ahead (its last four pairs are never consumed), then the last block's epilogue
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bh[0]), "+v"(bl[0]), "+v"(bh[1]), "+v"(bl[1]), "+v"(bh[2]), "+v"(bl[2]),
                      "+v"(bh[3]), "+v"(bl[3]) :: "memory");
-        if (PIPE) {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) epi_row(r);
-            store_part(nmine - 1, ptp);
-        }
+        for (int r = 0; r < 16; ++r) epi_row(r);
+        store_part(nmine - 1, ptp);
     };
     if constexpr (PIPE) {
         if (act == 1) run(std::true_type{});
@@ -1040,24 +951,9 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
-#pragma unroll
-            for (int sk = 0; sk < S; ++sk) {
-                const int u = sk + 4;
-                asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(bh[sk & 3]), "+v"(bl[sk & 3]) :: "memory");
-                __builtin_amdgcn_sched_barrier(0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[sk], bh[sk & 3], acc, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (u % CH > 0 && u % CH < PPW) issue_piece(u % CH);
-                __builtin_amdgcn_sched_barrier(0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bl[sk & 3], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[sk], bh[sk & 3], acc, 0, 0, 0);
-                __builtin_amdgcn_sched_barrier(0);
-                if (u % CH == 0) enter_chunk(i * NCH + u / CH);
-                GG_RD(u, u % CH);
-                __builtin_amdgcn_sched_barrier(0);
-            }
+            GG_KSTEPS(i, , )
             asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bh[0]), "+v"(bl[0]), "+v"(bh[1]), "+v"(bl[1]), "+v"(bh[2]), "+v"(bl[2]),
-                         "+v"(bh[3]), "+v"(bl[3]) :: "memory");
+                         "+v"(bh[3]), "+v"(bl[3]) :: "memory");  // the next block's first four pairs: landed before other LDS traffic
             float pt[G];
 #pragma unroll
             for (int g = 0; g < G; ++g) pt[g] = 0.0f;
@@ -1085,6 +981,7 @@ __global__ __launch_bounds__(256, 1) void gate_gemm_kernel(
         }
     }
     (void)red;
+#undef GG_KSTEPS
 #undef GG_RD
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");         // surplus ring DMA
 }
@@ -1207,6 +1104,49 @@ int dvq_launch_router_gate_prepare(const float *W1, int nb, int C, int Hid, void
     return (int)hipGetLastError();
 }
 
+static int gate_ncu()                                        // compute units of the CURRENT device (no process-wide cache)
+{
+    int dev = 0, n = 256;
+    if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
+    return n > 0 ? n : 256;
+}
+
+// The pooling pass of either form of the gate: one workgroup per (image, channel group), `lds` bytes of dynamic LDS; IMG (the GEMM
+// form) with the three pointers of the operand images, else nullptr.  The kernel follows from the layout, the element type (xt: 0
+// float32, 1 = DVQ_DTYPE_F16, 2 = DVQ_DTYPE_BF16) and `cached`.  channels_last branches (gate_pool_rows_kernel): the piece of E
+// elements, 16 bytes where the group's slice and the branches' actual alignment allow, else narrower; workgroups renumbered in 8
+// chunks, one per XCD.
+template <bool IMG>
+static void gate_pool_launch(DvqGateArgs a, int xt, int nhwc, bool cached, size_t lds, float2 *stats, float *pool, char *ximg,
+                             float *xs, const float *nbound, hipStream_t st)
+{
+    const int nwg = a.B * (a.groups > 0 ? a.groups : a.C / 8), chunk = (nwg + 7) / 8;
+    if (nhwc) {
+        const int es = xt != 0 ? 2 : 4, cpg = a.groups > 0 ? a.C / a.groups : 8;
+        uintptr_t al = 0;
+        for (int i = 0; i < a.nb; ++i) al |= (uintptr_t)a.h[i];
+        int E = 16 / es;
+        while (E > 1 && (cpg % E != 0 || al % ((uintptr_t)E * es) != 0)) E >>= 1;
+        a.vec = E;
+    }
+    auto launch = [&](auto nt, auto x) {
+        constexpr bool NT = decltype(nt)::value;
+        constexpr int XT = decltype(x)::value;
+        if (nhwc)
+            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG, NT, XT>), dim3(8 * chunk), dim3(256), lds, st, a, stats, pool, ximg, xs,
+                               nbound, nwg, chunk);
+        else
+            hipLaunchKernelGGL((gate_pool_kernel<IMG, NT, XT>), dim3(nwg), dim3(256), lds, st, a, stats, pool, ximg, xs, nbound);
+    };
+    auto of_type = [&](auto x) {
+        if (cached) launch(std::false_type{}, x);
+        else launch(std::true_type{}, x);
+    };
+    if (xt == 0) of_type(std::integral_constant<int, 0>{});
+    else if (xt == 1) of_type(std::integral_constant<int, 1>{});
+    else of_type(std::integral_constant<int, 2>{});
+}
+
 int dvq_launch_router_gate(int nb, const void *const *h, int xt, int nhwc, const float *const *gn_w, const float *const *gn_b,
                            int B, int C, int hc, int wc, int groups, float eps,
                            const float *W1, const float *b1, const float *W2, const float *b2,
@@ -1235,42 +1175,7 @@ int dvq_launch_router_gate(int nb, const void *const *h, int xt, int nhwc, const
     const bool cached = (size_t)B * C * hc * fs * wc * fs * sizeof(float) <= DVQ_CACHED_MAX_BYTES;
     float2 *stats = (float2 *)ws;                            // (scale, shift) per (image, feature)
     if (xt != 0 && xt != 1 && xt != 2) return -1000;
-    // the pooling pass on fp16 (xt = 1 = DVQ_DTYPE_F16) / bf16 (2 = DVQ_DTYPE_BF16) features: GRID workgroups, LDS bytes of dynamic LDS
-#define DVQ_POOL_X16(IMG_, NT_, GRID, LDS, XIMG, XS, NBOUND)                                                            \
-    do {                                                                                                                \
-        if (xt == 1)                                                                                                    \
-            hipLaunchKernelGGL((gate_pool_kernel<IMG_, NT_, 1>), GRID, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND);  \
-        else                                                                                                            \
-            hipLaunchKernelGGL((gate_pool_kernel<IMG_, NT_, 2>), GRID, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND);  \
-    } while (0)
     float *pool = (float *)((char *)ws + align256r((size_t)B * F * sizeof(float2)));
-    // channels_last branches (gate_pool_rows_kernel): the piece of E elements, 16 bytes where the group's slice and the branches'
-    // actual alignment allow, else narrower; workgroups renumbered in 8 chunks, one per XCD
-    if (nhwc) {
-        const int es = xt != 0 ? 2 : 4, cpg_r = groups > 0 ? C / groups : 8;
-        uintptr_t al = 0;
-        for (int i = 0; i < nb; ++i) al |= (uintptr_t)h[i];
-        int E = 16 / es;
-        while (E > 1 && (cpg_r % E != 0 || al % ((uintptr_t)E * es) != 0)) E >>= 1;
-        a.vec = E;
-    }
-    const int nwg_r = B * (groups > 0 ? groups : C / 8), chunk_r = (nwg_r + 7) / 8;
-#define DVQ_POOL_ROWS(IMG_, LDS, XIMG, XS, NBOUND)                                                                      \
-    do {                                                                                                                \
-        const dim3 grid_r(8 * chunk_r);                                                                                 \
-        if (xt == 0 && cached)                                                                                          \
-            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, false, 0>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
-        else if (xt == 0)                                                                                               \
-            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, true, 0>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
-        else if (xt == 1 && cached)                                                                                     \
-            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, false, 1>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
-        else if (xt == 1)                                                                                               \
-            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, true, 1>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
-        else if (cached)                                                                                                \
-            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, false, 2>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
-        else                                                                                                            \
-            hipLaunchKernelGGL((gate_pool_rows_kernel<IMG_, true, 2>), grid_r, dim3(256), LDS, st, a, stats, pool, XIMG, XS, NBOUND, nwg_r, chunk_r); \
-    } while (0)
     // ws: [folded GroupNorm affine][pooled averages (direct form) OR feature images (GEMM form)][W1 images, when the caller
     //      passes none][partial logits of the GEMM form][its scale word]
     const long ncell = (long)B * hc * wc;
@@ -1300,25 +1205,8 @@ int dvq_launch_router_gate(int nb, const void *const *h, int xt, int nhwc, const
         if ((ncell & 31) != 0)                               // the last block's unused cell columns must hold finite values
             (void)hipMemsetAsync(ximg + (size_t)(nblocks - 1) * S16 * 2048, 0, (size_t)S16 * 2048, st);
         const size_t pool_lds = (size_t)nb * cpg * hc * wc * sizeof(float);
-        if (nhwc) {
-            DVQ_POOL_ROWS(true, pool_lds, ximg, xs, nbound);
-        } else
-        if (xt != 0) {                                       // 16-bit features: the same two forms, loads widened
-            if (cached) DVQ_POOL_X16(true, false, dim3(B * groups), pool_lds, ximg, xs, nbound);
-            else DVQ_POOL_X16(true, true, dim3(B * groups), pool_lds, ximg, xs, nbound);
-        } else
-        if (cached)
-            hipLaunchKernelGGL((gate_pool_kernel<true, false>), dim3(B * groups), dim3(256), (size_t)nb * cpg * hc * wc * sizeof(float), st, a,
-                               stats, pool, ximg, xs, nbound);
-        else
-            hipLaunchKernelGGL((gate_pool_kernel<true, true>), dim3(B * groups), dim3(256), (size_t)nb * cpg * hc * wc * sizeof(float), st, a,
-                               stats, pool, ximg, xs, nbound);
-        int ncu = 256;
-        {
-            int dev = 0, n = 256;
-            if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-            ncu = n > 0 ? n : 256;
-        }
+        gate_pool_launch<true>(a, xt, nhwc, cached, pool_lds, stats, pool, ximg, xs, nbound, st);
+        const int ncu = gate_ncu();
         const int HG = (Hid + 127) / 128;
         int CG = ncu / HG;
         if (CG < 1) CG = 1;
@@ -1353,28 +1241,11 @@ int dvq_launch_router_gate(int nb, const void *const *h, int xt, int nhwc, const
         hipLaunchKernelGGL(gate_finalize_kernel, dim3((unsigned)((nout + 255) / 256)), dim3(256), 0, st, part, HG * 4, nout, nb, b2, gate);
         return (int)hipGetLastError();
     }
-    if (nhwc) {
-        DVQ_POOL_ROWS(false, 0, nullptr, nullptr, nullptr);
-    } else
-    if (xt != 0) {
-        if (cached) DVQ_POOL_X16(false, false, dim3(B * (groups > 0 ? groups : C / 8)), 0, nullptr, nullptr, nullptr);
-        else DVQ_POOL_X16(false, true, dim3(B * (groups > 0 ? groups : C / 8)), 0, nullptr, nullptr, nullptr);
-    } else
-    if (cached)
-        hipLaunchKernelGGL((gate_pool_kernel<false, false>), dim3(B * (groups > 0 ? groups : C / 8)), dim3(256), 0, st, a, stats, pool,
-                           nullptr, nullptr, nullptr);
-    else
-        hipLaunchKernelGGL((gate_pool_kernel<false, true>), dim3(B * (groups > 0 ? groups : C / 8)), dim3(256), 0, st, a, stats, pool,
-                           nullptr, nullptr, nullptr);
+    gate_pool_launch<false>(a, xt, nhwc, cached, 0, stats, pool, nullptr, nullptr, nullptr, st);
     // two blocks of 32 cells per workgroup when the split tile of 64 cells fits the LDS and there are enough cells to keep
     // every CU busy that way
     const size_t shmem2 = ((size_t)2 * 32 * Fp + (size_t)(1 + nb) * Hid) * sizeof(float);
-    int ncu = 256;                                           // of the CURRENT device (no process-wide cache)
-    {
-        int dev = 0, n = 256;
-        if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev);
-        ncu = n > 0 ? n : 256;
-    }
+    const int ncu = gate_ncu();
     const bool cb2 = act != 0 && shmem2 <= DVQ_GATE_LDS_MAX - 256 && ncell >= 64L * ncu;
     const int CBv = cb2 ? 2 : 1;
     const unsigned grid = (unsigned)((ncell + 32 * CBv - 1) / (32 * CBv));
@@ -1386,7 +1257,5 @@ int dvq_launch_router_gate(int nb, const void *const *h, int xt, int nhwc, const
     const int rc = nb == 2 ? (cb2 ? DVQ_GATE_LAUNCH(2, 2) : DVQ_GATE_LAUNCH(2, 1))
                            : (cb2 ? DVQ_GATE_LAUNCH(3, 2) : DVQ_GATE_LAUNCH(3, 1));
 #undef DVQ_GATE_LAUNCH
-#undef DVQ_POOL_X16
-#undef DVQ_POOL_ROWS
     return rc;
 }
