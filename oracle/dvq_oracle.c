@@ -106,6 +106,15 @@ void dvq_oracle_token_distances(const float *z, long zs, const float *E,
 }
 
 /*
+ * The dots alone for one token: out[j] = the sequential-k FMA chain of z with row j of E
+ * (the score of the DOT metric; with a bias added after the chain, a projection's logit).
+ */
+void dvq_oracle_token_dots(const float *z, long zs, const float *E, int D, int K, float *out)
+{
+    for (int j = 0; j < K; ++j) out[j] = chain_dot(z, zs, E + (long)j * D, D);
+}
+
+/*
  * VectorQuantize2.forward / VectorQuantizer2.forward, eval mode.
  *   z      [B, D, HW] f32 (NCHW with HW = H*W); HW == 1 gives the flat [N, D] case
  *   E      [K, D] f32 (codebook rows; the caller passes weight[:-1] for VQEmbedding)

@@ -87,6 +87,16 @@ def token_distances(z_token, E):
     return d
 
 
+def token_dots(z_token, E):
+    """Reference-arithmetic dot products of ONE token [D] with every code -> [K] f32 (the sequential-k fp32 FMA chain)."""
+    z, pz = _f32(z_token)
+    E, pE = _f32(E)
+    K, D = E.shape
+    out = np.empty(K, np.float32)
+    lib().dvq_oracle_token_dots(pz, ctypes.c_long(1), pE, ctypes.c_int(D), ctypes.c_int(K), out.ctypes.data_as(_f32p))
+    return out
+
+
 def vq_assign_nchw(z, E, mask=None, want_zq=True, want_dmin=False, out=None):
     """VectorQuantize2 / VectorQuantizer2 forward core on z [B, D, H, W] (or [B, D, HW]).
 
