@@ -116,8 +116,10 @@ _VALUE_QUERIES = ("dvq_version", "dvq_vq_assign_narrow_tile_codes")   # return a
 # status calls whose refusals tests/golden/abi_rejections_det.json pins (tools/gen_golden_abi_rejections.py writes that table beside
 # abi_rejections.json, which holds every other status call and is kept as it was): ordinary `int` status, checked.* raises as for the rest
 _TABLED_APART = ("dvq_code_sums_det", "dvq_vq_backward_codebook_det_f32")
+# GumbelQuantize's training step, added later still: tests/golden/abi_rejections_gumbel_train.json, written by the same tool
+_TABLED_GUMBEL_TRAIN = ("dvq_vq_gumbel_forward_train_f32", "dvq_vq_gumbel_backward_f32")
 # the int-returning entry points that tests/golden/abi_rejections.json does not cover: the value queries and the calls tabled apart
-_INT_QUERIES = _VALUE_QUERIES + _TABLED_APART
+_INT_QUERIES = _VALUE_QUERIES + _TABLED_APART + _TABLED_GUMBEL_TRAIN
 
 
 def _raise_on_error(rc, func, args):

@@ -1413,18 +1413,19 @@ size_t dvq_vq_gumbel_assign_workspace_bytes(int B, int HW)
     return (((N + 127) / 128) * sizeof(double) + 255) / 256 * 256 + 256;
 }
 
-int dvq_vq_gumbel_assign_f32(const float *z, const void *prep, const float *embed, int B, int C, int HW, int K, int d, float tau,
-                             float kl_K, const float *q, float *zq, int64_t *codes, float *kl, void *ws, size_t ws_bytes, void *stream)
+// the sweep's checked body: dvq_vq_gumbel_assign_f32 (train == false, logits == nullptr) and the training forward, which also writes the logits
+static int gumbel_forward(const char *fn, bool train, const float *z, const void *prep, const float *embed, int B, int C, int HW, int K,
+                          int d, float tau, float kl_K, const float *q, float *zq, int64_t *codes, float *kl, float *logits, void *ws,
+                          size_t ws_bytes, void *stream)
 {
-    const char *fn = "dvq_vq_gumbel_assign_f32";
-    if (!z || !prep || !embed || !codes) return null_pointer(fn);
+    if (!z || !prep || !embed || !codes || (train && !logits)) return null_pointer(fn);
     if (B <= 0 || HW <= 0 || K <= 0 || d <= 0) { dvq_set_error("%s: B=%d HW=%d K=%d d=%d must be positive", fn, B, HW, K, d); return DVQ_EINVAL; }
     if (!dim_ok(C)) { dvq_set_error("%s: C=%d unsupported (kernel widths 64, 128, 256)", fn, C); return DVQ_EUNSUPPORTED; }
     if (q && (!(tau > 0.0f) || !(tau < __builtin_inff()))) { dvq_set_error("%s: tau=%g must be finite and positive when q is given", fn, (double)tau); return DVQ_EINVAL; }
     if (!(kl_K > 0.0f) || !(kl_K < __builtin_inff())) { dvq_set_error("%s: kl_K=%g must be finite and positive", fn, (double)kl_K); return DVQ_EINVAL; }
     const size_t N = (size_t)B * (size_t)HW;
     if (int rc = check_size(fn, N, true, C, K, d)) return rc;
-    if ((((uintptr_t)z | (uintptr_t)embed | (uintptr_t)q | (uintptr_t)zq | (uintptr_t)kl) & 3) != 0 || ((uintptr_t)prep & 255) != 0 || ((uintptr_t)codes & 7) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
+    if ((((uintptr_t)z | (uintptr_t)embed | (uintptr_t)q | (uintptr_t)zq | (uintptr_t)kl | (uintptr_t)logits) & 3) != 0 || ((uintptr_t)prep & 255) != 0 || ((uintptr_t)codes & 7) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
     double *partials = nullptr;
     if (kl) {
         const size_t need = dvq_vq_gumbel_assign_workspace_bytes(B, HW);
@@ -1434,13 +1435,48 @@ int dvq_vq_gumbel_assign_f32(const float *z, const void *prep, const float *embe
     }
     hipStream_t st = (hipStream_t)stream;
     int rc = dvq_launch_gumbel_assign(z, (const float *)prep, embed, C, HW, K, d, (long)N, tau, log((double)kl_K), q, zq,
-                                      (long long *)codes, partials, st);
+                                      (long long *)codes, partials, st, logits);
     if (rc) return hip_rc(rc, "vq_gumbel_assign");
     if (kl) {
         rc = dvq_launch_gumbel_kl_finalize(partials, dvq_gumbel_blocks((long)N), 1.0 / (double)N, kl, st);
         if (rc) return hip_rc(rc, "vq_gumbel_kl_finalize");
     }
     return DVQ_OK;
+}
+
+int dvq_vq_gumbel_assign_f32(const float *z, const void *prep, const float *embed, int B, int C, int HW, int K, int d, float tau,
+                             float kl_K, const float *q, float *zq, int64_t *codes, float *kl, void *ws, size_t ws_bytes, void *stream)
+{
+    return gumbel_forward("dvq_vq_gumbel_assign_f32", false, z, prep, embed, B, C, HW, K, d, tau, kl_K, q, zq, codes, kl, nullptr, ws,
+                          ws_bytes, stream);
+}
+
+// ---- GumbelQuantize's training step: the forward that keeps the logits, the backward down to them (vq_gumbel_backward.hip) -------
+int dvq_vq_gumbel_forward_train_f32(const float *z, const void *prep, const float *embed, int B, int C, int HW, int K, int d, float tau,
+                                    float kl_K, const float *q, float *zq, int64_t *codes, float *kl, float *logits, void *ws,
+                                    size_t ws_bytes, void *stream)
+{
+    return gumbel_forward("dvq_vq_gumbel_forward_train_f32", true, z, prep, embed, B, C, HW, K, d, tau, kl_K, q, zq, codes, kl, logits,
+                          ws, ws_bytes, stream);
+}
+
+int dvq_vq_gumbel_backward_f32(const float *logits, const float *q, const float *u, const float *g_kl, int B, int HW, int K, float tau,
+                               float kl_K, float *dlogits, void *ws, size_t ws_bytes, void *stream)
+{
+    const char *fn = "dvq_vq_gumbel_backward_f32";
+    (void)ws; (void)ws_bytes;                                   // reserved: the kernel keeps its partial states in LDS
+    if (!logits || !dlogits) return null_pointer(fn);
+    if (int rc = check_positive(fn, B, HW, K)) return rc;
+    if (u && (!(tau > 0.0f) || !(tau < __builtin_inff()))) { dvq_set_error("%s: tau=%g must be finite and positive when u is given", fn, (double)tau); return DVQ_EINVAL; }
+    if (g_kl && (!(kl_K > 0.0f) || !(kl_K < __builtin_inff()))) { dvq_set_error("%s: kl_K=%g must be finite and positive when g_kl is given", fn, (double)kl_K); return DVQ_EINVAL; }
+    const size_t N = (size_t)B * (size_t)HW;
+    if (int rc = check_size(fn, N, true, K)) return rc;
+    if ((((uintptr_t)logits | (uintptr_t)q | (uintptr_t)u | (uintptr_t)g_kl | (uintptr_t)dlogits) & 3) != 0) { dvq_set_error("%s: misaligned pointer", fn); return DVQ_EINVAL; }
+    // dlogits [N K] may be u itself; any other overlap with an input -- u at an offset included -- is a race between workgroups
+    const uintptr_t d0 = (uintptr_t)dlogits, span = (uintptr_t)(N * (size_t)K * sizeof(float));
+    auto overlaps = [&](const void *p, uintptr_t bytes) { return p && (uintptr_t)p < d0 + span && d0 < (uintptr_t)p + bytes; };
+    if (overlaps(logits, span) || overlaps(q, span) || overlaps(g_kl, sizeof(float)) || (u != dlogits && overlaps(u, span))) { dvq_set_error("%s: dlogits may alias u only, and only as a whole", fn); return DVQ_EINVAL; }
+    return hip_rc(dvq_launch_gumbel_backward(logits, q, u, g_kl, HW, K, (long)N, tau, dlogits, (hipStream_t)stream), "vq_gumbel_backward");
 }
 
 // ---- narrow widths (D = 4, 8, 16): the exact VALU assign of vq_assign_narrow.hip, no prepared codebook image -----------------

@@ -155,7 +155,12 @@ int dvq_launch_apply_codes(const float *z, const float *E, const long long *code
 int dvq_launch_gumbel_bias(const float *bias, int K, int D, void *prep, hipStream_t st);
 int dvq_gumbel_blocks(long N);
 int dvq_launch_gumbel_assign(const float *z, const float *prep, const float *E, int C, int HW, int K, int d, long N, float tau,
-                             double log_kl_K, const float *q, float *zq, long long *codes, double *partials, hipStream_t st);
+                             double log_kl_K, const float *q, float *zq, long long *codes, double *partials, hipStream_t st,
+                             float *logits = nullptr);    // logits [B, K, HW] given: the training forward, which writes them too
+// GumbelQuantize's backward (vq_gumbel_backward.hip; include/dvq.h: dvq_vq_gumbel_backward_f32): dlogits [B, K, HW] from the saved
+// logits, the variates q (nullable), u = embed . G (nullable) and the device scalar g_kl (nullable); dlogits may be u itself
+int dvq_launch_gumbel_backward(const float *logits, const float *q, const float *u, const float *g_kl, int HW, int K, long N,
+                               float tau, float *dlogits, hipStream_t st);
 int dvq_narrow_tile_codes(int D);
 int dvq_narrow_blocks(long N);
 int dvq_launch_narrow(const float *z, const float *E, const float *mask, int D, int HW, int K, long N, bool flat, float *zq,

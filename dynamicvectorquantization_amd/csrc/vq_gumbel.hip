@@ -32,11 +32,15 @@
 #include "launchers.h"
 #include "dvq_exact_tile.h"
 
-template <int D, bool NOISE>
+// LOGITS (the training forward, dvq_vq_gumbel_forward_train_f32): the same sweep also writes l to logits [B, K, HW], the layout of
+// q -- register r of the 32 lanes of a half is one code of 32 consecutive tokens, 128 contiguous bytes per store, non-temporal (the
+// backward reads them, csrc/vq_gumbel_backward.hip; nothing here does).  Everything the flag adds stands behind `if constexpr`:
+// the instantiations without it are the code they were.
+template <int D, bool NOISE, bool LOGITS = false>
 __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
     const float *__restrict__ z, const float *__restrict__ tiles, const float *__restrict__ E, int HW, int K, int d, long N,
     float tau, double log_kl_K, const float *__restrict__ q, float *__restrict__ zq, long long *__restrict__ codes,
-    double *__restrict__ partials)
+    double *__restrict__ partials, float *__restrict__ logits)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];   // dvq_exact_lds_bytes(D)
     __shared__ double red[4];
@@ -83,6 +87,13 @@ __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
         f32x16 acc;
         exact_tile_dots<D>(buf, zr, c, h, acc);
         float l[16];
+        // the row of the tile's first code of this lane half, formed behind the MFMA chain (the empty asm ties it to the chain's result:
+        // formed ahead of it, the sixteen addresses would live through the chain, where the registers are fullest)
+        float *lrow = nullptr;
+        if constexpr (LOGITS) {
+            lrow = logits + (size_t)b * (size_t)K * (size_t)HW + (size_t)hw + (size_t)exact_code_of(t, 0, 0, h) * (size_t)HW;
+            asm volatile("" : "+v"(lrow) : "v"(acc[15]));
+        }
         // the tile's maximum over this lane's codes: fmaxf drops a NaN here, which reaches the sums through its own term
         float tm = -__builtin_inff();
 #pragma unroll
@@ -93,6 +104,9 @@ __global__ __launch_bounds__(256, 2) void vq_gumbel_assign_kernel(
                 const int r = g * 4 + j;
                 const int code = exact_code_of(t, g, j, h);
                 l[r] = __fadd_rn(acc[r], b4[j]);
+                if constexpr (LOGITS) {
+                    if (valid && code < K) __builtin_nontemporal_store(l[r], lrow + (size_t)(j + 8 * g) * (size_t)HW);
+                }
                 float s = l[r];
                 if constexpr (NOISE) s = __fadd_rn(s, -logf(qq[r])) / tau;
                 const bool take = argmax_take(s, best) && (code < K);
@@ -207,25 +221,34 @@ int dvq_gumbel_blocks(long N) { return (int)((N + 127) / 128); }
 
 template <int D>
 static int launch_gumbel(const float *z, const float *tiles, const float *E, int HW, int K, int d, long N, float tau, double log_kl_K,
-                         const float *q, float *zq, long long *codes, double *partials, hipStream_t st)
+                         const float *q, float *zq, long long *codes, double *partials, float *logits, hipStream_t st)
 {
     const size_t shmem = dvq_exact_lds_bytes(D);
     const dim3 grid((unsigned)dvq_gumbel_blocks(N)), block(256);
+    if (logits != nullptr) {                         // the training forward
+        if (q == nullptr)
+            return dvq_launch_lds<vq_gumbel_assign_kernel<D, false, true>>(grid, block, shmem, st, z, tiles, E, HW, K, d, N, tau,
+                                                                           log_kl_K, q, zq, codes, partials, logits);
+        return dvq_launch_lds<vq_gumbel_assign_kernel<D, true, true>>(grid, block, shmem, st, z, tiles, E, HW, K, d, N, tau, log_kl_K,
+                                                                      q, zq, codes, partials, logits);
+    }
     if (q == nullptr)
         return dvq_launch_lds<vq_gumbel_assign_kernel<D, false>>(grid, block, shmem, st, z, tiles, E, HW, K, d, N, tau, log_kl_K, q, zq,
-                                                                 codes, partials);
+                                                                 codes, partials, logits);
     return dvq_launch_lds<vq_gumbel_assign_kernel<D, true>>(grid, block, shmem, st, z, tiles, E, HW, K, d, N, tau, log_kl_K, q, zq,
-                                                            codes, partials);
+                                                            codes, partials, logits);
 }
 
-// z [B, C, HW] (HW == 1: row-major [N, C]); prep: the f32 tile images with the bias in the en slot; q nullable [B, K, HW]
+// z [B, C, HW] (HW == 1: row-major [N, C]); prep: the f32 tile images with the bias in the en slot; q nullable [B, K, HW];
+// logits nullable [B, K, HW]: given, the sweep writes them too
 int dvq_launch_gumbel_assign(const float *z, const float *prep, const float *E, int C, int HW, int K, int d, long N, float tau,
-                             double log_kl_K, const float *q, float *zq, long long *codes, double *partials, hipStream_t st)
+                             double log_kl_K, const float *q, float *zq, long long *codes, double *partials, hipStream_t st,
+                             float *logits)
 {
     switch (C) {
-    case 64:  return launch_gumbel<64>(z, prep, E, HW, K, d, N, tau, log_kl_K, q, zq, codes, partials, st);
-    case 128: return launch_gumbel<128>(z, prep, E, HW, K, d, N, tau, log_kl_K, q, zq, codes, partials, st);
-    case 256: return launch_gumbel<256>(z, prep, E, HW, K, d, N, tau, log_kl_K, q, zq, codes, partials, st);
+    case 64:  return launch_gumbel<64>(z, prep, E, HW, K, d, N, tau, log_kl_K, q, zq, codes, partials, logits, st);
+    case 128: return launch_gumbel<128>(z, prep, E, HW, K, d, N, tau, log_kl_K, q, zq, codes, partials, logits, st);
+    case 256: return launch_gumbel<256>(z, prep, E, HW, K, d, N, tau, log_kl_K, q, zq, codes, partials, logits, st);
     default:  return -1000;
     }
 }

@@ -18,6 +18,7 @@ import math
 import torch
 import torch.distributed as dist
 from torch import nn
+from torch.autograd.function import once_differentiable
 from torch.nn import functional as F
 
 from . import _lib
@@ -1695,6 +1696,130 @@ def gumbel_assign(z, prep_buf, embed, tau=1.0, q=None, kl_K=None, want_zq=True, 
     return zq, codes, kl
 
 
+def _gumbel_shape(z, embed, q):
+    z = _lib.require_cuda_f32(z, "z")
+    embed = _lib.require_cuda_f32(embed, "embed.weight")
+    if z.dim() < 2:
+        raise ValueError("z must be [B, C, ...]")
+    K = embed.shape[0]
+    B, spatial = z.shape[0], tuple(z.shape[2:])
+    HW = 1
+    for sdim in spatial:
+        HW *= sdim
+    if q is not None:
+        q = _lib.require_cuda_f32(q, "q")
+        if q.numel() != B * K * HW:
+            raise ValueError("q has %d elements, expected B*K*H*W = %d" % (q.numel(), B * K * HW))
+    return z, embed, q, B, K, HW, spatial
+
+
+def gumbel_forward_train(z, prep_buf, embed, tau=1.0, q=None, kl_K=None):
+    """`gumbel_assign` that also keeps the logits (`dvq_vq_gumbel_forward_train_f32`, the same sweep):
+    -> (zq [B, d, *spatial], codes [B, *spatial] i64, kl [1], logits [B, K, *spatial]).  zq, codes and kl are gumbel_assign's bits;
+    logits are the fp32 values the sweep compares, in the layout of q -- what `gumbel_backward_logits` reads."""
+    z, embed, q, B, K, HW, spatial = _gumbel_shape(z, embed, q)
+    C, d, dev, tau = z.shape[1], embed.shape[1], z.device, float(tau)
+    if q is not None and not (tau > 0.0 and math.isfinite(tau)):
+        raise ValueError("tau must be finite and positive when q is given, got %r" % tau)
+    zq = torch.empty((B, d) + spatial, dtype=torch.float32, device=dev)
+    codes = torch.empty((B,) + spatial, dtype=torch.int64, device=dev)
+    kl = torch.empty(1, dtype=torch.float32, device=dev)
+    logits = torch.empty((B, K) + spatial, dtype=torch.float32, device=dev)
+    if B * HW == 0:
+        return zq, codes, kl, logits
+    ws = torch.empty(checked.dvq_vq_gumbel_assign_workspace_bytes(B, HW), dtype=torch.uint8, device=dev)
+    with _lib.on_device(dev):
+        checked.dvq_vq_gumbel_forward_train_f32(
+            z.data_ptr(), prep_buf.data_ptr(), embed.data_ptr(), B, C, HW, K, d, tau, float(K if kl_K is None else kl_K),
+            _lib.ptr(q), zq.data_ptr(), codes.data_ptr(), kl.data_ptr(), logits.data_ptr(), ws.data_ptr(), ws.numel(),
+            _lib.stream_ptr(dev))
+    return zq, codes, kl, logits
+
+
+def gumbel_backward_logits(logits, q=None, u=None, g_kl=None, tau=1.0, kl_K=None, out=None):
+    """dL/dlogits [B, K, *spatial] of GumbelQuantize's hard form (`dvq_vq_gumbel_backward_f32`) from the saved logits, the forward's
+    variates q (or None), u = embed . dL/dz_q in the logits' layout (None: no gradient through z_q) and g_kl, dL/dkl as a GPU tensor of
+    one float (None: no gradient through the KL term; it is never brought to the host).  out None: the result is written over u
+    where u is given (u is consumed), into a new tensor otherwise."""
+    logits = _lib.require_cuda_f32(logits, "logits")
+    if logits.dim() < 2:
+        raise ValueError("logits must be [B, K, ...]")
+    B, K = logits.shape[:2]
+    HW = logits[0, 0].numel() if logits.dim() > 2 else 1
+    for name, t in (("q", q), ("u", u)):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device != logits.device or t.dtype != torch.float32
+                              or not t.is_contiguous() or t.numel() != logits.numel()):
+            raise ValueError("%s must be a contiguous float32 GPU tensor of the logits' %d elements" % (name, logits.numel()))
+    if g_kl is not None:
+        g_kl = _lib.require_cuda_f32(g_kl, "g_kl").reshape(-1)
+        if g_kl.numel() != 1:
+            raise ValueError("g_kl must hold one float")
+    if out is None:
+        out = u if u is not None else torch.empty_like(logits)
+    elif not isinstance(out, torch.Tensor) or out.device != logits.device or out.dtype != torch.float32 or not out.is_contiguous() \
+            or out.numel() != logits.numel():
+        raise ValueError("out must be a contiguous float32 tensor of the logits' %d elements on %s" % (logits.numel(), logits.device))
+    if logits.numel() == 0:
+        return out
+    with _lib.on_device(logits.device):
+        checked.dvq_vq_gumbel_backward_f32(logits.data_ptr(), _lib.ptr(q), _lib.ptr(u), _lib.ptr(g_kl), B, HW, K, float(tau),
+                                           float(K if kl_K is None else kl_K), out.data_ptr(), 0, 0, _lib.stream_ptr(logits.device))
+    return out
+
+
+class _GumbelQuantizeHard(torch.autograd.Function):
+    """GumbelQuantize's hard (straight-through) form as one differentiable op: the forward is the sweep that keeps the logits, the
+    backward one streaming kernel down to the logits and vendor GEMMs from there."""
+
+    @staticmethod
+    def forward(ctx, z, weight, bias, embed, prep_buf, tau, q, kl_K):
+        zq, codes, kl, logits = gumbel_forward_train(z, prep_buf, embed.detach(), tau, q, kl_K)
+        ctx.save_for_backward(z, q, logits, codes, weight, embed)
+        # The backward does not read the image.  The reference is kept so that the buffer outlives the sweep queued against it: a
+        # training-mode module rebuilds its image per call into a FRESH buffer (PreparedImage.rebuild) and keeps only the last few
+        # retired ones alive, while a caller of gumbel_quantize may drop its own reference at once
+        ctx.prep_buf = prep_buf
+        ctx.tau, ctx.kl_K = float(tau), kl_K
+        ctx.mark_non_differentiable(codes)
+        ctx.set_materialize_grads(False)             # an output nobody uses arrives as None, and its term is left out
+        return zq, codes, kl
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_zq, g_codes, g_kl):
+        z, q, logits, codes, weight, embed = ctx.saved_tensors
+        need_z, need_w, need_b, need_e = ctx.needs_input_grad[:4]
+        K, C = weight.shape[:2]
+        G = None if g_zq is None else g_zq.contiguous()          # (a decoder may hand back channels_last)
+        B, HW = logits.shape[0], logits[0, 0].numel()
+        dz = dw = db = de = None
+        if need_z or need_w or need_b:
+            # u [B, K, HW] = embed [K, d] x G [B, d, HW] and dz [B, C, HW] = W^T [C, K] x dl [B, K, HW]: batched GEMMs that write the
+            # NCHW layout themselves (an einsum may hand back a permuted view, and making that contiguous is one more [N, K] pass)
+            u = None if G is None else torch.matmul(embed, G.view(B, embed.shape[1], HW)).view(logits.shape)
+            dl = gumbel_backward_logits(logits, q, u, g_kl, ctx.tau, ctx.kl_K)      # over u
+            if need_z:
+                dz = torch.matmul(weight.reshape(K, C).t(), dl.view(B, K, HW)).view(z.shape)
+            if need_w:
+                dw = torch.einsum("bkhw,bchw->kc", dl, z).reshape(weight.shape)
+            if need_b:
+                db = dl.sum((0, 2, 3))
+        if need_e:
+            de = torch.zeros_like(embed) if G is None else code_sums(G, codes, K)[1]
+        return dz, dw, db, de, None, None, None, None
+
+
+def gumbel_quantize(z, proj_weight, proj_bias, embed, prep_buf, tau, q, kl_K=None):
+    """GumbelQuantize's hard form, differentiable: z [B, C, H, W] f32 GPU, proj_weight [K, C] or [K, C, 1, 1], proj_bias [K] or None,
+    embed [K, d], prep_buf the image of (proj_weight, proj_bias) from `dvq_gumbel_prepare_f32`, q the Exp(1) variates [B, K, H, W]
+    or None -> (z_q [B, d, H, W], codes [B, H, W] i64, kl [1]).  The forward's values are `gumbel_assign`'s bits.  Gradients reach z,
+    proj_weight, proj_bias (through the soft y = softmax((logits - log q) / tau) and the KL term) and embed (the sum of dL/dz_q over
+    each code's tokens: `code_sums`, which honours `set_deterministic`).  No double backward; codes carry no gradient."""
+    if z.dim() != 4:
+        raise ValueError("z must be [B, C, H, W]")
+    return _GumbelQuantizeHard.apply(z, proj_weight, proj_bias, embed, prep_buf, tau, q, kl_K)
+
+
 class GumbelQuantize(InvalidatesPrepared, nn.Module):
     """Reference modules/vector_quantization/quantize_vqgan.py:110-210 (Gumbel-softmax quantizer).
       target: dynamicvectorquantization_amd.quantize.GumbelQuantize
@@ -1704,8 +1829,17 @@ class GumbelQuantize(InvalidatesPrepared, nn.Module):
     draws them, and `gumbel_assign` does the rest in one call: proj, Gumbel argmax, KL term, z_q = embed[ind].
     Every other case (soft training, recorded autograd, remap, return_logits, other widths) runs the reference's arithmetic as
     differentiable torch ops on the GPU.  CPU tensors raise DvqError.  `q=` passes the variates explicitly ([B, K, H, W]; with
-    remap: [B, len(used), H, W]).  There is no fused backward."""
+    remap: [B, len(used), H, W]).
+
+    Fused training step -- `fused_backward = True` (off by default; `GumbelQuantizeFused` is the class with it on): with autograd
+    recording and otherwise the conditions of the fused path (hard one-hot, no remap, return_logits false, f32, a kernel width) the
+    forward is the same sweep, which then also writes the logits, and the backward is one streaming kernel down to dL/dlogits with
+    vendor GEMMs behind it (`gumbel_quantize`; last_path == "fused_train").  z_q, diff and the codes are the fused forward's bits; the
+    gradients are the hard form's (the one-hot's value, the soft y's gradient; embed receives the sum of dL/dz_q per code, without
+    the reference's factor fl(fl(1 - y) + y), which is within 2^-23 of 1).  The soft form (straight_through=False), remap,
+    return_logits, other widths, 16-bit input and double backward stay on torch ops."""
     _prepared = ("_proj_img",)
+    fused_backward = False                          # True: the hard form trains on the kernels
 
     def __init__(self, num_hiddens, embedding_dim, n_embed, straight_through=True,
                  kl_weight=5e-4, temp_init=1.0, use_vqinterface=True,
@@ -1733,7 +1867,7 @@ class GumbelQuantize(InvalidatesPrepared, nn.Module):
         else:
             self.re_embed = n_embed
         self._proj_img = PreparedImage()
-        self.last_path = None                       # "fused" / "torch": what the last forward ran
+        self.last_path = None                       # "fused" / "fused_train" / "torch": what the last forward ran
 
     def invalidate_proj_cache(self):
         """call after writing proj.weight / proj.bias through `.data` in eval mode"""
@@ -1786,6 +1920,7 @@ class GumbelQuantize(InvalidatesPrepared, nn.Module):
             w2.data_ptr(), _lib.ptr(b2), K, C, pbuf, size, stream))
 
     def _fusable(self, z, hard, return_logits):
+        """False, "fused" (autograd is not recording) or "fused_train" (it is, and fused_backward is set)"""
         if not hard or self.remap is not None or return_logits or z.dtype != torch.float32 or z.dim() != 4:
             return False
         if self.proj.in_channels not in (64, 128, 256) or self.proj.weight.dtype != torch.float32:
@@ -1793,8 +1928,8 @@ class GumbelQuantize(InvalidatesPrepared, nn.Module):
         if torch.is_grad_enabled():
             tensors = [z, self.proj.weight, self.embed.weight] + ([] if self.proj.bias is None else [self.proj.bias])
             if any(t.requires_grad for t in tensors):
-                return False
-        return True
+                return "fused_train" if self.fused_backward and self.embed.weight.dtype == torch.float32 else False
+        return "fused"
 
     def forward(self, z, temp=None, return_logits=False, q=None):
         # force hard = True when we are in eval mode, as we must quantize
@@ -1802,12 +1937,17 @@ class GumbelQuantize(InvalidatesPrepared, nn.Module):
         temp = self.temperature if temp is None else temp
         if not isinstance(z, torch.Tensor) or not z.is_cuda:
             raise _lib.DvqError("z is on %s: the dvq kernels run on the GPU only (no CPU fallback)" % getattr(z, "device", None))
-        if self._fusable(z, hard, return_logits):
-            self.last_path = "fused"
+        path = self._fusable(z, hard, return_logits)
+        if path:
+            self.last_path = path
             B, _, H, W = z.shape
             if q is None:
                 q = torch.empty(B, self.n_embed, H, W, device=z.device).exponential_()
-            z_q, ind, kl = gumbel_assign(z, self._proj_image(), self.embed.weight.detach(), float(temp), q, self.n_embed)
+            if path == "fused_train":
+                z_q, ind, kl = gumbel_quantize(z, self.proj.weight, self.proj.bias, self.embed.weight, self._proj_image(), float(temp),
+                                               q, self.n_embed)
+            else:
+                z_q, ind, kl = gumbel_assign(z, self._proj_image(), self.embed.weight.detach(), float(temp), q, self.n_embed)
             diff = self.kl_weight * kl[0]
             logits = None
         else:
@@ -1852,6 +1992,13 @@ class GumbelQuantize(InvalidatesPrepared, nn.Module):
         if self.remap is not None:
             indices = self.unmap_to_all(indices)
         return self.embed(indices).permute(0, 3, 1, 2).contiguous()
+
+
+class GumbelQuantizeFused(GumbelQuantize):
+    """GumbelQuantize with the fused training step on (`fused_backward = True`): the same constructor, forward and state_dict keys,
+    for configurations that can name a class but cannot set an attribute.
+      target: dynamicvectorquantization_amd.quantize.GumbelQuantizeFused"""
+    fused_backward = True
 
 
 class CodeUsage:

@@ -37,6 +37,9 @@
  *          Added later under the same version number (detect them by their symbols): dvq_code_sums_det, dvq_vq_backward_codebook_det_f32
  *          and their *_workspace_bytes queries -- the per-code sums of the training step (EMA statistics, codebook gradient) in one
  *          documented, fixed summation order, without float atomics.  Nothing else changed.
+ *          Added later still, also under 0.20.0: dvq_vq_gumbel_forward_train_f32 and dvq_vq_gumbel_backward_f32 -- GumbelQuantize's training
+ *          step in its hard form: the sweep of dvq_vq_gumbel_assign_f32 that also writes the logits, and the streaming kernel that turns
+ *          them, the variates and embed . dL/dz_q into dL/dlogits.  Nothing else changed.
  *   0.19.0 DVQ_FEATURES(dtype): dvq_route_select_dual_f32, dvq_route_select_triple_f32 and dvq_router_gate_f32 take fp16 / bf16 branch
  *          features when DVQ_FEATURES(DVQ_DTYPE_F16 / DVQ_DTYPE_BF16) is OR-ed into their enumerated argument (gate_dtype, activation);
  *          the h_* / h_out parameters of the three are declared `const void *` / `void *` for that (binary- and source-compatible
@@ -897,6 +900,43 @@ DVQ_API size_t dvq_vq_gumbel_assign_workspace_bytes(int B, int HW);
 DVQ_API int dvq_vq_gumbel_assign_f32(const float *z, const void *prep, const float *embed, int B, int C, int HW, int K, int d,
                                      float tau, float kl_K, const float *q, float *zq, int64_t *codes, float *kl,
                                      void *ws, size_t ws_bytes, void *stream);
+
+/*
+ * GumbelQuantize, the training step of the hard (straight-through) form: a forward that keeps the logits, and the backward down to them.
+ * Replaces: what autograd records for GumbelQuantize.forward (quantize_vqgan.py:171-200) and replays backwards -- the one-hot einsum,
+ *           F.gumbel_softmax's softmax and divide, the second softmax, log and sum of the KL term: ten passes over [N, K] floats and
+ *           their saved [N, K] tensors, and as many again.  Here one [N, K] tensor (the logits) is saved next to the variates q.
+ *
+ * dvq_vq_gumbel_forward_train_f32 -- dvq_vq_gumbel_assign_f32 with one more output:
+ *   logits [B, K, HW] (the layout of q), not null: l_k as defined there, bit for bit what the sweep compares.  Every other argument, the
+ *   prep image (dvq_gumbel_prepare_f32), the workspace (dvq_vq_gumbel_assign_workspace_bytes), the checks and their words are that
+ *   entry point's; codes, zq and kl are its bits.  DVQ_EINVAL also for a null or misaligned logits.
+ *
+ * dvq_vq_gumbel_backward_f32 -- dlogits [B, K, HW] from the saved logits; per token n, N = B HW:
+ *   s_k  = fl(fl(l_k - logf(q_k)) / tau)  (q == NULL: fl(l_k / tau)): the forward's operations in the forward's order
+ *   y    = softmax(s), p = softmax(l), delta = sum_k y_k u_k, KL_n = sum_k p_k log(p_k kl_K)
+ *   dl_k = y_k (u_k - delta) / tau  +  (g_kl[0] / N) p_k (log p_k + log kl_K - KL_n)
+ *   logits [B, K, HW]; q nullable [B, K, HW], the forward's variates (not read when u is NULL)
+ *   u      nullable [B, K, HW]: u[b, k, hw] = embed[k, :] . G[b, :, hw], G = dL/dz_q -- the hard form's straight-through gradient, a GEMM
+ *          the caller makes; NULL: no gradient arrives through z_q and the first term is left out
+ *   g_kl   nullable, a DEVICE pointer to one float, dL/dkl of the forward's kl[0] (the mean over tokens); NULL: the second term is left out.
+ *          u and g_kl both NULL: dlogits is zero-filled
+ *   tau    finite, > 0 when u is given;  kl_K finite, > 0 when g_kl is given (the value cancels: log kl_K stands in KL_n as well)
+ *   dlogits may be u itself (the same lane reads u_k and then writes dl_k over it), and nothing else: its B K HW floats may not
+ *          overlap logits, q or g_kl anywhere, nor u at an offset (DVQ_EINVAL: the ranges are compared, not only the pointers)
+ *   ws, ws_bytes: reserved, not read (pass NULL, 0): the kernel keeps its partial sums in LDS
+ *   A term with p_k == 0 is 0 (a code whose logit is -inf gets exactly 0, as torch gives).  A token whose logits are all -inf, or hold a
+ *   NaN, has NaN in every dl_k, as the torch chain has.
+ * DVQ_EINVAL: null logits / dlogits, a non-positive size, tau / kl_K as above, a misaligned pointer, dlogits overlapping logits, q, g_kl, or u other than as a whole.
+ * DVQ_EUNSUPPORTED: B * HW >= 2^31 or B * HW * K >= 2^40.  Any K.  One launch, no atomics, no host synchronisation, no allocation;
+ * vector stores only; the same bits run to run.  dW, db, dz are GEMMs of the caller on dlogits; dembed is dvq_code_sums_det /
+ * dvq_ema_accumulate_nchw_f32 of G under the forward's codes.
+ */
+DVQ_API int dvq_vq_gumbel_forward_train_f32(const float *z, const void *prep, const float *embed, int B, int C, int HW, int K, int d,
+                                            float tau, float kl_K, const float *q, float *zq, int64_t *codes, float *kl,
+                                            float *logits, void *ws, size_t ws_bytes, void *stream);
+DVQ_API int dvq_vq_gumbel_backward_f32(const float *logits, const float *q, const float *u, const float *g_kl, int B, int HW, int K,
+                                       float tau, float kl_K, float *dlogits, void *ws, size_t ws_bytes, void *stream);
 
 /*
  * Nearest-codebook assignment at the NARROW widths D = 4, 8, 16: codes, z_q and the commitment loss in one exact kernel.

@@ -7,7 +7,8 @@
       whose behaviour is to be pinned (DVQ_LIBRARY=<path> selects another build than csrc/libdvq.so).
       The entry points of DET_FNS (dvq_code_sums_det, dvq_vq_backward_codebook_det_f32: ordinary status calls) have a table of their
       own, tests/golden/abi_rejections_det.json (--det-o), written in the same run: the first table is kept byte for byte as it was
-      when they were added, and a later change that may touch it can merge the two.
+      when they were added, and a later change that may touch it can merge the two.  GUMBEL_TRAIN_FNS (GumbelQuantize's training
+      step) likewise: tests/golden/abi_rejections_gumbel_train.json (--gumbel-train-o).
   tools/gen_golden_abi_rejections.py --replay table.json
       makes the table's calls again and prints [[rc, message], ...] as JSON (tests/test_abi_rejections.py compares).
 
@@ -34,6 +35,8 @@ LIB = os.environ.get("DVQ_LIBRARY") or os.path.join(ROOT, "dynamicvectorquantiza
 GOLDEN = os.path.join(ROOT, "tests", "golden", "abi_rejections.json")
 GOLDEN_DET = os.path.join(ROOT, "tests", "golden", "abi_rejections_det.json")
 DET_FNS = ("dvq_code_sums_det", "dvq_vq_backward_codebook_det_f32")     # their rows go to GOLDEN_DET
+GOLDEN_GUMBEL_TRAIN = os.path.join(ROOT, "tests", "golden", "abi_rejections_gumbel_train.json")
+GUMBEL_TRAIN_FNS = ("dvq_vq_gumbel_forward_train_f32", "dvq_vq_gumbel_backward_f32")     # and theirs to GOLDEN_GUMBEL_TRAIN
 _CTYPES = {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64,
            "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t}
 REFUSALS = (-1, -2, -3)          # DVQ_EINVAL, DVQ_EUNSUPPORTED, DVQ_EWORKSPACE
@@ -236,6 +239,20 @@ ladder("dvq_code_sums_det", d(dtype=0, z=2, D=4, K=16385), d(K=16384), d(z=4, D=
 ladder("dvq_vq_backward_codebook_det_f32", d(g_loss=0, B=0, D=6, K=20000, codebook=8, ws=16, ws_bytes=0), d(g_loss=P), d(B=1), d(D=8), d(K=8193),
        d(codebook=P), d(ws_bytes=BIG), d(ws=0), d(ws=P, g_weight=0))
 
+# GumbelQuantize's training step: a table of their own (GOLDEN_GUMBEL_TRAIN).  The forward is the sweep's checked body: the same ladder,
+# and the logits that may be neither null nor misaligned; the backward's checks in their order
+ladder("dvq_vq_gumbel_forward_train_f32", d(z=0, B=0, C=100, K=64, d=0, tau=0.0, kl_K=0.0, ws=0, ws_bytes=9, logits=2), d(z=2), d(B=1), d(d=8), WIDE,
+       d(C=64), d(tau=0.5), d(kl_K=float("inf")), d(kl_K=64.0), ONE, d(z=P), d(logits=P, codes=4), d(codes=P), d(ws=16, ws_bytes=0), d(ws_bytes=BIG))
+ladder("dvq_vq_gumbel_forward_train_f32", d(C=64, K=64, d=8, logits=0))
+ladder("dvq_vq_gumbel_backward_f32", d(logits=0, B=0, K=1 << 11, tau=0.0, kl_K=0.0, dlogits=2), d(logits=8), d(B=1 << 20, HW=1 << 12), d(tau=float("nan")),
+       d(tau=2.0), d(kl_K=float("inf")), d(kl_K=8.0), d(B=1 << 10, HW=1 << 20), d(B=1, HW=1), d(dlogits=8), d(logits=P, dlogits=P, q=2),
+       d(q=P, u=2), d(u=P, g_kl=1), d(g_kl=P))
+ladder("dvq_vq_gumbel_backward_f32", d(logits=P, dlogits=512, q=512), d(q=P, HW=0), d(HW=1, dlogits=0))
+# overlap is a matter of ranges (B HW K floats), not of equal pointers: logits, q, g_kl inside dlogits, u at an offset
+_span = d(B=4, HW=4, K=4, logits=1 << 12, q=1 << 13, u=1 << 14, g_kl=1 << 15, dlogits=1 << 16)
+ladder("dvq_vq_gumbel_backward_f32", d(_span, dlogits=(1 << 12) + 252), d(dlogits=(1 << 12) - 252), d(dlogits=(1 << 13) + 4), d(dlogits=(1 << 15) - 252),
+       d(dlogits=(1 << 14) + 8), d(dlogits=(1 << 14) - 8))
+
 
 def rows(protos):
     out = []
@@ -260,6 +277,7 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("-o", default=GOLDEN)
     ap.add_argument("--det-o", default=GOLDEN_DET)
+    ap.add_argument("--gumbel-train-o", default=GOLDEN_GUMBEL_TRAIN)
     ap.add_argument("--replay", metavar="TABLE")
     a = ap.parse_args()
     os.environ["HIP_VISIBLE_DEVICES"] = os.environ["ROCR_VISIBLE_DEVICES"] = ""      # before the library and the HIP runtime load
@@ -279,7 +297,8 @@ def main():
             table.append(dict(r, rc=rc, message=msg))
     missing = set(protos) - {r["fn"] for r in table}
     assert not missing, "entry points without a row: %s" % sorted(missing)
-    for path, part in ((a.o, [r for r in table if r["fn"] not in DET_FNS]), (a.det_o, [r for r in table if r["fn"] in DET_FNS])):
+    for path, part in ((a.o, [r for r in table if r["fn"] not in DET_FNS + GUMBEL_TRAIN_FNS]), (a.det_o, [r for r in table if r["fn"] in DET_FNS]),
+                       (a.gumbel_train_o, [r for r in table if r["fn"] in GUMBEL_TRAIN_FNS])):
         with open(path, "w") as f:                            # a row per line
             f.write("[\n" + ",\n".join(json.dumps(r) for r in part) + "\n]\n")
         print("%d refusals of %d entry points -> %s" % (len(part), len({r["fn"] for r in part}), path))

@@ -6,6 +6,14 @@ the logits, and the variates q, are 1 GiB each).  Timed: the module's forward (d
 tests' fixture.  One JSON line, the whole record to --out.
 
     python tools/gumbel_prof.py [--iters 20] [--warmup 5] [--batch 256] [--out profiles/gumbel.json]
+
+--train: the training leg instead -- forward + backward of the SAME module in training mode with `fused_backward` off (the torch-op
+chain under autograd) and on (the sweep that keeps the logits, the streaming backward kernel, vendor GEMMs), in the same run: HIP
+events, median of --iters after --warmup, and torch.cuda.max_memory_allocated of each, at B = 256, C = 256, 32 x 32, K = 1024,
+d = 256 and at B = 16, C = 256, 32 x 32, K = 8192, d = 256.  The loss is sum(z_q G) + diff with a fixed G ~ N(0, 1); the draw of the
+variates is inside both.
+
+    python tools/gumbel_prof.py --train [--iters 20] [--warmup 5] [--out profiles/gumbel_train.json]
 """
 import argparse
 import json
@@ -49,14 +57,60 @@ def chain_forward(z, proj, embed, n_embed, kl_weight, temp):
     return z_q, diff, ind
 
 
+TRAIN_SHAPES = ((256, 256, 32, 32, 1024, 256), (16, 256, 32, 32, 8192, 256))     # B, C, H, W, K, d
+
+
+def train_leg(dev, iters, warmup):
+    rec = {"tool": "tools/gumbel_prof.py --train", "iters": iters, "warmup": warmup, "shapes": []}
+    for B, C, H, W, K, d in TRAIN_SHAPES:
+        torch.manual_seed(4302)
+        m = GumbelQuantize(C, d, K).to(dev).train()
+        with torch.no_grad():
+            m.proj.weight.normal_(0.0, 1.5 / C ** 0.5)
+            m.proj.bias.normal_(0.0, 0.5)
+        z = torch.randn(B, C, H, W, device=dev, requires_grad=True)
+        G = torch.randn(B, d, H, W, device=dev)
+        one = torch.ones((), device=dev)
+
+        def step():
+            z.grad = None
+            for p in m.parameters():
+                p.grad = None
+            z_q, diff, _ = m(z)
+            torch.autograd.backward([z_q, diff], [G, one])
+
+        row = {"B": B, "C": C, "H": H, "W": W, "K": K, "d": d, "N": B * H * W, "logits_bytes": B * H * W * K * 4}
+        for name, flag in (("torch", False), ("fused", True)):
+            m.fused_backward = flag
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats(dev)
+            ms = median_ms(step, iters, warmup)
+            assert m.last_path == ("fused_train" if flag else "torch"), m.last_path
+            row[name + "_ms"] = round(ms, 4)
+            row[name + "_max_memory_allocated"] = int(torch.cuda.max_memory_allocated(dev))
+        row["speedup"] = round(row["torch_ms"] / row["fused_ms"], 2)
+        rec["shapes"].append(row)
+        del m, z, G
+        torch.cuda.empty_cache()
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true")
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=256)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.train:
+        rec = train_leg(dev, a.iters, a.warmup)
+        print(json.dumps(rec), flush=True)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(rec, f, indent=1)
+        return
     B, C, H, W, K, d = a.batch, 256, 32, 32, 1024, 256
     N = B * H * W
     torch.manual_seed(4301)
