@@ -4,6 +4,9 @@ fixtures.  Imports no reference code.
   table64(E, W, b)      T = E W^T + b in float64 (W [C, D], b nullable)
   magnitude(E, W, b)    M = |E| |W|^T + |b|: what the conv's error bound is relative to
   head(T, F, L, codes)  fl(fl(T[codes] + F) + L) in float32 ops, NCHW; NaN rows for codes outside [0, rows)
+For tests/test_decode_shapes.py: form() / blocks() restate the head's launch dispatch, HEAD_CASES / case_items() the case table and
+what each case reaches, TABLE_CASES / table_inputs() / table_rel() / table_chain32() the table kernel's cases, bound and CPU chain,
+Guarded / at_offset() / same_bits() the pre-poisoned device buffers and the bit comparison.
 """
 import json
 import os
@@ -58,6 +61,165 @@ def bound(M, T, F, L, codes, conv_rel):
         if P is not None:
             mag = mag + np.abs(np.asarray(P, dtype=np.float64))[None]
     return conv_rel * gather_nchw(M, codes) + 4.0 * EPS * mag
+
+
+# ---- the launch dispatch of dvq_launch_decode_head, restated, and the case table of tests/test_decode_shapes.py ------------
+TOK, CH = 64, 64                                  # tokens x channels of one workgroup
+
+
+def form(B, C, H, W, off_out=0, off_F=0, off_L=0):
+    """"vec" (16 bytes per lane along the token axis) or "scalar" (lane = token, 4-byte accesses).  off_*: the byte offset of
+    that base from 16-byte alignment; a table that is not passed is a NULL pointer, i.e. offset 0."""
+    aligned = all(int(o) % 16 == 0 for o in (off_out, off_F, off_L))
+    return "vec" if (H * W) % 4 == 0 and aligned else "scalar"
+
+
+def blocks(B, C, H, W):
+    """the grid: (token blocks, channel blocks)"""
+    return (-(-B * H * W // TOK), -(-C // CH))
+
+
+# (B, C, H, W, off_out, off_F, off_L): the smallest shapes that reach each item of FORM_ITEMS / TOKEN_ITEMS / CHANNEL_ITEMS
+HEAD_CASES = (
+    (1, 4, 2, 2, 0, 0, 0), (3, 68, 2, 2, 0, 0, 0), (5, 60, 4, 3, 0, 0, 0), (2, 132, 6, 6, 0, 0, 0), (17, 64, 2, 2, 0, 0, 0),
+    (1, 1024, 2, 4, 0, 0, 0),
+    (1, 68, 1, 3, 0, 0, 0), (3, 132, 3, 7, 0, 0, 0), (5, 60, 1, 13, 0, 0, 0), (67, 8, 1, 1, 0, 0, 0), (2, 1024, 1, 1, 0, 0, 0),
+    (3, 68, 2, 6, 4, 0, 0), (3, 68, 2, 6, 0, 4, 0), (3, 68, 2, 6, 0, 0, 4),
+)
+FORM_ITEMS = ("vec", "scalar: HW % 4 != 0", "scalar: out off", "scalar: F off", "scalar: L off")
+TOKEN_ITEMS = ("N < 64", "N % 64 == 1, N > 64", "N % 64 == 63", "a block holds several whole images",
+               "a block boundary strictly inside an image", "HW == 1, N > 64")
+CHANNEL_ITEMS = ("C == 4", "4 < C < 64", "C % 64 == 4, C > 64", "C == 1024")
+
+
+def case_items(case):
+    """the items of the three lists that one case of HEAD_CASES reaches"""
+    B, C, H, W, oo, of, ol = case
+    HW, N = H * W, B * H * W
+    got = set()
+    if form(*case) == "vec":
+        got.add("vec")
+    else:
+        assert form(B, C, H, W) == "vec" or (oo, of, ol) == (0, 0, 0), "one cause per scalar case"
+        if HW % 4:
+            got.add("scalar: HW % 4 != 0")
+        for off, name in ((oo, "out"), (of, "F"), (ol, "L")):
+            if off % 16 and sum(1 for o in (oo, of, ol) if o % 16) == 1:
+                got.add("scalar: %s off" % name)
+    if N < 64:
+        got.add("N < 64")
+    if N > 64 and N % 64 == 1:
+        got.add("N % 64 == 1, N > 64")
+    if N % 64 == 63:
+        got.add("N % 64 == 63")
+    for n0 in range(0, N, TOK):
+        n1 = min(n0 + TOK, N)
+        first = -(-n0 // HW)                                             # the first image that starts inside the block
+        if (first + 2) * HW <= n1:
+            got.add("a block holds several whole images")
+        if n0 and n0 % HW:
+            got.add("a block boundary strictly inside an image")
+    if HW == 1 and N > 64:
+        got.add("HW == 1, N > 64")
+    if C == 4:
+        got.add("C == 4")
+    if 4 < C < 64:
+        got.add("4 < C < 64")
+    if C > 64 and C % 64 == 4:
+        got.add("C % 64 == 4, C > 64")
+    if C == 1024:
+        got.add("C == 1024")
+    return got
+
+
+# ---- the table kernel's cases, inputs and bound ---------------------------------------------------------------------------
+TABLE_CASES = ((1, 1, 4), (7, 3, 6), (8, 256, 68), (9, 1024, 260), (13, 96, 4), (17, 24, 1024))      # (rows, D, C)
+
+
+def table_inputs(rdc, bias):
+    """E [rows, D] ~ N(0, 1), W [C, D] ~ N(0, 1/16), b [C] ~ N(0, 0.1) or None"""
+    from dynamicvectorquantization_amd import synth
+    rows, D, C = rdc
+    seed = 5000 + 16 * TABLE_CASES.index(tuple(rdc))
+    E = synth.normal(seed, (rows, D), 0.0, 1.0)
+    W = synth.normal(seed + 1, (C, D), 0.0, 1.0 / 16.0)
+    return E, W, (synth.normal(seed + 2, (C,), 0.0, 0.1) if bias else None)
+
+
+def table_rel(D):
+    """min(1e-5, (D + 2) 2^-24): the conv contract of include/dvq.h, and D fmas plus one add at one rounding each, every
+    partial sum bounded by M; the +2 absorbs the second-order terms.  Relative to M = |E||W|^T + |b|."""
+    return min(1e-5, (D + 2) * EPS)
+
+
+def table_chain32(E, W, b=None):
+    """the kernel's documented arithmetic on the CPU: acc = 0; for k ascending acc = fl(W[o, k] E[r, k] + acc); then fl(acc + b).
+    The product of two float32 is exact in float64, so fl32(fl64(p + acc)) is the fma up to a double rounding."""
+    rows, D = E.shape
+    acc = np.zeros((rows, W.shape[0]), np.float32)
+    E64, W64 = E.astype(np.float64), W.astype(np.float64)
+    for k in range(D):
+        acc = (E64[:, k, None] * W64[None, :, k] + acc.astype(np.float64)).astype(np.float32)
+    return acc if b is None else (acc + b.astype(np.float32)[None, :]).astype(np.float32)
+
+
+# ---- guarded device buffers ---------------------------------------------------------------------------------------------
+SENTINEL = 0x7FE5C3D1                             # a quiet NaN with a payload no arithmetic here produces; compared as bits
+GUARD_WORDS = 1024                                # 4 KiB on each side
+BAD_CODES = (-1, None, 2 ** 32, 2 ** 32 + 5, 2 ** 40, -2 ** 63, 2 ** 63 - 1)          # None: `rows` itself
+
+
+def bad_codes(rows):
+    return np.array([rows if v is None else v for v in BAD_CODES], dtype=np.int64)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+class Guarded:
+    """n float32 words inside a larger device buffer, all of it pre-filled with SENTINEL; `view` starts `off` bytes past a
+    16-byte boundary.  tail_words more words after the view belong to the guard but lie inside what the callee was given (the
+    padding of a table)."""
+
+    def __init__(self, dev, n, off=0, tail_words=0):
+        import torch
+        assert off % 4 == 0
+        self.front, self.n = GUARD_WORDS + off // 4, n
+        self.whole = torch.full((self.front + n + tail_words + GUARD_WORDS + 4,), SENTINEL, dtype=torch.int32, device=dev)
+        assert self.whole.data_ptr() % 16 == 0
+        self.view = self.whole[self.front:self.front + n].view(torch.float32)
+        assert self.view.data_ptr() % 16 == off % 16
+
+    def result(self):
+        """the n words as uint32, after checking that the guards are intact and that every word inside was written"""
+        w = self.whole.cpu().numpy().view(np.uint32)
+        inside = w[self.front:self.front + self.n]
+        assert self.front >= GUARD_WORDS and len(w) - self.front - self.n >= GUARD_WORDS
+        assert (w[:self.front] == SENTINEL).all(), "a write before the output"
+        assert (w[self.front + self.n:] == SENTINEL).all(), "a write past the output"
+        assert not (inside == SENTINEL).any(), "%d words never written" % int((inside == SENTINEL).sum())
+        return inside.copy()
+
+
+def at_offset(dev, a, off):
+    """the float32 array `a` on the device, its base `off` bytes past a 16-byte boundary"""
+    import torch
+    if a is None:
+        return None
+    buf = torch.zeros(a.size + 4, dtype=torch.float32, device=dev)
+    assert buf.data_ptr() % 16 == 0 and off % 4 == 0 and off < 16
+    v = buf[off // 4:off // 4 + a.size]
+    v.copy_(torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32).reshape(-1)))
+    return v.view(a.shape)
+
+
+def same_bits(got_u32, ref):
+    """uint32 equality on every non-NaN element of the reference, NaN exactly where the reference has one"""
+    ref = np.ascontiguousarray(ref, dtype=np.float32)
+    got = np.asarray(got_u32, dtype=np.uint32).reshape(ref.shape)
+    nan_ref, nan_got = np.isnan(ref), np.isnan(got.view(np.float32))
+    return bool(np.array_equal(nan_ref, nan_got) and np.array_equal(got[~nan_ref], ref.view(np.uint32)[~nan_ref]))
 
 
 def load(name):
