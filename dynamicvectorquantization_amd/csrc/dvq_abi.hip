@@ -1078,11 +1078,12 @@ int dvq_exchange_pack(const int64_t *codes, const int64_t *grain, const float *l
                       int b_max, int64_t codes_per_image, int64_t grain_per_image, int num_codes, void *buf,
                       void *stream)
 {
-    if (!codes || !buf) return null_pointer("dvq_exchange_pack");
+    // an empty shard (b_local == 0: global_batch < world) has nothing to point at: its codes and grain may be null
+    if ((!codes && b_local != 0) || !buf) return null_pointer("dvq_exchange_pack");
     if (b_local < 0 || b_max <= 0 || b_local > b_max || codes_per_image <= 0 || grain_per_image < 0 || num_codes <= 0) {
         dvq_set_error("dvq_exchange_pack: bad sizes"); return DVQ_EINVAL;
     }
-    if (grain_per_image > 0 && !grain) { dvq_set_error("dvq_exchange_pack: null grain"); return DVQ_EINVAL; }
+    if (grain_per_image > 0 && !grain && b_local != 0) { dvq_set_error("dvq_exchange_pack: null grain"); return DVQ_EINVAL; }
     if (((uintptr_t)buf & 7) != 0) { dvq_set_error("dvq_exchange_pack: buffer must be 8-byte aligned"); return DVQ_EINVAL; }
     return hip_rc(dvq_launch_xch_pack((const long long *)codes, grain_per_image > 0 ? (const long long *)grain : nullptr,
                                       loss, numel, b_local, b_max, (long)codes_per_image, (long)grain_per_image,
@@ -1098,6 +1099,9 @@ int dvq_exchange_unpack(const void *gathered, int world, int global_batch, int64
         dvq_set_error("dvq_exchange_unpack: bad sizes"); return DVQ_EINVAL;
     }
     if (grain_per_image > 0 && !grain) { dvq_set_error("dvq_exchange_unpack: null grain"); return DVQ_EINVAL; }
+    if (((uintptr_t)gathered & 7) != 0) {                  // read as shorts, ints and doubles; every rank's slice is a multiple of 8 bytes
+        dvq_set_error("dvq_exchange_unpack: buffer must be 8-byte aligned"); return DVQ_EINVAL;
+    }
     return hip_rc(dvq_launch_xch_unpack(gathered, world, global_batch, (long)codes_per_image, (long)grain_per_image,
                                         num_codes, (long long *)codes, grain_per_image > 0 ? (long long *)grain : nullptr,
                                         mean, (hipStream_t)stream), "exchange_unpack");

@@ -41,12 +41,18 @@ __global__ __launch_bounds__(256) void xch_pack_kernel(const long long *__restri
         if (L.esize == 2) ((short *)buf)[i] = (short)v;
         else ((int *)buf)[i] = (int)v;
     }
-    if (grain != nullptr)
-        for (long i = t0; i < ng; i += stride) buf[L.off_grain + i] = (char)((i < ngl) ? grain[i] : 0);
+    // an empty shard (b_local == 0, ngl == 0) may come with a null grain: its section is zeros all the same
+    for (long i = t0; i < ng; i += stride) buf[L.off_grain + i] = (char)((i < ngl) ? grain[i] : 0);
+    if (t0 < 8) {                                                          // the up-to-7 bytes behind each section
+        const long end_c = nc * L.esize, end_g = L.off_grain + ng;
+        if (end_c + t0 < L.off_grain) buf[end_c + t0] = 0;
+        if (end_g + t0 < L.off_pair) buf[end_g + t0] = 0;
+    }
     if (t0 == 0) {
         double *pair = (double *)(buf + L.off_pair);
-        pair[0] = (loss != nullptr) ? (double)loss[0] * numel : 0.0;       // loss[0] = local mean
-        pair[1] = (loss != nullptr) ? numel : 0.0;
+        const bool has = loss != nullptr && numel != 0.0;                  // no elements: (0, 0) whatever loss[0] holds
+        pair[0] = has ? (double)loss[0] * numel : 0.0;                     // loss[0] = local mean
+        pair[1] = has ? numel : 0.0;
     }
 }
 

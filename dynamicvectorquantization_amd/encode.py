@@ -302,44 +302,68 @@ def all_gather_codes(codes, grain_indices, loss_sum, numel, num_codes, global_ba
     sizes = [shard_slice(global_batch, r, world) for r in range(world)]
     assert sizes[rank][1] - sizes[rank][0] == codes.shape[0]
     bmax = max(e - s for s, e in sizes)
-    wd = _wire_dtype(num_codes)
-    dev = codes.device
-    esize = torch.empty((), dtype=wd).element_size()
     cshape, gshape = tuple(codes.shape[1:]), (tuple(grain_indices.shape[1:]) if grain_indices is not None else None)
-    n_c = bmax * int(torch.Size(cshape).numel()) * esize
-    n_g = bmax * int(torch.Size(gshape).numel()) if gshape is not None else 0
-    n_c_pad = (n_c + 7) // 8 * 8
-    n_g_pad = (n_g + 7) // 8 * 8
-    nbytes = n_c_pad + n_g_pad + 16
-    b_local = codes.shape[0]
-
-    local = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
-    local[:b_local * (n_c // bmax)] = codes.to(wd).contiguous().view(torch.uint8).reshape(-1)
-    if grain_indices is not None:
-        local[n_c_pad:n_c_pad + b_local * (n_g // bmax)] = grain_indices.to(torch.int8).contiguous().view(torch.uint8).reshape(-1)
-    pair = torch.stack([loss_sum.detach().to(torch.float64).reshape(()),
-                        torch.full((), float(numel), dtype=torch.float64, device=dev)])
-    local[n_c_pad + n_g_pad:] = pair.view(torch.uint8)
-    out = torch.empty(world * nbytes, dtype=torch.uint8, device=dev)
+    local = _pack_torch(codes, grain_indices, loss_sum, numel, num_codes, bmax)
+    out = torch.empty(world * local.numel(), dtype=torch.uint8, device=codes.device)
     work = dist.all_gather_into_tensor(out, local, group=group, async_op=async_op)
 
     def unpack():
-        buf = out.view(world, nbytes)
-        c_parts, g_parts = [], []
-        for r, (s, e) in enumerate(sizes):
-            c = buf[r, :n_c].view(wd).reshape((bmax,) + cshape)[: e - s]
-            c_parts.append(c)
-            if gshape is not None:
-                g_parts.append(buf[r, n_c_pad:n_c_pad + n_g].view(torch.int8).reshape((bmax,) + gshape)[: e - s])
-        pairs = buf[:, n_c_pad + n_g_pad:].contiguous().view(torch.float64).reshape(world, 2)
-        tot = pairs.sum(0)                                   # rank order: identical on every rank
-        g_codes = torch.cat(c_parts, 0).to(torch.int64)
-        g_grain = torch.cat(g_parts, 0).to(torch.int64) if gshape is not None else None
-        return g_codes, g_grain, (tot[0] / tot[1]).to(torch.float32)
+        return _unpack_torch(out, world, global_batch, cshape, gshape, num_codes)
 
     if async_op:
         return _PendingGather(work, unpack)
     return unpack()
+
+
+def _wire_layout(cshape, gshape, bmax, num_codes):
+    """(wire dtype, code bytes, padded code bytes, grain bytes, padded grain bytes) of one rank's buffer"""
+    wd = _wire_dtype(num_codes)
+    esize = torch.empty((), dtype=wd).element_size()
+    n_c = bmax * int(torch.Size(cshape).numel()) * esize
+    n_g = bmax * int(torch.Size(gshape).numel()) if gshape is not None else 0
+    return wd, n_c, (n_c + 7) // 8 * 8, n_g, (n_g + 7) // 8 * 8
+
+
+def _pack_torch(codes, grain_indices, loss_sum, numel, num_codes, bmax):
+    """One rank's wire buffer (uint8 [nbytes], zero wherever the format defines no value) through torch ops: what
+    all_gather_codes sends.  No process group is touched.  Without elements (numel == 0) the loss pair is (0, 0)
+    whatever loss_sum holds: an empty shard's mean is not a number, and must not reach the global one."""
+    dev = codes.device
+    cshape, gshape = tuple(codes.shape[1:]), (tuple(grain_indices.shape[1:]) if grain_indices is not None else None)
+    wd, n_c, n_c_pad, n_g, n_g_pad = _wire_layout(cshape, gshape, bmax, num_codes)
+    b_local = codes.shape[0]
+    local = torch.zeros(n_c_pad + n_g_pad + 16, dtype=torch.uint8, device=dev)
+    local[:b_local * (n_c // bmax)] = codes.to(wd).reshape(-1).view(torch.uint8)
+    if grain_indices is not None:
+        local[n_c_pad:n_c_pad + b_local * (n_g // bmax)] = grain_indices.to(torch.int8).reshape(-1).view(torch.uint8)
+    if float(numel) != 0.0:
+        pair = torch.stack([loss_sum.detach().to(torch.float64).reshape(()),
+                            torch.full((), float(numel), dtype=torch.float64, device=dev)])
+        local[n_c_pad + n_g_pad:] = pair.view(torch.uint8)
+    return local
+
+
+def _unpack_torch(gathered, world, global_batch, cshape, gshape, num_codes):
+    """The gathered uint8 [world * nbytes] buffers -> (codes [B, *cshape] int64, grain [B, *gshape] int64 or None, global
+    mean) through torch ops: what all_gather_codes returns.  No process group is touched."""
+    sizes = [shard_slice(global_batch, r, world) for r in range(world)]
+    bmax = max(e - s for s, e in sizes)
+    cshape, gshape = tuple(cshape), (tuple(gshape) if gshape is not None else None)
+    wd, n_c, n_c_pad, n_g, n_g_pad = _wire_layout(cshape, gshape, bmax, num_codes)
+    buf = gathered.view(world, n_c_pad + n_g_pad + 16)
+    c_parts, g_parts = [], []
+    for r, (s, e) in enumerate(sizes):
+        c = buf[r, :n_c].view(wd).reshape((bmax,) + cshape)[: e - s]
+        c_parts.append(c)
+        if gshape is not None:
+            g_parts.append(buf[r, n_c_pad:n_c_pad + n_g].view(torch.int8).reshape((bmax,) + gshape)[: e - s])
+    pairs = buf[:, n_c_pad + n_g_pad:].contiguous().view(torch.float64).reshape(world, 2)
+    tot = torch.zeros(2, dtype=torch.float64, device=gathered.device)
+    for r in range(world):                               # rank order, one addition per rank: identical on every rank
+        tot = tot + pairs[r]
+    g_codes = torch.cat(c_parts, 0).to(torch.int64)
+    g_grain = torch.cat(g_parts, 0).to(torch.int64) if gshape is not None else None
+    return g_codes, g_grain, (tot[0] / tot[1]).to(torch.float32)
 
 
 class CodeExchange:
@@ -352,6 +376,8 @@ class CodeExchange:
         ... next batch's kernels ...
         g_codes, g_grain, g_mean = xch.finish()   # stream-waits for the collective, queues the unpack
 
+    A rank without an image (global_batch < world) passes its empty tensors and loss=None: the pack kernel takes their null
+    pointers, sends zeros and the pair (0, 0), and the rank gets the global tensors like every other.
     CPU tensors (the gloo tests of the host logic) take the torch-op pack of all_gather_codes."""
 
     def __init__(self, codes, grain, num_codes, global_batch, numel_per_image, group=None):

@@ -979,11 +979,13 @@ DVQ_API int dvq_vq_assign_narrow_flat_f32(const float *z, const float *codebook,
  * it runs one process per GPU under Lightning DDP, train.py:230 -- this is what lets downstream consumers
  * (permuter, stage-2 transformer) see the global code tensor).  Per rank one byte buffer of
  * dvq_exchange_bytes(): [codes as int16 (num_codes <= 32768) / int32, b_max images][grain indices as int8]
- * [(loss numerator, element count) as 2 x float64].
+ * [(loss numerator, element count) as 2 x float64]; the first two sections are zero padded to a multiple of
+ * 8 bytes, and pack writes every byte of the buffer.
  *   pack    codes [b_local, codes_per_image] int64, grain [b_local, grain_per_image] int64 (nullable when
- *           grain_per_image == 0), loss nullable ([0] = local mean; numel = local element count);
- *           rows b_local .. b_max-1 are zero padding (ragged shards)
- *   unpack  gathered [world, bytes] -> codes [global_batch, codes_per_image] int64, grain, mean[0] = global
+ *           grain_per_image == 0), loss nullable ([0] = local mean; numel = local element count; the pair is
+ *           (0, 0) without a loss or with numel == 0); rows b_local .. b_max-1 are zero padding (ragged
+ *           shards); an empty shard (b_local == 0) may pass null codes and grain; buf 8-byte aligned
+ *   unpack  gathered [world, bytes], 8-byte aligned -> codes [global_batch, codes_per_image] int64, grain, mean[0] = global
  *           mean (pairs added in rank order: same bits on every rank); shard r holds the images
  *           [r*base + min(r, extra), ...) of global_batch = world*base + extra, b_max = ceil(global_batch / world)
  */

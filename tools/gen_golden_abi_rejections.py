@@ -215,6 +215,9 @@ ladder("dvq_decode_table_prepare_f32", d(codebook=0, rows=0, D=8, C=16, conv_wei
 ladder("dvq_decode_head_f32", d(h_in=0, B=0, C=6, table=8), d(h_in=2), d(B=1), d(C=1028), d(C=8, B=1 << 16, HW=1 << 15), ONE, d(table=P))
 ladder("dvq_exchange_pack", d(buf=0, b_local=2, b_max=1, grain_per_image=1, grain=0), d(buf=4), d(b_local=1), d(grain=P))
 ladder("dvq_exchange_unpack", d(gathered=0, world=0, grain_per_image=1, grain=0), d(gathered=P), d(world=1))
+# null codes and grain are an empty shard's alone (b_local = 0 gets past validation); the gathered buffer is read as doubles
+ladder("dvq_exchange_pack", d(codes=0, b_local=1, grain_per_image=1, grain=0), d(codes=P))
+ladder("dvq_exchange_unpack", d(gathered=4))
 _ortho = [d(t=0, h=0, n=4, d=100, ws=0, ws_bytes=9), d(t=8), d(h=1), d(d=64, n=1 << 24), d(n=4)]
 ladder("dvq_ortho_loss_forward_f32", *_ortho, d(t=P, loss=2), d(loss=P), d(ws=16, ws_bytes=0), d(ws_bytes=BIG))
 ladder("dvq_ortho_loss_backward_f32", d(_ortho[0], grad=8), *_ortho[1:], d(t=P), d(grad=P), d(grad=512), d(ws=16, ws_bytes=0), d(ws_bytes=BIG))
